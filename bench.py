@@ -13,7 +13,11 @@ process has touched the GPU) and relays rank 0's JSON line; launched by torchrun
 ranks.  The batch is sharded (weak scaling, per-GPU batch fixed) and gradients are all-reduced over
 RCCL (backend "nccl" on ROCm) -- `src/distribute_utils.py:97-188`, `src/tasks/pretraining.py:273`.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the step figures;
+`--full` adds the side measurements (HIP-event rooflines of one attention forward and backward call, the CPU
+baselines).  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32): the
+step's returned tensors and, for the train step, the parameters it updated -- whole up to DUMP_SAMPLE elements,
+a fixed seeded sample of larger ones -- so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -34,6 +38,29 @@ XGMI_LINK_GBS = 153.0        # per xGMI link, 7 links per GPU
 
 
 F32_MFMA_PEAK_TF = 157.3     # exact-f32 MFMA (32x32x2) = the f32 vector rate
+
+DUMP_SAMPLE = 1 << 16        # --dump-outputs: elements kept of one output (the 188 parameters of config 3: 15 MB)
+DUMP_LIMIT = 64 << 20        # bytes written in all
+
+
+def dump_outputs(dirname, arrays):
+  """Writes each tensor as DIR/<name>.npy in float32 (float64 stays float64).  A tensor of more than DUMP_SAMPLE
+  elements is replaced by DUMP_SAMPLE of its flattened elements at indices drawn from a fixed seed, the same in
+  every run for the same shape."""
+  import numpy as np
+  import torch
+  os.makedirs(dirname, exist_ok=True)
+  total = 0
+  for name, t in arrays.items():
+    t = t.detach()
+    if t.numel() > DUMP_SAMPLE:
+      idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), DUMP_SAMPLE))
+      t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+    a = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+    total += a.nbytes
+    if total > DUMP_LIMIT:
+      raise RuntimeError(f'--dump-outputs: more than {DUMP_LIMIT >> 20} MB at {name}')
+    np.save(os.path.join(dirname, f'{name}.npy'), a)
 
 
 def traffic_file(cfg):
@@ -238,9 +265,16 @@ def main():
   ap.add_argument('--ids2d', action='store_true',
                   help="the same workload with the 2-D relative ids of the reference's *_2d*.yaml (one core layer, "
                        'relative_vocab_size 49) instead of the 1-D ids of BASELINE config 3 -- a side measurement, not the headline')
+  ap.add_argument('--full', action='store_true',
+                  help='after the timed steps, also the side measurements: HIP-event rooflines of one attention forward and '
+                       'backward call and (one GPU, unless --no-cpu-baseline) the CPU baselines')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='write what the last timed step computed as DIR/<name>.npy (float32; larger outputs as a fixed seeded sample)')
   args = ap.parse_args()
   if args.gpus < 1:
     ap.error('--gpus must be >= 1')
+  if args.steps < 1:
+    ap.error('--steps must be >= 1')
 
   if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
     sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -310,17 +344,18 @@ def main():
     from mmt_amd import benchmarks
     step_fn, step_info = benchmarks.make_allreduce_bench(dev, world, args.allreduce_mb)
   else:
-    g = torch.Generator(device=dev).manual_seed(1234 + rank)
-    pat = mmt_amd.AttentionPattern(local_radius=cfg['radius'], global_start=cfg['g0'],
-                                   n_global=cfg['ng'], id_mode=2 if args.ids2d else 1, max_dist=cfg['m'],
-                                   patches_per_row=cfg.get('P', 0) if args.ids2d else 0, core_layers=cfg.get('core', 0))
-    q, k, v = (torch.randn(B, S, N, D, device=dev, generator=g).to(tdtype) for _ in range(3))
-    emb = (torch.randn(R, N, D, device=dev, generator=g) * 0.02).to(tdtype)
-    bias = (torch.randn(R, N, device=dev, generator=g) * 0.02).to(tdtype)
-    drop = dict(dropout_p=0.1, dropout_seed=12345)       # the train step's attention_probs_dropout_prob
+    if mode == 'attn_fwd' or args.full:     # one attention call's inputs: the attn_fwd step, or the --full rooflines
+      g = torch.Generator(device=dev).manual_seed(1234 + rank)
+      pat = mmt_amd.AttentionPattern(local_radius=cfg['radius'], global_start=cfg['g0'],
+                                     n_global=cfg['ng'], id_mode=2 if args.ids2d else 1, max_dist=cfg['m'],
+                                     patches_per_row=cfg.get('P', 0) if args.ids2d else 0, core_layers=cfg.get('core', 0))
+      q, k, v = (torch.randn(B, S, N, D, device=dev, generator=g).to(tdtype) for _ in range(3))
+      emb = (torch.randn(R, N, D, device=dev, generator=g) * 0.02).to(tdtype)
+      bias = (torch.randn(R, N, device=dev, generator=g) * 0.02).to(tdtype)
+      drop = dict(dropout_p=0.1, dropout_seed=12345)       # the train step's attention_probs_dropout_prob
 
-    def attn_fwd():
-      return mmt_amd.relative_attention_forward(q, k, v, emb, bias, pattern=pat, **drop)
+      def attn_fwd():
+        return mmt_amd.relative_attention_forward(q, k, v, emb, bias, pattern=pat, **drop)
 
     if mode == 'train_step':
       step_fn, step_info = mmt_amd.make_train_step_bench(cfg, dev, rank, world, dtype=tdtype)
@@ -335,9 +370,18 @@ def main():
   barrier()
   t0 = time.perf_counter()
   for _ in range(args.steps):
-    step_fn()
+    result = step_fn()
   barrier()
   dt = time.perf_counter() - t0
+  if args.dump_outputs and rank == 0:   # before close(): a graphed step's result is the recorded graph's output buffer
+    if mode == 'train_step':
+      outputs = dict(result)
+      outputs.update((f'param.{n}', p) for n, p in step_fn.model.named_parameters())
+    elif mode == 'attn_fwd':
+      outputs = dict(zip(('out', 'lse'), result))
+    else:
+      outputs = {f'bucket.{i}': b for i, b in enumerate(step_fn.buckets)}
+    dump_outputs(args.dump_outputs, outputs)
   getattr(step_fn, 'close', lambda: None)()      # back to host-side step scalars for the per-call measurements below
   if world > 1:
     t = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -366,80 +410,75 @@ def main():
 
   value = B * world / (dt / args.steps)
 
-  # ---- rooflines of the attention kernels: HIP events on the launch stream (torch's current stream
-  # IS the stream the C-ABI launches on: ops._stream_ptr) ----
-  def timed(fn, iters=50):
-    for _ in range(5):
-      fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(iters):
-      fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
+  if args.full:
+    # ---- rooflines of the attention kernels: HIP events on the launch stream (torch's current stream
+    # IS the stream the C-ABI launches on: ops._stream_ptr) ----
+    def timed(fn, iters=50):
+      for _ in range(5):
+        fn()
+      e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+      torch.cuda.synchronize()
+      e0.record()
+      for _ in range(iters):
+        fn()
+      e1.record()
+      torch.cuda.synchronize()
+      return e0.elapsed_time(e1) / iters
 
-  flops, byts, bwd_byts = attn_algorithmic(cfg, elt)
-  attn_ms = timed(attn_fwd)
-  out, lse = attn_fwd()
-  dout = torch.randn_like(out)
-  dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-  de = torch.zeros(R, N, D, device=dev); db = torch.zeros(R, N, device=dev)
+    flops, byts, bwd_byts = attn_algorithmic(cfg, elt)
+    attn_ms = timed(attn_fwd)
+    out, lse = attn_fwd()
+    dout = torch.randn_like(out)
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    de = torch.zeros(R, N, D, device=dev); db = torch.zeros(R, N, device=dev)
 
-  def attn_bwd():
-    return mmt_amd.relative_attention_backward(dout, q, k, v, emb, bias, out, lse, pattern=pat,
-                                               grads_out=(dq, dk, dv), rel_grads_accum=(de, db), **drop)
-  bwd_ms = timed(attn_bwd, iters=30)
+    def attn_bwd():
+      return mmt_amd.relative_attention_backward(dout, q, k, v, emb, bias, out, lse, pattern=pat,
+                                                 grads_out=(dq, dk, dv), rel_grads_accum=(de, db), **drop)
+    bwd_ms = timed(attn_bwd, iters=30)
 
-  traffic = traffic_bwd = traffic_commit = None   # HBM bytes per launch from the committed PMC passes
-  us_prof = us_prof_bwd = None                    # rocprofv3 kernel durations of the same workload (profiles/, same commit)
-  try:
-    with open(os.path.join(ROOT, 'profiles', traffic_file(cfg))) as f:
-      tj = json.load(f)
-    traffic, traffic_bwd, traffic_commit = tj['fwd_hbm_bytes_per_launch'], tj['bwd_hbm_bytes_per_launch'], tj.get('commit')
-    us_prof, us_prof_bwd = tj.get('fwd_kernel_us_rocprof'), tj.get('bwd_kernel_us_rocprof')
-  except (OSError, KeyError, ValueError):
-    pass
+    traffic = traffic_bwd = traffic_commit = None   # HBM bytes per launch from the committed PMC passes
+    us_prof = us_prof_bwd = None                    # rocprofv3 kernel durations of the same workload (profiles/, same commit)
+    try:
+      with open(os.path.join(ROOT, 'profiles', traffic_file(cfg))) as f:
+        tj = json.load(f)
+      traffic, traffic_bwd, traffic_commit = tj['fwd_hbm_bytes_per_launch'], tj['bwd_hbm_bytes_per_launch'], tj.get('commit')
+      us_prof, us_prof_bwd = tj.get('fwd_kernel_us_rocprof'), tj.get('bwd_kernel_us_rocprof')
+    except (OSError, KeyError, ValueError):
+      pass
 
-  mfma_peak = F32_MFMA_PEAK_TF if f32 else MFMA_BF16_PEAK_TF
+    mfma_peak = F32_MFMA_PEAK_TF if f32 else MFMA_BF16_PEAK_TF
 
-  def roof(ms, nbytes, nflops, traffic, kernel, us_rocprof=None):
-    """Both roofline terms ("report both fractions for every run and name the binding one"): the HBM
-    fraction of the algorithmic bytes and the MFMA fraction of the algorithmic flops -- against the exact-f32 MFMA
-    rate for fp32 I/O (config 2), the dense bf16 rate otherwise; `bound` is the larger of the two."""
-    gbs = nbytes * B / (ms * 1e-3) / 1e9
-    tfs = nflops * B / (ms * 1e-3) / 1e12
-    hbm_frac, mfma_frac = gbs / HBM_PEAK_GBS, tfs / mfma_peak
-    by_hbm = hbm_frac >= mfma_frac
-    us_sum = sum(us_rocprof.values()) * 1e-6 if us_rocprof else None
-    return {'bound': 'hbm' if by_hbm else ('mfma_f32' if f32 else 'mfma'),
-            'achieved': round(gbs, 1) if by_hbm else round(tfs, 2), 'peak': HBM_PEAK_GBS if by_hbm else mfma_peak,
-            'unit': 'GB/s' if by_hbm else 'TFLOP/s', 'frac': round(max(hbm_frac, mfma_frac), 4),
-            'traffic': traffic, 'traffic_measured_at': traffic_commit,
-            'kernel': kernel, 'launch_us': round(ms * 1e3, 2), 'algorithmic_bytes_per_launch': nbytes * B,
-            'algorithmic_flops_per_launch': int(nflops * B),
-            'hbm_gbs': round(gbs, 1), 'hbm_frac': round(hbm_frac, 4),
-            'mfma_tflops': round(tfs, 2), 'mfma_peak_tflops': mfma_peak, 'mfma_frac': round(mfma_frac, 5),
-            'dropout_p': drop['dropout_p'],
-            # per-kernel average durations under rocprofv3 --kernel-trace --stats (profiles/*_attn_kernel_stats.csv):
-            # frac can be recomputed from them as algorithmic bytes (or flops) per launch / sum(us) / peak
-            'kernel_us_rocprof': us_rocprof,
-            'frac_rocprof': (round((nbytes * B / us_sum / 1e9 / HBM_PEAK_GBS) if by_hbm else (nflops * B / us_sum / 1e12 / mfma_peak), 4)
-                             if us_rocprof else None)}
+    def roof(ms, nbytes, nflops, traffic, kernel, us_rocprof=None):
+      """Both roofline terms ("report both fractions for every run and name the binding one"): the HBM
+      fraction of the algorithmic bytes and the MFMA fraction of the algorithmic flops -- against the exact-f32 MFMA
+      rate for fp32 I/O (config 2), the dense bf16 rate otherwise; `bound` is the larger of the two."""
+      gbs = nbytes * B / (ms * 1e-3) / 1e9
+      tfs = nflops * B / (ms * 1e-3) / 1e12
+      hbm_frac, mfma_frac = gbs / HBM_PEAK_GBS, tfs / mfma_peak
+      by_hbm = hbm_frac >= mfma_frac
+      us_sum = sum(us_rocprof.values()) * 1e-6 if us_rocprof else None
+      return {'bound': 'hbm' if by_hbm else ('mfma_f32' if f32 else 'mfma'),
+              'achieved': round(gbs, 1) if by_hbm else round(tfs, 2), 'peak': HBM_PEAK_GBS if by_hbm else mfma_peak,
+              'unit': 'GB/s' if by_hbm else 'TFLOP/s', 'frac': round(max(hbm_frac, mfma_frac), 4),
+              'traffic': traffic, 'traffic_measured_at': traffic_commit,
+              'kernel': kernel, 'launch_us': round(ms * 1e3, 2), 'algorithmic_bytes_per_launch': nbytes * B,
+              'algorithmic_flops_per_launch': int(nflops * B),
+              'hbm_gbs': round(gbs, 1), 'hbm_frac': round(hbm_frac, 4),
+              'mfma_tflops': round(tfs, 2), 'mfma_peak_tflops': mfma_peak, 'mfma_frac': round(mfma_frac, 5),
+              'dropout_p': drop['dropout_p'],
+              # per-kernel average durations under rocprofv3 --kernel-trace --stats (profiles/*_attn_kernel_stats.csv):
+              # frac can be recomputed from them as algorithmic bytes (or flops) per launch / sum(us) / peak
+              'kernel_us_rocprof': us_rocprof,
+              'frac_rocprof': (round((nbytes * B / us_sum / 1e9 / HBM_PEAK_GBS) if by_hbm else (nflops * B / us_sum / 1e12 / mfma_peak), 4)
+                               if us_rocprof else None)}
 
-  roofline = roof(attn_ms, byts, flops, traffic,
-                  f'one attention-forward call, B={B} (mmt_attn_fwd)', us_prof)
-  roofline_bwd = roof(bwd_ms, bwd_byts, 2.5 * flops, traffic_bwd,
-                      f'one attention-backward call, B={B} (mmt_attn_bwd: dQ pass, dK/dV pass, table-gradient reduce)', us_prof_bwd)
+    roofline = roof(attn_ms, byts, flops, traffic,
+                    f'one attention-forward call, B={B} (mmt_attn_fwd)', us_prof)
+    roofline_bwd = roof(bwd_ms, bwd_byts, 2.5 * flops, traffic_bwd,
+                        f'one attention-backward call, B={B} (mmt_attn_bwd: dQ pass, dK/dV pass, table-gradient reduce)', us_prof_bwd)
 
   if rank == 0:
-    cpu = cpu_fb = cpu_step = None
-    if world == 1 and not args.no_cpu_baseline:
-      if S <= 4096:      # the dense restatement materialises [N,S,S] fp32 tensors: 3.2 GB each at S=8192 -- not run there
-        cpu = cpu_baseline_attention(cfg)
-        cpu_fb = cpu_baseline_attention(cfg, backward=True)
-      cpu_step = cpu_baseline_train_step()
     line = {
         'metric': f'train-step samples/sec + attention TFLOPS, {S}-tok seq',
         'value': round(value, 3),
@@ -452,16 +491,25 @@ def main():
                    'step': mode, 'per_gpu_batch': B, 'global_batch': B * world, 'seq_len': S,
                    'parallelism': f'dp{world}', 'backend': backend if (world > 1 or force_dist) else None,
                    'ranks_seen': ranks_seen, **step_info},
-        'attention_fwd': {'us_per_layer_call': round(attn_ms * 1e3, 2), 'tflops': roofline['mfma_tflops'],
-                          'samples_per_s': round(B / (attn_ms * 1e-3), 1)},
-        'attention_bwd': {'us_per_layer_call': round(bwd_ms * 1e3, 2), 'tflops': roofline_bwd['mfma_tflops'],
-                          'samples_per_s': round(B / (bwd_ms * 1e-3), 1)},
-        'roofline': roofline,
-        'roofline_bwd': roofline_bwd,
-        'cpu_baseline': cpu,
-        'cpu_baseline_attention_fwd_bwd': cpu_fb,
-        'cpu_baseline_train_step': cpu_step,
     }
+    if args.full:
+      cpu = cpu_fb = cpu_step = None
+      if world == 1 and not args.no_cpu_baseline:
+        if S <= 4096:      # the dense restatement materialises [N,S,S] fp32 tensors: 3.2 GB each at S=8192 -- not run there
+          cpu = cpu_baseline_attention(cfg)
+          cpu_fb = cpu_baseline_attention(cfg, backward=True)
+        cpu_step = cpu_baseline_train_step()
+      line.update({
+          'attention_fwd': {'us_per_layer_call': round(attn_ms * 1e3, 2), 'tflops': roofline['mfma_tflops'],
+                            'samples_per_s': round(B / (attn_ms * 1e-3), 1)},
+          'attention_bwd': {'us_per_layer_call': round(bwd_ms * 1e3, 2), 'tflops': roofline_bwd['mfma_tflops'],
+                            'samples_per_s': round(B / (bwd_ms * 1e-3), 1)},
+          'roofline': roofline,
+          'roofline_bwd': roofline_bwd,
+          'cpu_baseline': cpu,
+          'cpu_baseline_attention_fwd_bwd': cpu_fb,
+          'cpu_baseline_train_step': cpu_step,
+      })
     print(json.dumps(line), flush=True)
   if world > 1 or force_dist:
     dist.destroy_process_group()

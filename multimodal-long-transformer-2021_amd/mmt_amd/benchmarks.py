@@ -109,5 +109,6 @@ def make_allreduce_bench(device, world: int, mbytes=None):
     reducer.finish()
 
   step.check = lambda: float(reducer.buckets[0][0]) == float(world)   # SUM of ones over the ranks
+  step.buckets = reducer.buckets
   return step, {'bytes_per_rank': 4 * sum(sizes), 'buckets': len(reducer.buckets),
                 'bucket_mb': strategy.bucket_bytes / (1 << 20)}

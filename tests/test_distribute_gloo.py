@@ -35,7 +35,14 @@ class _DirectScale(torch.autograd.Function):
     return g * wv, None
 
 
+def _gloo_on_cpu():
+  """The spawned workers exchange CPU tensors over gloo.  With a GPU visible the strategy would take nccl and put both
+  ranks on the one device, so the workers do not see it."""
+  torch.cuda.is_available = lambda: False
+
+
 def _worker(rank, world, port, reduce, out):
+  _gloo_on_cpu()
   os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
   from mmt_amd import distribute
   strategy = distribute.get_distribution_strategy('mirrored', num_gpus=0, bucket_mb=3000 / (1 << 20))
@@ -138,6 +145,7 @@ class _DropWordIds(torch.nn.Module):     # train_step reads the batch size off i
 
 
 def _scale_loss_worker(rank, world, port, out):
+  _gloo_on_cpu()
   os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
   from mmt_amd import distribute, tasks
   strategy = distribute.get_distribution_strategy('mirrored', num_gpus=0)
@@ -174,19 +182,25 @@ def test_scale_loss_world2_equals_micro_batched_single_process():
       assert torch.allclose(a, b, atol=1e-6), float((a - b).abs().max())
 
 
-def test_bench_launches_its_own_ranks():
+def test_bench_launches_its_own_ranks(tmp_path):
   """`python bench.py --gpus 2` with no WORLD_SIZE starts two ranks itself (children; the parent never
-  touches a GPU), runs the gradient exchange over gloo here, and relays ONE JSON line."""
+  touches a GPU), runs the gradient exchange over gloo here, and relays ONE JSON line; `--dump-outputs` writes rank 0's
+  reduced gradients."""
   import json
   import subprocess
   import sys
+  import numpy as np
   root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
   env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT')}
   env['MMT_DIST_BACKEND'] = 'gloo'
+  env['MMT_ONE_GPU'] = '1'              # on a machine with a GPU: both ranks on cuda:0 (no effect without one)
   r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--mode', 'allreduce',
-                      '--allreduce-mb', '4', '--steps', '3', '--warmup', '1'],
+                      '--allreduce-mb', '4', '--steps', '3', '--warmup', '1', '--dump-outputs', str(tmp_path)],
                      env=env, capture_output=True, text=True, timeout=240)
   assert r.returncode == 0, r.stderr[-2000:]
+  assert sorted(os.listdir(tmp_path)) == ['bucket.0.npy']
+  g = np.load(tmp_path / 'bucket.0.npy')              # a seeded sample of the 48 MB bucket: 4 MB of SUMs of ones, then padding
+  assert g.dtype == np.float32 and set(np.unique(g).tolist()) == {0.0, 2.0}
   lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
   assert len(lines) == 1, r.stdout
   d = json.loads(lines[0])

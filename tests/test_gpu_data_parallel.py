@@ -164,19 +164,24 @@ def test_replicas_draw_different_dropout_masks():
   assert not torch.equal(a[0], b[0])
 
 
-def test_rccl_path_executes_with_one_rank():
+def test_rccl_path_executes_with_one_rank(tmp_path):
   """`MMT_FORCE_DIST=1 python bench.py`: ONE rank, but through `init_process_group('nccl')`, the multi-rank reducer
   (ready hooks, one async RCCL all-reduce per 48 MB bucket under backward, waits), the main-stream weight gradients
   and the reduced CU budget -- the RCCL code path of BASELINE config 4 (`distribute_utils.py:97-188`,
   `pretraining.py:273`) executed on real hardware, which the one-GPU box cannot do with more ranks.  The all-reduce
-  of ones must see exactly this rank, and the step must produce a finite throughput."""
+  of ones must see exactly this rank, and the step must produce a finite throughput; `--dump-outputs` writes the last
+  step's loss and updated parameters."""
   import json, subprocess, sys
+  import numpy as np
   root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
   env = dict(os.environ, MMT_FORCE_DIST='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
   env.pop('MMT_DIST_BACKEND', None)
-  out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '2', '--no-cpu-baseline'],
-                       env=env, capture_output=True, text=True, timeout=600)
+  out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '2', '--no-cpu-baseline',
+                        '--dump-outputs', str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
   assert out.returncode == 0, out.stderr[-2000:]
+  assert np.isfinite(np.load(tmp_path / 'loss.npy')).all()
+  params = [f for f in os.listdir(tmp_path) if f.startswith('param.')]
+  assert len(params) > 100 and all(np.isfinite(np.load(tmp_path / f)).all() for f in params)
   line = json.loads(out.stdout.strip().splitlines()[-1])
   assert line['config']['backend'] == 'nccl' and line['config']['ranks_seen'] == 1
   assert 'RCCL' in line['config']['grad_allreduce']

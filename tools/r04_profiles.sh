@@ -7,7 +7,7 @@ C=${1:-3}; G=${2:-8}; TAG=${3:-r04_cfg${C}_g${G}}
 export MMT_BENCH_CONFIG=$C MMT_BENCH_GLOBALS=$G
 D=gpurun_out/$TAG
 rm -rf $D; mkdir -p $D
-python3 bench.py --config $C --globals $G --steps 20 --warmup 5 > $D/bench.json 2> $D/bench.err || { tail -5 $D/bench.err; exit 1; }
+python3 bench.py --full --config $C --globals $G --steps 20 --warmup 5 > $D/bench.json 2> $D/bench.err || { tail -5 $D/bench.err; exit 1; }
 rocprofv3 --kernel-trace --stats --output-format csv -d $D/attn_ks -o a -- python3 tools/attn_pmc_workload.py > /dev/null 2>&1 || exit 2
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $D/pmc_f -o f -- python3 tools/attn_pmc_workload.py > /dev/null 2>&1 || exit 3
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $D/pmc_w -o w -- python3 tools/attn_pmc_workload.py > /dev/null 2>&1 || exit 4

@@ -70,15 +70,20 @@ enum {
 #define MMT_TUNE_BWD_NO_PEEL_DKV 0x40u   /* backward: likewise for the global query rows of the recomputing dK/dV pass  */
 #define MMT_TUNE_BWD_DQ_PLANE_MAJOR 0x80u /* backward: plane-major block placement of the dQ pass                       */
 
-/* Attention pattern + id generator.  With local_radius >= S and n_global == 0 the
+/* Attention pattern + id generator.  With local_radius >= S, n_global == 0 and no image grid the
  * pattern is exactly the reference's segmented mask (data_utils.py:321-322):
  *   mask(q,k) = (q < valid_len[b]) == (k < valid_len[b])
  * otherwise (build-defined):
- *   mask(q,k) = segmented(q,k) && (|q-k| <= local_radius || global(q) || global(k)),
+ *   mask(q,k) = segmented(q,k) && (|q-k| <= local_radius || global(q) || global(k) || grid(q,k)),
  *   global(x) = global_start <= x < global_start + n_global, or -- with global_index --
  *   x is one of the n_global listed positions.  The structured kernels take the contiguous
  *   form only; a listed set is served by materialising the mask (mmt_side_inputs with
- *   materialize_pattern) and calling the dense operator with it.                       */
+ *   materialize_pattern) and calling the dense operator with it.
+ *   grid(q,k) = a > 0 && img(q) && img(k) && |row(q)-row(k)| <= a && |col(q)-col(k)| <= a  (ABI 4, image_grid):
+ *   img(x) = g <= x < g + P*P, row(x) = (x-g) / P, col(x) = (x-g) % P, P = patches_per_row: the 2-D
+ *   neighbourhood of the image patches (raster order, no wrap across rows).  Symmetric in (q,k).  */
+/* image_grid word of mmt_mask_desc: grid radius a (1..8) and first image position g */
+#define MMT_IMAGE_GRID(a, g) ((int32_t)(((uint32_t)(a) & 0xFFu) | (((uint32_t)(g) & 0x7FFFFFu) << 8)))
 typedef struct mmt_mask_desc {
   const int32_t* valid_len; /* [B] device ints (num_image_wordpieces + num_text_wordpieces),
                                NULL = every position valid                            */
@@ -89,6 +94,9 @@ typedef struct mmt_mask_desc {
   int32_t max_dist;         /* relative_pos_max_distance m (encoders.py:60)          */
   int32_t patches_per_row;  /* P  = image_size // patch_size        (MMT_IDS_2D)     */
   int32_t core_layers;      /* r  = relative_att_num_core_layers    (MMT_IDS_2D)     */
+  int32_t image_grid;       /* ABI 4, in what was padding: 0 = no grid term; else grid radius a (bits 0-7) |
+                               first image position g (bits 8-30); P = patches_per_row.  Callers must zero it.
+                               MMT_IMAGE_GRID(a, g) builds it; a is built up to 8.      */
   const int32_t* global_index; /* NULL: the contiguous range above; else n_global ascending,
                                distinct positions in [0, S) on the device (global_start
                                is ignored).  ABI 2.                                     */

@@ -82,6 +82,28 @@ int main(void) {
     free(ws);
   }
 
+  /* ---- image grid (ABI 4): the general kernels, forward and backward, whatever the tuning switches ---- */
+  {
+    const uint32_t tunings[] = {0u, MMT_TUNE_FWD_WALK, MMT_TUNE_FWD_PWIN, MMT_TUNE_FWD_FORCE_WIN, MMT_TUNE_BWD_HO_PER_WAVE};
+    for (unsigned t = 0; t < sizeof(tunings) / sizeof(tunings[0]); ++t) {
+      d = base_desc(4, 4096, 12, 32, MMT_BF16);
+      d.mask.patches_per_row = 63; d.mask.image_grid = MMT_IMAGE_GRID(1, 2);
+      d.tuning = tunings[t];
+      uint32_t sync[48] = {0};
+      d.sync = sync; d.sync_words = 48;
+      const size_t need = mmt_workspace_bytes(&d);
+      unsigned char* ws = (unsigned char*)malloc(need);
+      CHECK(ws != NULL);
+      g_ws_lo = ws; g_ws_hi = ws + need;
+      CHECK(mmt_attn_fwd(&d, dummy, dummy, dummy, dummy, NULL, NULL, NULL, dummy, (float*)dummy, ws, need, NULL) == MMT_OK);
+      CHECK(g_last_kind == 1);      /* the general kernel: no lean, window, walk or sliding-window kernel */
+      CHECK(mmt_attn_bwd(&d, dummy, dummy, dummy, dummy, NULL, NULL, NULL, dummy, dummy, (const float*)dummy, dummy, dummy, dummy,
+                         (float*)dummy, NULL, ws, need, NULL) == MMT_OK);
+      CHECK(g_last_kind == 5 && g_last_handover == 0);
+      free(ws);
+    }
+  }
+
   /* ---- side inputs: the reference generator's argument errors (feature_utils.py:60-65) ---- */
   mmt_mask_desc m;
   memset(&m, 0, sizeof(m));

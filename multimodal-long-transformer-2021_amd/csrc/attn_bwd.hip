@@ -54,7 +54,7 @@ __device__ __forceinline__ TileWalk band_walk(const PatternDev& pat, int x0, int
 }
 
 // Mask bit and relative-table column of one (q,k) pair (col < 0: no relative term).
-template <int MODE, bool GEN, typename P>
+template <int MODE, bool GEN, bool GRID, typename P>
 __device__ __forceinline__ void pair_mask_col(const P& p, int b, int valid_len, int q, int k,
                                               bool& keep, int& col) {
   int id = -1;
@@ -65,7 +65,7 @@ __device__ __forceinline__ void pair_mask_col(const P& p, int b, int valid_len, 
     if (p.rel_ids) id = p.rel_ids[off];
     if ((unsigned)id < (unsigned)p.R) col = id;
   } else if (GEN) {
-    keep = pattern_mask(p.pat, valid_len, q, k);
+    keep = pattern_mask<GRID>(p.pat, p.grid, valid_len, q, k);
     if (p.pat.id_mode) id = rel_id(p.pat, q, k);
     if ((unsigned)id < (unsigned)p.R) col = id;
   } else {
@@ -73,7 +73,7 @@ __device__ __forceinline__ void pair_mask_col(const P& p, int b, int valid_len, 
     const unsigned W = (unsigned)p.pat.radius;
     const bool near = (unsigned)(d + (int)W) <= 2u * W;
     const bool seg = (k < valid_len) == (q < valid_len);
-    keep = (int)seg & ((int)near | (int)is_global(p.pat, k) | (int)is_global(p.pat, q));
+    keep = (int)seg & ((int)near | (int)is_global(p.pat, k) | (int)is_global(p.pat, q) | (int)(GRID && in_grid(p.pat, p.grid, q, k)));
     if (p.pat.id_mode == 1) col = min(max(d, -p.pat.m), p.pat.m) + p.pat.m;
   }
 }
@@ -118,7 +118,8 @@ __device__ __forceinline__ void build_table(const P& p, int n, const Frag<T>& xf
 // =========================================================================================
 // K4a: dQ, delta, dRel.  Lane (r,h) owns query row q0 + r; registers walk keys.
 // =========================================================================================
-template <typename T, int MODE, int Rp, bool GEN>
+// GRID: as attn_fwd_kernel (attn_fwd.hip) -- GridWalk's union and the grid term in the mask, for image-grid patterns only.
+template <typename T, int MODE, int Rp, bool GEN, bool GRID>
 __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dq_kernel(const BwdParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x & 63;
@@ -167,6 +168,13 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dq_ker
     if (split_item) { w.b0 = chunk * p.chunk_tiles; w.lenB = min(n_tiles, w.b0 + p.chunk_tiles) - w.b0; }
     else w = band_walk(p.pat, q0, p.S);
   }
+  GridWalk gw;                    // GRID: cursor over the union (t_cur, t_nxt); w.count() unused
+  int t_cur = 0, t_nxt = 0;
+  if constexpr (GRID) {
+    if (split_item) gw.init_chunk(w.b0, w.b0 + w.lenB - 1);
+    else gw.init_band(p.pat, p.grid, q0, p.S);
+    t_cur = gw.next(0);
+  }
 
   Frag<T> qf, dof;
   qf.load_row(Q + qc * qs1, h);
@@ -208,21 +216,22 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dq_ker
   Frag<T> kf, vf;
   VTile<T> kt;
   {
-    const int k0 = w.at(0) * 32;
+    const int k0 = (GRID ? t_cur : w.at(0)) * 32;
     kf.load_row(K + (unsigned)min(k0 + r, p.S - 1) * ks1, h);
     vf.load_row(V + (unsigned)min(k0 + r, p.S - 1) * vs1, h);
     kt.load(K, ks1, k0, p.S, lane, 0);
   }
-  for (int it = 0; it < n_it; ++it) {
-    const int k0 = w.at(it) * 32;
+  for (int it = 0; GRID ? t_cur != GridWalk::kEnd : it < n_it; ++it, t_cur = t_nxt) {
+    const int k0 = (GRID ? t_cur : w.at(it)) * 32;
     kt.to_lds(xlds, lane);
     VTile<T> kcur;
     if constexpr (sizeof(T) == 4) kcur = kt;
     f32x16 c = {0}, dp = {0};
     c = mma_rows(kf, qf, c);     // S^T  [key x q]
     dp = mma_rows(vf, dof, dp);  // dP^T [key x q]
-    if (it + 1 < n_it) {         // next tile's operands arrive under this tile's math
-      const int k1 = w.at(it + 1) * 32;
+    if constexpr (GRID) t_nxt = gw.next(t_cur + 1);
+    if (GRID ? t_nxt != GridWalk::kEnd : it + 1 < n_it) {         // next tile's operands arrive under this tile's math
+      const int k1 = (GRID ? t_nxt : w.at(it + 1)) * 32;
       kf.load_row(K + (unsigned)min(k1 + r, p.S - 1) * ks1, h);
       vf.load_row(V + (unsigned)min(k1 + r, p.S - 1) * vs1, h);
       kt.load(K, ks1, k1, p.S, lane, 0);
@@ -235,7 +244,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dq_ker
     for (int i = 0; i < 16; ++i) {
       const int kk = k0 + kap(i, h);
       bool keep;
-      pair_mask_col<MODE, GEN>(p, b, valid_len, q, kk, keep, cols[i]);
+      pair_mask_col<MODE, GEN, GRID>(p, b, valid_len, q, kk, keep, cols[i]);
       keepm |= (unsigned)keep << i;
       existm |= (unsigned)(kk < p.S && q_ok) << i;
       rel[i] = cols[i] >= 0 ? trow[cols[i]] : 0.f;
@@ -381,8 +390,10 @@ __global__ __launch_bounds__(64) void attn_bwd_dq_combine_kernel(const BwdParams
 // =========================================================================================
 // K4b: dK, dV.  Lane (r,h) owns key k0 + r; registers walk query rows.
 // =========================================================================================
-template <typename T, int MODE, int Rp, bool GEN>
-__global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dkv_kernel(const BwdParams p) {
+// GRID instantiations are built for one workgroup per CU: at two the bf16 form spills to scratch (as the GRID = false
+// ones do, whose figures are kept as they were).
+template <typename T, int MODE, int Rp, bool GEN, bool GRID>
+__global__ __launch_bounds__(256, ((sizeof(T) == 2 && !GRID) ? 2 : 1)) void attn_bwd_dkv_kernel(const BwdParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -431,6 +442,13 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dkv_ke
     if (split_item) { w.b0 = chunk * p.chunk_tiles; w.lenB = min(n_tiles, w.b0 + p.chunk_tiles) - w.b0; }
     else w = band_walk(p.pat, k0, p.S);
   }
+  GridWalk gw;                    // GRID: the same walk over query tiles (the pattern is symmetric)
+  int t_cur = 0, t_nxt = 0;
+  if constexpr (GRID) {
+    if (split_item) gw.init_chunk(w.b0, w.b0 + w.lenB - 1);
+    else gw.init_band(p.pat, p.grid, k0, p.S);
+    t_cur = gw.next(0);
+  }
 
   Frag<T> kf, vf;
   kf.load_row(K + kc * ks1, h);
@@ -442,18 +460,19 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dkv_ke
   const int n_it = w.count();
   VTile<T> qt, dot;
   if constexpr (sizeof(T) == 2) {            // first tile's rows (prefetch registers)
-    qt.load(Q, qs1, w.at(0) * 32, p.S, lane, 0);
-    dot.load(DO, os1, w.at(0) * 32, p.S, lane, 0);
+    qt.load(Q, qs1, (GRID ? t_cur : w.at(0)) * 32, p.S, lane, 0);
+    dot.load(DO, os1, (GRID ? t_cur : w.at(0)) * 32, p.S, lane, 0);
   }
-  for (int it = 0; it < n_it; ++it) {
-    const int q0 = w.at(it) * 32;
+  for (int it = 0; GRID ? t_cur != GridWalk::kEnd : it < n_it; ++it, t_cur = t_nxt) {
+    const int q0 = (GRID ? t_cur : w.at(it)) * 32;
+    if constexpr (GRID) t_nxt = gw.next(t_cur + 1);
     Frag<T> qf, dof;
     if constexpr (sizeof(T) == 2) {
       qt.to_lds(qlds, lane);
       dot.to_lds(dolds, lane);
-      if (it + 1 < n_it) {                   // next tile's rows arrive under this tile's math
-        qt.load(Q, qs1, w.at(it + 1) * 32, p.S, lane, 0);
-        dot.load(DO, os1, w.at(it + 1) * 32, p.S, lane, 0);
+      if (GRID ? t_nxt != GridWalk::kEnd : it + 1 < n_it) {                   // next tile's rows arrive under this tile's math
+        qt.load(Q, qs1, (GRID ? t_nxt : w.at(it + 1)) * 32, p.S, lane, 0);
+        dot.load(DO, os1, (GRID ? t_nxt : w.at(it + 1)) * 32, p.S, lane, 0);
       }
     } else {
       qf.load_row(Q + (unsigned)min(q0 + r, p.S - 1) * qs1, h);
@@ -478,7 +497,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dkv_ke
     for (int i = 0; i < 16; ++i) {
       const int qq = q0 + kap(i, h);
       bool keep;
-      pair_mask_col<MODE, GEN>(p, b, valid_len, qq, k, keep, cols[i]);
+      pair_mask_col<MODE, GEN, GRID>(p, b, valid_len, qq, k, keep, cols[i]);
       keepm |= (unsigned)keep << i;
       existm |= (unsigned)(qq < p.S && k_ok) << i;
       rel[i] = cols[i] >= 0 ? tab[kap(i, h) * kTStride(Rp) + cols[i]] : 0.f;
@@ -615,7 +634,7 @@ static void allow_lds(K kernel, int bytes) {
                                                    hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
-template <typename T, int MODE, int Rp, bool GEN>
+template <typename T, int MODE, int Rp, bool GEN, bool GRID>
 static hipError_t launch_bwd_one(const BwdParams& p_in, hipStream_t st) {
   BwdParams p = p_in;
   p.red_per_plane = ((p.S + 127) >> 7) * 4;               // one dE partial per wave (32 rows)
@@ -623,16 +642,16 @@ static hipError_t launch_bwd_one(const BwdParams& p_in, hipStream_t st) {
   const int per_bn = (p.n_chunks * p.n_gblk + 3) / 4;
   dim3 grid(p.n_band_blocks + (MODE == kBand ? per_bn * p.B * p.N : 0));
   const int lds_a = 4 * BwdLds<T, Rp>::kDq, lds_b = 4 * BwdLds<T, Rp>::kDkv;
-  allow_lds(attn_bwd_dq_kernel<T, MODE, Rp, GEN>, lds_a);
-  allow_lds(attn_bwd_dkv_kernel<T, MODE, Rp, GEN>, lds_b);
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<T, MODE, Rp, GEN>), grid, dim3(256), lds_a, st, p);
+  allow_lds(attn_bwd_dq_kernel<T, MODE, Rp, GEN, GRID>, lds_a);
+  allow_lds(attn_bwd_dkv_kernel<T, MODE, Rp, GEN, GRID>, lds_b);
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<T, MODE, Rp, GEN, GRID>), grid, dim3(256), lds_a, st, p);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (MODE == kBand && p.n_gblk > 0) {
     hipLaunchKernelGGL(attn_bwd_dq_combine_kernel<T>, dim3(p.pat.ng, p.B * p.N), dim3(64), 0, st, p);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
-  hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, MODE, Rp, GEN>), grid, dim3(256), lds_b, st, p);
+  hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, MODE, Rp, GEN, GRID>), grid, dim3(256), lds_b, st, p);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if (MODE == kBand && p.n_gblk > 0) {
     hipLaunchKernelGGL(attn_bwd_dkv_combine_kernel<T>, dim3(p.pat.ng, p.B * p.N), dim3(64), 0, st, p);
@@ -645,18 +664,20 @@ static hipError_t launch_bwd_one(const BwdParams& p_in, hipStream_t st) {
   return e;
 }
 
-template <typename T, int MODE, bool GEN>
+template <typename T, int MODE, bool GEN, bool GRID>
 static hipError_t launch_bwd_rp(const BwdParams& p, hipStream_t st) {
-  if (p.Rp == 32) return launch_bwd_one<T, MODE, 32, GEN>(p, st);
-  if (p.Rp == 64) return launch_bwd_one<T, MODE, 64, GEN>(p, st);
-  return launch_bwd_one<T, MODE, 128, GEN>(p, st);
+  if (p.Rp == 32) return launch_bwd_one<T, MODE, 32, GEN, GRID>(p, st);
+  if (p.Rp == 64) return launch_bwd_one<T, MODE, 64, GEN, GRID>(p, st);
+  return launch_bwd_one<T, MODE, 128, GEN, GRID>(p, st);
 }
 
 template <typename T>
 static hipError_t launch_bwd_t(const BwdParams& p, int mode, hipStream_t st) {
-  if (mode == kDense) return launch_bwd_rp<T, kDense, true>(p, st);
+  if (mode == kDense) return launch_bwd_rp<T, kDense, true, false>(p, st);
   const bool gen = !(p.pat.id_mode == 0 || p.perm_1d);
-  return gen ? launch_bwd_rp<T, kBand, true>(p, st) : launch_bwd_rp<T, kBand, false>(p, st);
+  if (p.grid.ga > 0)                 // image grid: its own instantiations
+    return gen ? launch_bwd_rp<T, kBand, true, true>(p, st) : launch_bwd_rp<T, kBand, false, true>(p, st);
+  return gen ? launch_bwd_rp<T, kBand, true, false>(p, st) : launch_bwd_rp<T, kBand, false, false>(p, st);
 }
 
 hipError_t launch_bwd_dq_combine(const BwdParams& p, bool bf16, hipStream_t st) {
@@ -680,7 +701,7 @@ hipError_t launch_drel_reduce(const BwdParams& p, bool bf16, hipStream_t st) {
 }
 
 hipError_t launch_attn_bwd(const BwdParams& p, int mode, bool bf16, hipStream_t st) {
-  if (mode == kBand && bf16 && (p.pat.id_mode == 0 || (p.perm_1d && p.Rp <= 64) || p.lean2d)) return launch_attn_bwd_band_bf16(p, st);
+  if (mode == kBand && bf16 && p.grid.ga == 0 && (p.pat.id_mode == 0 || (p.perm_1d && p.Rp <= 64) || p.lean2d)) return launch_attn_bwd_band_bf16(p, st);
   return bf16 ? launch_bwd_t<__bf16>(p, mode, st) : launch_bwd_t<float>(p, mode, st);
 }
 

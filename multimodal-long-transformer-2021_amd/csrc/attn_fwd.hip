@@ -23,7 +23,9 @@ namespace mmt {
 
 // GEN = true: ids/mask through the generic per-element generators (2-D ids, or 1-D ids whose
 // vocabulary is smaller than 2m+1); GEN = false: no ids or 1-D ids with the permuted table.
-template <typename T, int MODE, int Rp, bool GEN>
+// GRID = true (kBand only): the pattern has the image-grid term -- the tile walk is GridWalk's union and the
+// per-element mask ORs in_grid; GRID = false instantiations (every pattern without a grid) are the kernels as before.
+template <typename T, int MODE, int Rp, bool GEN, bool GRID>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x & 63;
@@ -86,6 +88,14 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
   auto tile_at = [&](int it) {
     return it < lenA ? a0 + it : (it < lenA + lenB ? b0 + (it - lenA) : c0 + (it - lenA - lenB));
   };
+  // GRID: the walk is a cursor over GridWalk's union (t_cur, and t_nxt found under the tile's math); n_it unused
+  GridWalk gw;
+  int t_cur = 0, t_nxt = 0;
+  if constexpr (GRID) {
+    if (rows_item) gw.init_chunk(b0, b0 + lenB - 1);
+    else gw.init_band(p.pat, p.grid, q0, p.S);
+    t_cur = gw.next(0);
+  }
 
   Frag<T> qf;
   qf.load_row(Q + (unsigned)min(q, p.S - 1) * qs1, h);
@@ -94,7 +104,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
   Frag<T> kf;
   VTile<T> vt;
   {
-    const int k0 = tile_at(0) * 32;
+    const int k0 = (GRID ? t_cur : tile_at(0)) * 32;
     kf.load_row(K + (unsigned)min(k0 + r, p.S - 1) * ks1, h);
     vt.load(V, vs1, k0, p.S, lane, 0);
   }
@@ -130,8 +140,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
   const bool qblk_valid = q0 + 31 < valid_len, qblk_pad = q0 >= valid_len;
   const bool qblk_plain = q0 + 31 < p.S && !(p.pat.ng > 0 && q0 + 31 >= p.pat.g0 && q0 < p.pat.g0 + p.pat.ng);
 
-  for (int it = 0; it < n_it; ++it) {
-    const int k0 = tile_at(it) * 32;
+  for (int it = 0; GRID ? t_cur != GridWalk::kEnd : it < n_it; ++it, t_cur = t_nxt) {
+    const int k0 = (GRID ? t_cur : tile_at(it)) * 32;
     vt.to_lds(vlds, lane);
 
     f32x16 c = {0};
@@ -139,8 +149,9 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
 
     VTile<T> vcur;
     if constexpr (sizeof(T) == 4) vcur = vt;
-    if (it + 1 < n_it) {   // prefetch the next tile (registers) under this tile's math
-      const int k1 = tile_at(it + 1) * 32;
+    if constexpr (GRID) t_nxt = gw.next(t_cur + 1);
+    if (GRID ? t_nxt != GridWalk::kEnd : it + 1 < n_it) {   // prefetch the next tile (registers) under this tile's math
+      const int k1 = (GRID ? t_nxt : tile_at(it + 1)) * 32;
       kf.load_row(K + (unsigned)min(k1 + r, p.S - 1) * ks1, h);
       vt.load(V, vs1, k1, p.S, lane, 0);
     }
@@ -182,7 +193,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
         const bool near = (unsigned)(d + (int)W) <= 2u * W;
         const bool gk = (unsigned)(kk - p.pat.g0) < (unsigned)p.pat.ng;
         const bool seg = (kk < valid_len) == qv;
-        const bool keep = (int)seg & ((int)near | (int)gk | (int)gq);
+        const bool keep = (int)seg & ((int)near | (int)gk | (int)gq | (int)(GRID && in_grid(p.pat, p.grid, q, kk)));
         float rel = 0.f;
         if (id_mode == 1) rel = trow[min(max(d, -mdist), mdist) + mdist];
         float s = fmaf(c[i], p.sscale, rel);
@@ -202,7 +213,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
           keep = p.att_mask ? p.att_mask[off] != 0 : true;
           if (p.rel_ids) id = p.rel_ids[off];
         } else {
-          keep = pattern_mask(p.pat, valid_len, q, kk);
+          keep = pattern_mask<GRID>(p.pat, p.grid, valid_len, q, kk);
           if (id_mode) id = rel_id(p.pat, q, kk);
         }
         float rel = 0.f;
@@ -336,27 +347,29 @@ __global__ __launch_bounds__(64) void attn_rows_combine_kernel(const FwdParams p
 }
 
 // ------------------------------------ launchers -----------------------------------------
-template <typename T, int MODE, int Rp, bool GEN>
+template <typename T, int MODE, int Rp, bool GEN, bool GRID>
 static hipError_t launch_one(const FwdParams& p, dim3 grid, hipStream_t st) {
   const int lds = 4 * WaveLds<T, Rp>::kBytes;
   if (lds > 64 * 1024)               // (the 128-wide table: relative vocabularies of 65..128 ids)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<T, MODE, Rp, GEN>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  hipLaunchKernelGGL((attn_fwd_kernel<T, MODE, Rp, GEN>), grid, dim3(256), lds, st, p);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<T, MODE, Rp, GEN, GRID>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  hipLaunchKernelGGL((attn_fwd_kernel<T, MODE, Rp, GEN, GRID>), grid, dim3(256), lds, st, p);
   return hipGetLastError();
 }
 
-template <typename T, int MODE, bool GEN>
+template <typename T, int MODE, bool GEN, bool GRID>
 static hipError_t launch_rp(const FwdParams& p, dim3 grid, hipStream_t st) {
-  if (p.R <= 32) return launch_one<T, MODE, 32, GEN>(p, grid, st);
-  if (p.R <= 64) return launch_one<T, MODE, 64, GEN>(p, grid, st);
-  return launch_one<T, MODE, 128, GEN>(p, grid, st);
+  if (p.R <= 32) return launch_one<T, MODE, 32, GEN, GRID>(p, grid, st);
+  if (p.R <= 64) return launch_one<T, MODE, 64, GEN, GRID>(p, grid, st);
+  return launch_one<T, MODE, 128, GEN, GRID>(p, grid, st);
 }
 
 template <typename T>
 static hipError_t launch_t(const FwdParams& p, int mode, dim3 grid, hipStream_t st) {
-  if (mode == kDense) return launch_rp<T, kDense, true>(p, grid, st);
+  if (mode == kDense) return launch_rp<T, kDense, true, false>(p, grid, st);
   const bool gen = !(p.pat.id_mode == 0 || p.perm_1d);
-  return gen ? launch_rp<T, kBand, true>(p, grid, st) : launch_rp<T, kBand, false>(p, grid, st);
+  if (p.grid.ga > 0)                 // image grid: its own instantiations (the others carry no trace of it)
+    return gen ? launch_rp<T, kBand, true, true>(p, grid, st) : launch_rp<T, kBand, false, true>(p, grid, st);
+  return gen ? launch_rp<T, kBand, true, false>(p, grid, st) : launch_rp<T, kBand, false, false>(p, grid, st);
 }
 
 hipError_t launch_attn_fwd(const FwdParams& p, int mode, bool bf16, hipStream_t st) {

@@ -46,6 +46,7 @@ struct FwdParams {
   unsigned* sync;
   long long* dbg;     // -DMMT_STAMP diagnostic builds only: in-kernel s_memtime stamps (never set in the product)
   int dbg_mode, dbg_sleep;   // -DMMT_STAMP builds only: ablations (1 = no tile loop, 2 = no DMA), start delay of the second resident round
+  GridDev grid;       // image-grid term (general kernels only; last, so that no other field moves)
 };
 
 hipError_t launch_attn_fwd(const FwdParams& p, int mode, bool bf16, hipStream_t st);
@@ -107,6 +108,7 @@ struct BwdParams {
   int dq_plane_major;   // dQ pass: plane-major block placement (attn_lean.h) instead of long-items-first + XCD remap
   long long* dbg;    // -DMMT_STAMP diagnostic builds only (see FwdParams)
   int dbg_mode;
+  GridDev grid;      // image-grid term (general kernels only; last, so that no other field moves)
 };
 
 hipError_t launch_attn_bwd(const BwdParams& p, int mode, bool bf16, hipStream_t st);
@@ -122,6 +124,7 @@ struct SideParams {
   const int32_t *img_wp, *txt_wp;
   int materialize_pattern;
   int32_t *att_mask, *rel_ids, *segment_ids;
+  GridDev grid;
 };
 hipError_t launch_side_inputs(const SideParams& p, hipStream_t st);
 // mmt_write_step_scalars: one thread writes the step's epoch and {lr, bias corrections} (side_inputs.hip)

@@ -6,6 +6,48 @@ namespace mmt {
 
 template <typename T> struct Frag;
 
+// Tile walk of a 32-row block at x0 under a pattern with the image-grid term (grid.ga > 0): the ascending union of
+//   the band's tiles, the global tokens' tiles, and, for each image-row offset dr in [-a, a], the tiles of
+//   [ia + dr P - a, ib + dr P + a] n [gs, gs + P^2), [ia, ib] = the block's rows inside the image,
+// i.e. every tile that can hold an unmasked pair, each once (a tile counted twice would enter the online softmax and
+// the dK/dV sums twice).  The pattern is symmetric in (q, k): the dK/dV pass walks the query tiles of a key block with
+// the same walk.  Everything here is wave-uniform scalars; next(t) scans the <= 2a + 3 sources for the smallest tile
+// >= t of the union (no runtime-indexed per-lane array: those go to scratch).  The split items of the global rows /
+// keys walk their chunk [band_lo, band_hi] alone (empty global and grid sources).
+struct GridWalk {
+  static constexpr int kEnd = 0x7fffffff;
+  int band_lo, band_hi, glob_lo, glob_hi;   // tile ranges (lo > hi: empty)
+  int ia, ib, img_lo, img_hi;               // positions
+  int a, P;
+  __device__ __forceinline__ void init_band(const PatternDev& pat, const GridDev& grid, int x0, int S) {
+    band_lo = max(x0 - pat.radius, 0) >> 5;
+    band_hi = min(x0 + 31 + pat.radius, S - 1) >> 5;
+    glob_lo = pat.ng > 0 ? pat.g0 >> 5 : 1;
+    glob_hi = pat.ng > 0 ? (pat.g0 + pat.ng - 1) >> 5 : 0;
+    img_lo = grid.gs; img_hi = grid.gs + grid.gI - 1;
+    ia = max(x0, img_lo); ib = min(x0 + 31, img_hi);
+    a = grid.ga; P = pat.P;
+  }
+  __device__ __forceinline__ void init_chunk(int t0, int t1) {
+    band_lo = t0; band_hi = t1; glob_lo = 1; glob_hi = 0; ia = 1; ib = 0; img_lo = img_hi = 0; a = 0; P = 1;
+  }
+  __device__ __forceinline__ int next(int t) const {
+    int best = kEnd;
+    if (max(band_lo, t) <= band_hi) best = max(band_lo, t);
+    if (max(glob_lo, t) <= glob_hi) best = min(best, max(glob_lo, t));
+    if (ia <= ib) {
+      for (int dr = -a; dr <= a; ++dr) {       // intervals ascend with dr
+        const int lo = max(ia + dr * P - a, img_lo), hi = min(ib + dr * P + a, img_hi);
+        if (lo > hi) continue;
+        const int c = max(lo >> 5, t);
+        if (c >= best) break;
+        if (c <= (hi >> 5)) best = c;
+      }
+    }
+    return best;
+  }
+};
+
 // ------------------------------- bf16: 32x32x16 MFMA ---------------------------------
 // MFMA k-index (8h + j) of step s is mapped to head-dim d = 32h + 8s + j, so each lane
 // loads 64 contiguous bytes of its row (4 x 16 B).

@@ -48,11 +48,28 @@ struct Plan {
 // P / dS hand-over between the two backward passes (lean bf16 kernels, 1-D or no relative ids): shapes it is built for.
 // The global tokens, if any, must be the peeled kind (<= 8, contiguous); the band at most 8 tiles wide.
 int handover_slots(const mmt_attn_desc* d, bool dense) {
-  if (dense || d->dtype != MMT_BF16) return 0;
+  if (dense || d->dtype != MMT_BF16 || (d->mask.image_grid & 0xFF)) return 0;     // (an image grid: the general kernels)
   if (d->mask.global_index || d->mask.n_global > 8) return 0;
   const int W = d->mask.local_radius > d->S ? d->S : d->mask.local_radius;
   const int slots = 2 * ((W + 31) / 32) + 1;
   return slots <= 8 ? slots : 0;
+}
+
+// image_grid word of mmt_mask_desc (MMT_IMAGE_GRID): radius a in bits 0-7, first image position g in bits 8-30
+int grid_radius(const mmt_mask_desc& m) { return m.image_grid & 0xFF; }
+int grid_start(const mmt_mask_desc& m) { return (m.image_grid >> 8) & 0x7FFFFF; }
+
+// argument errors of the image-grid term (shared by check_desc and mmt_side_inputs); 0 = fine or no grid
+int check_grid(const mmt_mask_desc& m, int S) {
+  if (m.image_grid == 0) return MMT_OK;
+  if (m.image_grid < 0) return fail(MMT_E_INVALID, "image_grid: bit 31 must be zero");
+  const int a = grid_radius(m);
+  if (a == 0) return MMT_OK;
+  if (a > 8) return fail(MMT_E_UNSUPPORTED, "grid radius %d: built up to 8", a);
+  if (m.patches_per_row <= 0) return fail(MMT_E_INVALID, "an image grid needs patches_per_row > 0");
+  if ((int64_t)grid_start(m) + (int64_t)m.patches_per_row * m.patches_per_row > S)
+    return fail(MMT_E_INVALID, "image grid outside the sequence (g + P*P > S)");
+  return MMT_OK;
 }
 
 int check_desc(const mmt_attn_desc* d) {
@@ -78,7 +95,7 @@ int check_desc(const mmt_attn_desc* d) {
     if (m.patches_per_row <= 0 || m.core_layers <= 0) return fail(MMT_E_INVALID, "2-D ids need patches_per_row > 0 and core_layers > 0");
     if ((int64_t)m.patches_per_row * m.patches_per_row > d->S) return fail(MMT_E_INVALID, "image part longer than the sequence");
   }
-  return MMT_OK;
+  return check_grid(m, d->S);
 }
 
 mmt::PatternDev make_pattern(const mmt_mask_desc& m, int S) {
@@ -95,6 +112,14 @@ mmt::PatternDev make_pattern(const mmt_mask_desc& m, int S) {
   p.image_part = m.patches_per_row * m.patches_per_row + 8 + 2 * m.max_dist + 1;
   p.text_part = p.image_part + 1;
   return p;
+}
+
+mmt::GridDev make_grid(const mmt_mask_desc& m) {
+  mmt::GridDev g;
+  g.ga = grid_radius(m);                                          // validated: a <= 8, P > 0, g + P*P <= S
+  g.gs = g.ga ? grid_start(m) : 0;
+  g.gI = g.ga ? m.patches_per_row * m.patches_per_row : 0;
+  return g;
 }
 
 Plan make_plan(const mmt_attn_desc* d, bool dense) {
@@ -133,8 +158,8 @@ Plan make_plan(const mmt_attn_desc* d, bool dense) {
 // below R (small images: P = 4, m = 3 gives 31 / 32 against R = 49); never more than R (ids >= R contribute 0 under
 // the one-hot lookup).  0 = not eligible (the general kernels of attn_fwd.hip / attn_bwd.hip take
 // the call).
-int lean2d_width(const mmt::PatternDev& pat, int R, bool dense) {
-  if (dense || pat.id_mode != MMT_IDS_2D || R <= 0) return 0;
+int lean2d_width(const mmt::PatternDev& pat, const mmt::GridDev& grid, int R, bool dense) {
+  if (dense || pat.id_mode != MMT_IDS_2D || R <= 0 || grid.ga > 0) return 0;
   const int d = 2 * pat.r + 1, n2 = d + 2;
   if (n2 * n2 > 256) return 0;                       // look-up table of the clamped (dx, dy) grid
   int need = std::max(d * d + 8, 2 * pat.m + 1);
@@ -155,6 +180,7 @@ void fill_common(mmt::FwdParams& p, const mmt_attn_desc* d) {
   p.tscale = (d->flags & MMT_FLAG_SCALE_BEFORE_ADD) ? mmt::kLog2e : d->scale * mmt::kLog2e;
   p.mask_add = d->mask_value * mmt::kLog2e;
   p.pat = make_pattern(d->mask, d->S);
+  p.grid = make_grid(d->mask);
   p.valid_len = d->mask.valid_len;
   if (d->dropout_p > 0.f) {
     unsigned t = (unsigned)((double)d->dropout_p * 65536.0 + 0.5);
@@ -225,8 +251,10 @@ int mmt_attn_fwd(const mmt_attn_desc* desc, const void* q, const void* k, const 
     p.part_o = reinterpret_cast<float*>(workspace);
     p.part_ml = p.part_o + (size_t)desc->B * desc->N * pl.n_rowblk * pl.n_chunks * (32 * 64);
   }
-  p.lean_rp = lean2d_width(p.pat, desc->R, dense);
-  const bool lean = bf16 && (p.pat.id_mode == 0 || (p.perm_1d && desc->R <= 64) || p.lean_rp);   // attn_fwd_band.hip (tables up to 64 wide)
+  p.lean_rp = lean2d_width(p.pat, p.grid, desc->R, dense);
+  // an image grid (p.grid.ga > 0) is served by the general kernels only (attn_fwd.hip): every lean / window / walk kernel
+  // below needs `lean`, so no tuning switch can route a grid pattern past its grid term
+  const bool lean = bf16 && p.grid.ga == 0 && (p.pat.id_mode == 0 || (p.perm_1d && desc->R <= 64) || p.lean_rp);   // attn_fwd_band.hip (tables up to 64 wide)
   p.part_scale = (lean && p.drop_thresh) ? p.inv_keep : 1.f;
   // window kernel (attn_fwd_win.hip): K / V staged once per workgroup, global keys as a peeled quarter-tile step,
   // rows of up to 16 global tokens by flipped-orientation workgroups of the same launch (no workspace, no combine
@@ -351,11 +379,12 @@ int mmt_attn_bwd(const mmt_attn_desc* desc, const void* q, const void* k, const 
   p.rel_gscale = (desc->flags & MMT_FLAG_SCALE_BEFORE_ADD) ? 1.f : desc->scale;
   p.drel_accum = (desc->flags & MMT_FLAG_ACCUM_REL_GRADS) ? 1 : 0;
   p.pat = f.pat;
+  p.grid = f.grid;
   if (desc->R == 0) { p.pat.id_mode = 0; p.rel_ids = nullptr; }
   p.perm_1d = (!dense && p.pat.id_mode == MMT_IDS_1D && desc->R >= 2 * p.pat.m + 1) ? 1 : 0;
   p.drop_thresh = f.drop_thresh; p.seed_lo = f.seed_lo; p.seed_hi = f.seed_hi; p.inv_keep = f.inv_keep; p.epoch = f.epoch;
   if (desc->dtype == MMT_BF16) {
-    if (const int w2 = lean2d_width(p.pat, desc->R, dense)) {      // lean 2-D path: the kernels run at the narrowed table width
+    if (const int w2 = lean2d_width(p.pat, p.grid, desc->R, dense)) {      // lean 2-D path: the kernels run at the narrowed table width
       p.lean2d = 1;
       p.Rp = w2;
     }
@@ -379,12 +408,13 @@ int mmt_attn_bwd(const mmt_attn_desc* desc, const void* q, const void* k, const 
   // peeled global keys need clipped relative ids only: every peeled key lies beyond the radius, hence beyond max_dist
   p.peel_gkeys = (!dense && pl.split_rows && p.pat.ng <= 8 && (p.pat.id_mode == 0 || (p.perm_1d && p.pat.radius >= p.pat.m))) ? 3 : 0;
   if (!dense && pl.split_rows && p.pat.ng <= 8 && p.lean2d) p.peel_gkeys = 1;      // 2-D ids: the dQ pass's peeled step looks its columns up (the recomputing dK/dV pass keeps its tile visit)
+  if (p.grid.ga > 0) p.peel_gkeys = 0;                                   // an image grid: the general kernels, no peeled steps
   if (desc->tuning & MMT_TUNE_BWD_NO_PEEL_DQ) p.peel_gkeys &= ~1;       // bit 0: dQ pass, bit 1: dK/dV pass
   if (desc->tuning & MMT_TUNE_BWD_NO_PEEL_DKV) p.peel_gkeys &= ~2;
   p.dkv_slots = p.n_chunks;
   {   // P / dS hand-over: the dK/dV pass reads what the dQ pass computed (needs the peeled kind of global tokens, if any)
     const bool on = !(desc->tuning & MMT_TUNE_BWD_NO_HANDOVER);
-    const bool lean = desc->dtype == MMT_BF16 && !dense && (p.pat.id_mode == 0 || (p.perm_1d && p.Rp <= 64) || p.lean2d);
+    const bool lean = desc->dtype == MMT_BF16 && !dense && p.grid.ga == 0 && (p.pat.id_mode == 0 || (p.perm_1d && p.Rp <= 64) || p.lean2d);
     if (on && lean && pl.ho_slots > 0 && (p.pat.ng == 0 || !pl.split_rows || (p.peel_gkeys & 1))) {
       p.ho = reinterpret_cast<unsigned char*>(ws + pl.off_ho);
       p.ho_slots = pl.ho_slots;
@@ -414,12 +444,14 @@ int mmt_side_inputs(const mmt_mask_desc* mask, int32_t B, int32_t S,
     if ((int64_t)mask->patches_per_row * mask->patches_per_row > S) return fail(MMT_E_INVALID, "image part longer than the sequence");
   }
   if (mask->id_mode != MMT_IDS_NONE && mask->max_dist < 0) return fail(MMT_E_INVALID, "`text_relative_pos_max_distance` must be positive.");
+  if (int rc = check_grid(*mask, S)) return rc;
   if (rel_ids_out && mask->id_mode == MMT_IDS_NONE) return fail(MMT_E_INVALID, "rel_ids_out requested with id_mode NONE");
   if (materialize_pattern && (mask->local_radius < 0 || mask->n_global < 0 ||
                               (!mask->global_index && (mask->global_start < 0 || mask->global_start + mask->n_global > S))))
     return fail(MMT_E_INVALID, "bad pattern");
   mmt::SideParams p;
   p.pat = make_pattern(*mask, S);
+  p.grid = make_grid(*mask);
   p.B = B; p.S = S;
   p.img_wp = num_image_wordpieces; p.txt_wp = num_text_wordpieces;
   p.materialize_pattern = materialize_pattern;

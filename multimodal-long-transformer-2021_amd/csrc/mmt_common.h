@@ -41,6 +41,14 @@ struct PatternDev {
   int text_part;   // image_part + 1     (feature_utils.py:82)
 };
 
+// Image-grid term of the pattern (mmt_mask_desc.image_grid).  Kept out of PatternDev and appended to the parameter
+// blocks (FwdParams, BwdParams, SideParams), so that the argument layout -- and the code -- of every kernel that does
+// not take the grid is what it was.  Uses PatternDev's P and magicP.
+struct GridDev {
+  int ga;          // grid radius a (0: no grid term)
+  int gs, gI;      // image positions [gs, gs + gI) of the grid, gI = P*P (0 without a grid)
+};
+
 // 1-D clipped id (etcmodel RelativePositionGenerator).
 __device__ __forceinline__ int id_1d(int q, int k, int m) {
   int d = k - q;
@@ -83,11 +91,23 @@ __device__ __forceinline__ bool is_global(const PatternDev& p, int x) {
   return (unsigned)(x - p.g0) < (unsigned)p.ng;
 }
 
-// mask(q,k) = segmented(q,k) && (|q-k| <= W || global(q) || global(k))   
-__device__ __forceinline__ bool pattern_mask(const PatternDev& p, int valid_len, int q, int k) {
+// grid(q,k): both positions in the image [gs, gs + P*P) and at most `ga` image rows and `ga` columns apart (no wrap
+// across rows).  Row = (x - gs) / P by the exact magicP multiply (x - gs < P*P).  False whenever ga == 0 (gI = 0).
+__device__ __forceinline__ bool in_grid(const PatternDev& p, const GridDev& g, int q, int k) {
+  const unsigned xq = (unsigned)(q - g.gs), xk = (unsigned)(k - g.gs);
+  const int rq = (int)__umulhi(xq, p.magicP), rk = (int)__umulhi(xk, p.magicP);
+  const int cq = (int)xq - rq * p.P, ck = (int)xk - rk * p.P;
+  return (int)(xq < (unsigned)g.gI) & (int)(xk < (unsigned)g.gI) &
+         (int)((unsigned)(rq - rk + g.ga) <= 2u * g.ga) & (int)((unsigned)(cq - ck + g.ga) <= 2u * g.ga);
+}
+
+// mask(q,k) = segmented(q,k) && (|q-k| <= W || global(q) || global(k) || grid(q,k))   
+// GRID = false (kernel instantiations for patterns without the grid term): the term is not evaluated at all.
+template <bool GRID>
+__device__ __forceinline__ bool pattern_mask(const PatternDev& p, const GridDev& g, int valid_len, int q, int k) {
   const bool seg = (q < valid_len) == (k < valid_len);
   const bool near = abs(q - k) <= p.radius;
-  return seg && (near || is_global(p, q) || is_global(p, k));
+  return seg && (near || is_global(p, q) || is_global(p, k) || (GRID && in_grid(p, g, q, k)));
 }
 
 // ---------------------------------------------------------------------------------------

@@ -34,8 +34,9 @@ __global__ __launch_bounds__(256) void side_inputs_kernel(const SideParams p) {
       const int k = k0 + j;
       bool keep = (q < valid) == (k < valid);            // data_utils.py:321-322
       if (p.materialize_pattern) {
-        if (p.gidx) keep = keep && (abs(q - k) <= p.pat.radius || gq || in_list(p.gidx, p.pat.ng, k));   // listed global set
-        else keep = pattern_mask(p.pat, valid, q, k);
+        if (p.gidx) keep = keep && (abs(q - k) <= p.pat.radius || gq || in_list(p.gidx, p.pat.ng, k) ||   // listed global set
+                                    in_grid(p.pat, p.grid, q, k));                                                 // (+ the image grid)
+        else keep = pattern_mask<true>(p.pat, p.grid, valid, q, k);
       }
       mv[j] = keep ? 1 : 0;
       iv[j] = p.pat.id_mode ? rel_id(p.pat, q, k) : 0;

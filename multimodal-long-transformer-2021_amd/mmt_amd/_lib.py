@@ -18,6 +18,12 @@ MMT_F32, MMT_BF16 = 0, 1
 MMT_IDS_NONE, MMT_IDS_1D, MMT_IDS_2D = 0, 1, 2
 MMT_FLAG_SCALE_BEFORE_ADD = 1
 MMT_FLAG_ACCUM_REL_GRADS = 2
+
+
+def image_grid(radius: int, start: int) -> int:
+  """`MMT_IMAGE_GRID(a, g)` of include/mmt_attn.h: the `mmt_mask_desc.image_grid` word (0 = no grid term)."""
+  return (int(radius) & 0xFF) | ((int(start) & 0x7FFFFF) << 8)
+
 # mmt_attn_desc.tuning (include/mmt_attn.h): kernel-selection switches; 0 = the library's defaults
 MMT_TUNE_FWD_WALK = 0x01
 MMT_TUNE_FWD_PWIN = 0x100
@@ -58,7 +64,7 @@ class MaskDesc(ctypes.Structure):
               ('global_start', ctypes.c_int32), ('n_global', ctypes.c_int32),
               ('id_mode', ctypes.c_int32), ('max_dist', ctypes.c_int32),
               ('patches_per_row', ctypes.c_int32), ('core_layers', ctypes.c_int32),
-              ('global_index', ctypes.c_void_p)]
+              ('image_grid', ctypes.c_int32), ('global_index', ctypes.c_void_p)]
 
 
 class AttnDesc(ctypes.Structure):

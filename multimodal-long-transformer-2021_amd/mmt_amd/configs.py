@@ -140,6 +140,7 @@ class MmtDataConfig(Config):        # data/configs.py:20-55 (+ TFM DataConfig ba
   # Build-defined long-sequence pattern; defaults = reference mask.
   local_radius: int = 1 << 30
   num_global_tokens: int = 0
+  image_grid_radius: int = 0        # App. A.5 `grid_radius`: 2-D neighbourhood of the image patches; 0 = off
 
 
 @dataclasses.dataclass

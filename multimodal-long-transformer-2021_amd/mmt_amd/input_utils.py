@@ -45,11 +45,13 @@ def attention_pattern_from_config(data_cfg, encoder_cfg=None) -> AttentionPatter
   r = data_cfg.relative_att_num_core_layers
   n_img = 2 + P * P
   g = int(getattr(data_cfg, 'num_global_tokens', 0))
+  a = int(getattr(data_cfg, 'image_grid_radius', 0))
   return AttentionPattern(
       local_radius=int(getattr(data_cfg, 'local_radius', 1 << 30)),
       global_start=n_img if g else 0, n_global=g,     # the [ATT] marker and the tokens after it
       id_mode=_lib.MMT_IDS_NONE if m <= 0 else (_lib.MMT_IDS_2D if r > 0 else _lib.MMT_IDS_1D),
-      max_dist=m, patches_per_row=P if r > 0 else 0, core_layers=r)
+      max_dist=m, patches_per_row=P if (r > 0 or a > 0) else 0, core_layers=r,
+      grid_radius=a, grid_start=2)                    # the patches sit behind [CLS][PATCH]
 
 
 def synthetic_batch(data_cfg, batch_size: int, device, generator: Optional[torch.Generator] = None,
@@ -87,7 +89,7 @@ def synthetic_batch(data_cfg, batch_size: int, device, generator: Optional[torch
   }
   if dense_side_inputs:     # exactly what the reference feeds: int32 [B,S,S] tensors
     si = side_inputs(pattern, n_image, n_text, S,
-                     materialize_pattern=pattern.local_radius < S or pattern.n_global > 0)
+                     materialize_pattern=pattern.local_radius < S or pattern.n_global > 0 or pattern.grid_radius > 0)
     inputs.update(si)
     if si['relative_att_ids'] is None:
       inputs.pop('relative_att_ids')

@@ -34,6 +34,10 @@ class AttentionPattern:
   positions (a tuple of ints).  A listed set that is in fact a contiguous run takes the structured kernels like
   the range form; any other set is served through the dense operator with the materialised mask (correct, but
   O(S^2) work and memory: there is no structured kernel for scattered global tokens).
+
+  Image grid (`grid_radius` a > 0; SURVEY.md App. A.5 `grid_radius`): patches at most a image rows and a columns
+  apart also attend each other -- the image at positions [grid_start, grid_start + P^2) in raster order,
+  P = `patches_per_row` (which must then be set, whatever `id_mode`; with 1-D ids it changes no id).  0 = off.
   """
   local_radius: int = 1 << 30
   global_start: int = 0
@@ -43,6 +47,8 @@ class AttentionPattern:
   patches_per_row: int = 0
   core_layers: int = 0
   global_index: Optional[tuple] = None
+  grid_radius: int = 0
+  grid_start: int = 2
 
   def normalized(self) -> 'AttentionPattern':
     """The same pattern with a listed global set sorted, de-duplicated and -- when it is a contiguous run -- turned
@@ -65,6 +71,7 @@ class AttentionPattern:
     m.global_start, m.n_global = int(self.global_start), int(self.n_global)
     m.id_mode, m.max_dist = int(self.id_mode), int(self.max_dist)
     m.patches_per_row, m.core_layers = int(self.patches_per_row), int(self.core_layers)
+    m.image_grid = _lib.image_grid(self.grid_radius, self.grid_start) if self.grid_radius > 0 else 0
     m.global_index = None
     if self.global_index is not None:
       if device is None:

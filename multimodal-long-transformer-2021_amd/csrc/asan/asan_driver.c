@@ -104,6 +104,54 @@ int main(void) {
     }
   }
 
+  /* ---- head size 128: the general kernels, forward and backward, whatever the tuning switches; every derived
+   *      workspace pointer inside what mmt_workspace_bytes asked for (exact-size allocations) ---- */
+  {
+    static const int shapes[][8] = {   /* B, S, N, R, n_global, dtype, 2-D ids, grid radius */
+        {2, 512, 2, 9, 8, MMT_BF16, 0, 0},   {1, 300, 3, 0, 0, MMT_F32, 0, 0},  {2, 1024, 2, 49, 0, MMT_BF16, 1, 0},
+        {1, 4096, 6, 100, 8, MMT_BF16, 0, 0}, {2, 200, 2, 32, 8, MMT_F32, 0, 0}, {1, 640, 2, 32, 8, MMT_BF16, 0, 1},
+        {1, 520, 1, 100, 40, MMT_BF16, 1, 2}};
+    const uint32_t tunings[] = {0u, MMT_TUNE_FWD_WALK, MMT_TUNE_FWD_PWIN, MMT_TUNE_FWD_FORCE_WIN, MMT_TUNE_BWD_HO_PER_WAVE};
+    for (unsigned i = 0; i < sizeof(shapes) / sizeof(shapes[0]); ++i) {
+      for (unsigned t = 0; t < sizeof(tunings) / sizeof(tunings[0]); ++t) {
+        const int* s = shapes[i];
+        d = base_desc(s[0], s[1], s[2], s[3], s[5]);
+        d.D = 128;
+        const int64_t st[3] = {(int64_t)s[1] * s[2] * 128, (int64_t)s[2] * 128, 128};
+        for (int j = 0; j < 3; ++j) d.q_stride[j] = d.k_stride[j] = d.v_stride[j] = d.o_stride[j] = st[j];
+        d.mask.n_global = s[4]; d.mask.global_start = s[4] ? s[1] / 2 - s[4] / 2 : 0;
+        if (s[6]) { d.mask.id_mode = MMT_IDS_2D; d.mask.patches_per_row = 16; d.mask.core_layers = 1; }
+        if (s[7]) { d.mask.patches_per_row = 16; d.mask.image_grid = MMT_IMAGE_GRID(s[7], 2); }
+        d.tuning = tunings[t];
+        uint32_t sync[16] = {0};
+        d.sync = sync; d.sync_words = 16;
+        const size_t need = mmt_workspace_bytes(&d);
+        CHECK(need > 0);
+        unsigned char* ws = (unsigned char*)malloc(need);
+        CHECK(ws != NULL);
+        g_ws_lo = ws; g_ws_hi = ws + need;
+        CHECK(mmt_attn_fwd(&d, dummy, dummy, dummy, s[3] ? dummy : NULL, NULL, NULL, NULL, dummy, (float*)dummy, ws, need, NULL) == MMT_OK);
+        CHECK(g_last_kind == (s[4] ? 4 : 1));    /* the general kernel (+ its global-rows combine) */
+        CHECK(mmt_attn_bwd(&d, dummy, dummy, dummy, s[3] ? dummy : NULL, NULL, NULL, NULL, dummy, dummy, (const float*)dummy, dummy, dummy, dummy,
+                           s[3] ? (float*)dummy : NULL, NULL, ws, need, NULL) == MMT_OK);
+        CHECK(g_last_kind == 5 && g_last_handover == 0);
+        /* the dense operator (att_mask given) */
+        CHECK(mmt_attn_fwd(&d, dummy, dummy, dummy, s[3] ? dummy : NULL, NULL, (const int32_t*)dummy, NULL, dummy, (float*)dummy, ws, need, NULL) == MMT_OK);
+        CHECK(g_last_kind == 1);
+        CHECK(mmt_attn_bwd(&d, dummy, dummy, dummy, s[3] ? dummy : NULL, NULL, (const int32_t*)dummy, NULL, dummy, dummy, (const float*)dummy, dummy, dummy, dummy,
+                           s[3] ? (float*)dummy : NULL, NULL, ws, need, NULL) == MMT_OK);
+        free(ws);
+      }
+    }
+    const int refused[] = {0, 32, 96, 256};
+    for (unsigned i = 0; i < sizeof(refused) / sizeof(refused[0]); ++i) {
+      d = base_desc(2, 300, 3, 32, MMT_BF16);
+      d.D = refused[i];
+      CHECK(mmt_workspace_bytes(&d) == 0);
+      CHECK(strstr(mmt_last_error(), "head size 64") != NULL);
+    }
+  }
+
   /* ---- side inputs: the reference generator's argument errors (feature_utils.py:60-65) ---- */
   mmt_mask_desc m;
   memset(&m, 0, sizeof(m));

@@ -30,7 +30,7 @@ namespace mmt {
 hipError_t launch_attn_fwd(const FwdParams& p, int, bool, hipStream_t) {
   ++g_launches; g_last_kind = 1; g_last_epoch = p.epoch;
   const size_t slots = (size_t)p.B * p.N * p.n_rowblk * p.n_chunks;
-  inside(p.part_o, slots * 32 * 64 * 4, "part_o");
+  inside(p.part_o, slots * 32 * p.D * 4, "part_o");
   inside(p.part_ml, slots * 64 * 4, "part_ml");
   return hipSuccess;
 }
@@ -92,15 +92,15 @@ hipError_t launch_attn_bwd(const BwdParams& p, int, bool, hipStream_t) {
   inside(p.delta, bn * p.S * 4, "delta");
   inside(p.relfar, bn * p.S * 2 * 4, "relfar");
   inside(p.drel, bn * (size_t)p.pat.ng * p.Rp * 4, "drel");
-  inside(p.part_dq, slots * 32 * 64 * 4, "part_dq");
+  inside(p.part_dq, slots * 32 * p.D * 4, "part_dq");
   inside(p.part_dtab, slots * 32 * p.Rp * 4, "part_dtab");
-  inside(p.part_dkv, bn * p.n_gblk * (size_t)p.dkv_slots * 2 * 32 * 64 * 4, "part_dkv");
+  inside(p.part_dkv, bn * p.n_gblk * (size_t)p.dkv_slots * 2 * 32 * p.D * 4, "part_dkv");
   if (p.ho) {          // P hand-over: band tiles, global-key strips, global-row tiles (attn_kernels.h)
     const size_t n_tiles = (size_t)(p.S + 31) / 32;
     inside(p.ho, bn * n_tiles * ((size_t)p.ho_slots * 2048 + 512 + 512), "ho");
     if (p.dkv_slots != p.n_chunks + (p.n_gblk > 0 ? 1 : 0)) { std::fprintf(stderr, "asan driver: hand-over without its partial slot\n"); std::abort(); }
   }
-  inside(p.part_red, bn * ((p.S + 127) / 128) * 4 * ((size_t)p.Rp * 64 + p.Rp) * 4, "part_red");
+  inside(p.part_red, bn * ((p.S + 127) / 128) * 4 * ((size_t)p.Rp * p.D + p.Rp) * 4, "part_red");
   return hipSuccess;
 }
 hipError_t launch_side_inputs(const SideParams&, hipStream_t) { ++g_launches; g_last_kind = 6; return hipSuccess; }

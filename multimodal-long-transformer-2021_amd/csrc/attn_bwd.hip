@@ -20,12 +20,16 @@
 
 namespace mmt {
 
-// LDS per wave: T table, dT table (K4a) / second tile (K4b), one or two 32 x 128 B tiles.
-template <typename T, int Rp> struct BwdLds {
+// LDS per wave: T table, dT table (K4a) / second tile (K4b), one or two 32 x 2 DH B tiles.
+template <typename T, int Rp, int DH = 64> struct BwdLds {
   static constexpr int kTab = (32 * kTStride(Rp) * 4 + 15) & ~15;
-  static constexpr int kTile = sizeof(T) == 2 ? 32 * 128 : 0;
+  static constexpr int kTile = sizeof(T) == 2 ? 32 * 2 * DH : 0;
   static constexpr int kBias = Rp * 4;                // bias[id] * tscale
-  static constexpr int kDq = 2 * kTab + kTile + kBias;   // tab, dtab, K/E tile, bias
+  // K4a with whole K / E / Q tiles would pass the CU's 160 KiB at DH = 128, Rp = 128 (4 x 41 984 B): there the tile
+  // is staged in two 64-column halves through one 32 x 128 B buffer (HalfTile), 4 x 37 888 B
+  static constexpr bool kDqHalf = 4 * (2 * kTab + kTile + kBias) > 160 * 1024;
+  static constexpr int kDqTile = kDqHalf ? 32 * 128 : kTile;
+  static constexpr int kDq = 2 * kTab + kDqTile + kBias;   // tab, dtab, K/E tile, bias
   static constexpr int kDkv = kTab + 2 * kTile + kBias;  // tab, Q tile, dO tile, bias
 };
 
@@ -94,16 +98,35 @@ __device__ __forceinline__ void fill_bias(const P& p, int n, float* bias_ts, int
 
 // Builds T[row][col(id)] = (x_row . E[id]) * tscale + bias_ts[id] for the 32 rows whose fragments
 // are in `xf` (row = lane & 31).
-template <typename T, int Rp, bool IDENT, typename P>
-__device__ __forceinline__ void build_table(const P& p, int n, const Frag<T>& xf, float* tab,
+template <typename T, int Rp, bool IDENT, int DH, typename P>
+__device__ __forceinline__ void build_table(const P& p, int n, const Frag<T, DH>& xf, float* tab,
                                             const float* bias_ts, int lane) {
   const int r = lane & 31, h = lane >> 5;
-  const T* E = reinterpret_cast<const T*>(p.emb) + (long)n * 64;
+  const T* E = reinterpret_cast<const T*>(p.emb) + (long)n * DH;
+  if constexpr (DH == 128 && Rp == 128) {
+    // four 32-id blocks one after the other: unrolled, their E fragments (32 VGPRs each) are all loaded ahead and the
+    // dK/dV pass spills
+#pragma nounroll
+    for (int rb = 0; rb < Rp / 32; ++rb) {
+      const int rr = rb * 32 + r;
+      Frag<T, DH> ef;
+      ef.load_row(E + (long)min(rr, p.R - 1) * p.N * DH, h);
+      f32x16 c = {0};
+      c = mma_rows(ef, xf, c);  // [id x row]
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int id = rb * 32 + kap(i, h);
+        const int col = IDENT ? id : tcol(p.perm_1d, p.pat.m, id);
+        tab[r * kTStride(Rp) + col] = fmaf(c[i], p.tscale, bias_ts[id]);
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int rb = 0; rb < Rp / 32; ++rb) {
     const int rr = rb * 32 + r;
-    Frag<T> ef;
-    ef.load_row(E + (long)min(rr, p.R - 1) * p.N * 64, h);
+    Frag<T, DH> ef;
+    ef.load_row(E + (long)min(rr, p.R - 1) * p.N * DH, h);
     f32x16 c = {0};
     c = mma_rows(ef, xf, c);  // [id x row]
 #pragma unroll
@@ -119,18 +142,21 @@ __device__ __forceinline__ void build_table(const P& p, int n, const Frag<T>& xf
 // K4a: dQ, delta, dRel.  Lane (r,h) owns query row q0 + r; registers walk keys.
 // =========================================================================================
 // GRID: as attn_fwd_kernel (attn_fwd.hip) -- GridWalk's union and the grid term in the mask, for image-grid patterns only.
-template <typename T, int MODE, int Rp, bool GEN, bool GRID>
-__global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dq_kernel(const BwdParams p) {
+// DH = 128 (head size): four dQ accumulators (a2, a3: head dims 64 .. 127), one workgroup per CU (at two the bf16 form
+// spills to scratch); XT = the K / Q / E tile, whole or in halves (BwdLds::kDqHalf).
+template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH>
+__global__ __launch_bounds__(256, (sizeof(T) == 2 && DH == 64 ? 2 : 1)) void attn_bwd_dq_kernel(const BwdParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r = lane & 31, h = lane >> 5;
-  using L = BwdLds<T, Rp>;
+  using L = BwdLds<T, Rp, DH>;
+  using XT = std::conditional_t<L::kDqHalf, HalfTile, VTile<T, DH>>;
   unsigned char* wl = smem + wave * L::kDq;
   float* tab = reinterpret_cast<float*>(wl);
   float* dtab = reinterpret_cast<float*>(wl + L::kTab);
   unsigned char* xlds = wl + 2 * L::kTab;
-  float* bias_ts = reinterpret_cast<float*>(wl + 2 * L::kTab + L::kTile);
+  float* bias_ts = reinterpret_cast<float*>(wl + 2 * L::kTab + L::kDqTile);
   constexpr bool IDENT = MODE == kDense || GEN;
 
   const int n_tiles = (p.S + 31) >> 5, nqb = (p.S + 127) >> 7;
@@ -176,15 +202,15 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dq_ker
     t_cur = gw.next(0);
   }
 
-  Frag<T> qf, dof;
+  Frag<T, DH> qf, dof;
   qf.load_row(Q + qc * qs1, h);
   dof.load_row(DO + qc * os1, h);
   float delta;
   {
-    Frag<T> of;
+    Frag<T, DH> of;
     of.load_row(O + qc * os1, h);
     float acc = 0.f;
-    constexpr int kN = sizeof(T) == 2 ? 4 : 32;
+    constexpr int kN = sizeof(T) == 2 ? DH / 16 : DH / 2;
 #pragma unroll
     for (int s = 0; s < kN; ++s) {
       if constexpr (sizeof(T) == 2) {
@@ -204,17 +230,18 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dq_ker
   for (int i = lane; i < 32 * kTStride(Rp); i += 64) dtab[i] = 0.f;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
-  if (p.R > 0) build_table<T, Rp, IDENT>(p, n, qf, tab, bias_ts, lane);
+  if (p.R > 0) build_table<T, Rp, IDENT, DH>(p, n, qf, tab, bias_ts, lane);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
 
   f32x16 a0 = {0}, a1 = {0};
+  f32x16 a2 = {0}, a3 = {0};   // DH = 128
   float far_neg = 0.f, far_pos = 0.f;
   const float* trow = tab + r * kTStride(Rp);
   float* dtrow = dtab + r * kTStride(Rp);
   const int n_it = w.count();
-  Frag<T> kf, vf;
-  VTile<T> kt;
+  Frag<T, DH> kf, vf;
+  XT kt;
   {
     const int k0 = (GRID ? t_cur : w.at(0)) * 32;
     kf.load_row(K + (unsigned)min(k0 + r, p.S - 1) * ks1, h);
@@ -224,8 +251,8 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dq_ker
   for (int it = 0; GRID ? t_cur != GridWalk::kEnd : it < n_it; ++it, t_cur = t_nxt) {
     const int k0 = (GRID ? t_cur : w.at(it)) * 32;
     kt.to_lds(xlds, lane);
-    VTile<T> kcur;
-    if constexpr (sizeof(T) == 4) kcur = kt;
+    XT kcur;                     // (a HalfTile is staged by the product at the end: it keeps the tile across the prefetch)
+    if constexpr (sizeof(T) == 4 || L::kDqHalf) kcur = kt;
     f32x16 c = {0}, dp = {0};
     c = mma_rows(kf, qf, c);     // S^T  [key x q]
     dp = mma_rows(vf, dof, dp);  // dP^T [key x q]
@@ -284,8 +311,13 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dq_ker
     }
 #pragma unroll
     for (int i = 0; i < 16; ++i) g[i] *= p.gscale;
-    if constexpr (sizeof(T) == 2) mma_xt(a0, a1, kt, xlds, g, lane);   // dQ^T += K^T . dS^T
-    else mma_xt(a0, a1, kcur, xlds, g, lane);
+    if constexpr (DH == 128) {
+      if constexpr (sizeof(T) == 2 && !L::kDqHalf) mma_xt(a0, a1, a2, a3, kt, xlds, g, lane);
+      else mma_xt(a0, a1, a2, a3, kcur, xlds, g, lane);
+    } else {
+      if constexpr (sizeof(T) == 2) mma_xt(a0, a1, kt, xlds, g, lane);   // dQ^T += K^T . dS^T
+      else mma_xt(a0, a1, kcur, xlds, g, lane);
+    }
   }
   if (!IDENT && p.pat.id_mode == 1) {       // flush the clipped columns (both halves of the row)
     const float fn = half_sum(far_neg), fp = half_sum(far_pos);
@@ -299,11 +331,15 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dq_ker
 
   if (split_item) {
     const long slot = ((long)bn * p.n_gblk + gblk) * p.n_chunks + chunk;
-    float* po = p.part_dq + slot * (32 * 64) + r * 64;
+    float* po = p.part_dq + slot * (32 * DH) + r * DH;
 #pragma unroll
     for (int gi = 0; gi < 4; ++gi) {
       *reinterpret_cast<f32x4*>(po + 8 * gi + 4 * h) = f32x4{a0[4 * gi], a0[4 * gi + 1], a0[4 * gi + 2], a0[4 * gi + 3]};
       *reinterpret_cast<f32x4*>(po + 32 + 8 * gi + 4 * h) = f32x4{a1[4 * gi], a1[4 * gi + 1], a1[4 * gi + 2], a1[4 * gi + 3]};
+      if constexpr (DH == 128) {
+        *reinterpret_cast<f32x4*>(po + 64 + 8 * gi + 4 * h) = f32x4{a2[4 * gi], a2[4 * gi + 1], a2[4 * gi + 2], a2[4 * gi + 3]};
+        *reinterpret_cast<f32x4*>(po + 96 + 8 * gi + 4 * h) = f32x4{a3[4 * gi], a3[4 * gi + 1], a3[4 * gi + 2], a3[4 * gi + 3]};
+      }
     }
     float* pt = p.part_dtab + slot * (32 * Rp);
     for (int i = lane; i < 32 * Rp; i += 64) {
@@ -317,11 +353,11 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dq_ker
     // (1) this wave's share of dE^T[d x id] = sum_q Q[q][d] * dRel[q][id] and dbias[id] (lane = id).
     //     Rows of global tokens are excluded here when they are produced by the split items.
     {
-      VTile<T> qt;
+      XT qt;
       qt.load(Q, qs1, q0, p.S, lane, 0);
       qt.to_lds(xlds, lane);
       const int widx = (xcd_remap(blockIdx.x, p.n_band_blocks)) * 4 + wave;
-      float* pe = p.part_red + (long)widx * (Rp * 64 + Rp);
+      float* pe = p.part_red + (long)widx * (Rp * DH + Rp);
 #pragma unroll
       for (int rb = 0; rb < Rp / 32; ++rb) {
         const int id = rb * 32 + r;
@@ -336,18 +372,24 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dq_ker
         }
         bsum = half_sum(bsum);
         f32x16 e0 = {0}, e1 = {0};
-        mma_xt_hilo(e0, e1, qt, xlds, vals, lane);
-        float* row = pe + (long)id * 64;
+        f32x16 e2 = {0}, e3 = {0};   // DH = 128
+        if constexpr (DH == 128) mma_xt_hilo(e0, e1, e2, e3, qt, xlds, vals, lane);
+        else mma_xt_hilo(e0, e1, qt, xlds, vals, lane);
+        float* row = pe + (long)id * DH;
 #pragma unroll
         for (int gi = 0; gi < 4; ++gi) {
           *reinterpret_cast<f32x4*>(row + 8 * gi + 4 * h) = f32x4{e0[4 * gi], e0[4 * gi + 1], e0[4 * gi + 2], e0[4 * gi + 3]};
           *reinterpret_cast<f32x4*>(row + 32 + 8 * gi + 4 * h) = f32x4{e1[4 * gi], e1[4 * gi + 1], e1[4 * gi + 2], e1[4 * gi + 3]};
+          if constexpr (DH == 128) {
+            *reinterpret_cast<f32x4*>(row + 64 + 8 * gi + 4 * h) = f32x4{e2[4 * gi], e2[4 * gi + 1], e2[4 * gi + 2], e2[4 * gi + 3]};
+            *reinterpret_cast<f32x4*>(row + 96 + 8 * gi + 4 * h) = f32x4{e3[4 * gi], e3[4 * gi + 1], e3[4 * gi + 2], e3[4 * gi + 3]};
+          }
         }
-        if (h == 0) pe[Rp * 64 + id] = bsum;
+        if (h == 0) pe[Rp * DH + id] = bsum;
       }
     }
     // (2) dQ^T += E^T[d x id] . dRel^T[id x q]   (dRel at ~16 mantissa bits: hi/lo bf16 split)
-    const T* E = reinterpret_cast<const T*>(p.emb) + (long)n * 64;
+    const T* E = reinterpret_cast<const T*>(p.emb) + (long)n * DH;
 #pragma unroll
     for (int rb = 0; rb < Rp / 32; ++rb) {
       float vals[16];
@@ -356,10 +398,11 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dq_ker
         const int id = rb * 32 + kap(i, h);
         vals[i] = id < p.R ? dtrow[IDENT ? id : tcol(p.perm_1d, p.pat.m, id)] : 0.f;
       }
-      VTile<T> et;   // rows = ids rb*32 .. rb*32+31 of E (clamped past R: their dRel is 0)
-      et.load(E + (long)(rb * 32) * p.N * 64, (unsigned)(p.N * 64), 0, max(p.R - rb * 32, 1), lane, 0);
+      XT et;   // rows = ids rb*32 .. rb*32+31 of E (clamped past R: their dRel is 0)
+      et.load(E + (long)(rb * 32) * p.N * DH, (unsigned)(p.N * DH), 0, max(p.R - rb * 32, 1), lane, 0);
       et.to_lds(xlds, lane);
-      mma_xt_hilo(a0, a1, et, xlds, vals, lane);
+      if constexpr (DH == 128) mma_xt_hilo(a0, a1, a2, a3, et, xlds, vals, lane);
+      else mma_xt_hilo(a0, a1, et, xlds, vals, lane);
     }
   }
   if (!q_ok || (p.skip_global && is_global(p.pat, q))) return;
@@ -373,32 +416,42 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dq_ker
       for (int j = 0; j < 4; ++j) { x[j] = (__bf16)a0[4 * gi + j]; y[j] = (__bf16)a1[4 * gi + j]; }
       *reinterpret_cast<bf16x4*>(DQ + d) = x;
       *reinterpret_cast<bf16x4*>(DQ + 32 + d) = y;
+      if constexpr (DH == 128) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { x[j] = (__bf16)a2[4 * gi + j]; y[j] = (__bf16)a3[4 * gi + j]; }
+        *reinterpret_cast<bf16x4*>(DQ + 64 + d) = x;
+        *reinterpret_cast<bf16x4*>(DQ + 96 + d) = y;
+      }
     } else {
       *reinterpret_cast<f32x4*>(DQ + d) = f32x4{a0[4 * gi], a0[4 * gi + 1], a0[4 * gi + 2], a0[4 * gi + 3]};
       *reinterpret_cast<f32x4*>(DQ + 32 + d) = f32x4{a1[4 * gi], a1[4 * gi + 1], a1[4 * gi + 2], a1[4 * gi + 3]};
+      if constexpr (DH == 128) {
+        *reinterpret_cast<f32x4*>(DQ + 64 + d) = f32x4{a2[4 * gi], a2[4 * gi + 1], a2[4 * gi + 2], a2[4 * gi + 3]};
+        *reinterpret_cast<f32x4*>(DQ + 96 + d) = f32x4{a3[4 * gi], a3[4 * gi + 1], a3[4 * gi + 2], a3[4 * gi + 3]};
+      }
     }
   }
 }
 
-// Global rows: sum the chunk partials, add dRel.E, write dQ and the row's dRel (for dE/dbias).
-template <typename T>
-__global__ __launch_bounds__(64) void attn_bwd_dq_combine_kernel(const BwdParams p) {
+// Global rows: sum the chunk partials, add dRel.E, write dQ and the row's dRel (for dE/dbias).  DH threads.
+template <typename T, int DH>
+__global__ __launch_bounds__(DH) void attn_bwd_dq_combine_kernel(const BwdParams p) {
   __shared__ float dr_s[128];
-  dq_combine_row<T>(p, blockIdx.y, blockIdx.x, threadIdx.x, dr_s, [] { __syncthreads(); });
+  dq_combine_row<T, DH>(p, blockIdx.y, blockIdx.x, threadIdx.x, dr_s, [] { __syncthreads(); });
 }
 
 // =========================================================================================
 // K4b: dK, dV.  Lane (r,h) owns key k0 + r; registers walk query rows.
 // =========================================================================================
 // GRID instantiations are built for one workgroup per CU: at two the bf16 form spills to scratch (as the GRID = false
-// ones do, whose figures are kept as they were).
-template <typename T, int MODE, int Rp, bool GEN, bool GRID>
-__global__ __launch_bounds__(256, ((sizeof(T) == 2 && !GRID) ? 2 : 1)) void attn_bwd_dkv_kernel(const BwdParams p) {
+// ones do, whose figures are kept as they were).  So are the DH = 128 ones (dk2, dk3, dv2, dv3: head dims 64 .. 127).
+template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH>
+__global__ __launch_bounds__(256, ((sizeof(T) == 2 && !GRID && DH == 64) ? 2 : 1)) void attn_bwd_dkv_kernel(const BwdParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r = lane & 31, h = lane >> 5;
-  using L = BwdLds<T, Rp>;
+  using L = BwdLds<T, Rp, DH>;
   unsigned char* wl = smem + wave * L::kDkv;
   float* tab = reinterpret_cast<float*>(wl);
   unsigned char* qlds = wl + L::kTab;
@@ -450,15 +503,16 @@ __global__ __launch_bounds__(256, ((sizeof(T) == 2 && !GRID) ? 2 : 1)) void attn
     t_cur = gw.next(0);
   }
 
-  Frag<T> kf, vf;
+  Frag<T, DH> kf, vf;
   kf.load_row(K + kc * ks1, h);
   vf.load_row(V + kc * vs1, h);
   f32x16 dk0 = {0}, dk1 = {0}, dv0 = {0}, dv1 = {0};
+  f32x16 dk2 = {0}, dk3 = {0}, dv2 = {0}, dv3 = {0};   // DH = 128
   fill_bias<T, Rp>(p, n, bias_ts, lane);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   const int n_it = w.count();
-  VTile<T> qt, dot;
+  VTile<T, DH> qt, dot;
   if constexpr (sizeof(T) == 2) {            // first tile's rows (prefetch registers)
     qt.load(Q, qs1, (GRID ? t_cur : w.at(0)) * 32, p.S, lane, 0);
     dot.load(DO, os1, (GRID ? t_cur : w.at(0)) * 32, p.S, lane, 0);
@@ -466,7 +520,7 @@ __global__ __launch_bounds__(256, ((sizeof(T) == 2 && !GRID) ? 2 : 1)) void attn
   for (int it = 0; GRID ? t_cur != GridWalk::kEnd : it < n_it; ++it, t_cur = t_nxt) {
     const int q0 = (GRID ? t_cur : w.at(it)) * 32;
     if constexpr (GRID) t_nxt = gw.next(t_cur + 1);
-    Frag<T> qf, dof;
+    Frag<T, DH> qf, dof;
     if constexpr (sizeof(T) == 2) {
       qt.to_lds(qlds, lane);
       dot.to_lds(dolds, lane);
@@ -483,7 +537,7 @@ __global__ __launch_bounds__(256, ((sizeof(T) == 2 && !GRID) ? 2 : 1)) void attn
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     if constexpr (sizeof(T) == 2) frag_from_tile(qf, qlds, lane);
-    if (p.R > 0) build_table<T, Rp, IDENT>(p, n, qf, tab, bias_ts, lane);   // T rows = this q tile
+    if (p.R > 0) build_table<T, Rp, IDENT, DH>(p, n, qf, tab, bias_ts, lane);   // T rows = this q tile
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     f32x16 c = {0}, dp = {0};
@@ -525,22 +579,33 @@ __global__ __launch_bounds__(256, ((sizeof(T) == 2 && !GRID) ? 2 : 1)) void attn
         g[i] = pr * (dp[i] * df - d4[j]) * p.gscale;
       }
     }
-    mma_xt(dv0, dv1, dot, dolds, pv, lane);  // dV^T[d x key] += dO^T[d x q] . P[q x key]
-    mma_xt(dk0, dk1, qt, qlds, g, lane);     // dK^T[d x key] += Q^T[d x q] . dS[q x key]
+    if constexpr (DH == 128) {
+      mma_xt(dv0, dv1, dv2, dv3, dot, dolds, pv, lane);
+      mma_xt(dk0, dk1, dk2, dk3, qt, qlds, g, lane);
+    } else {
+      mma_xt(dv0, dv1, dot, dolds, pv, lane);  // dV^T[d x key] += dO^T[d x q] . P[q x key]
+      mma_xt(dk0, dk1, qt, qlds, g, lane);     // dK^T[d x key] += Q^T[d x q] . dS[q x key]
+    }
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     __builtin_amdgcn_wave_barrier();
   }
 
   if (split_item) {
     const long slot = ((long)bn * p.n_gblk + gblk) * p.dkv_slots + chunk;
-    float* pk = p.part_dkv + slot * (2 * 32 * 64) + r * 64;
-    float* pv2 = pk + 32 * 64;
+    float* pk = p.part_dkv + slot * (2 * 32 * DH) + r * DH;
+    float* pv2 = pk + 32 * DH;
 #pragma unroll
     for (int gi = 0; gi < 4; ++gi) {
       *reinterpret_cast<f32x4*>(pk + 8 * gi + 4 * h) = f32x4{dk0[4 * gi], dk0[4 * gi + 1], dk0[4 * gi + 2], dk0[4 * gi + 3]};
       *reinterpret_cast<f32x4*>(pk + 32 + 8 * gi + 4 * h) = f32x4{dk1[4 * gi], dk1[4 * gi + 1], dk1[4 * gi + 2], dk1[4 * gi + 3]};
       *reinterpret_cast<f32x4*>(pv2 + 8 * gi + 4 * h) = f32x4{dv0[4 * gi], dv0[4 * gi + 1], dv0[4 * gi + 2], dv0[4 * gi + 3]};
       *reinterpret_cast<f32x4*>(pv2 + 32 + 8 * gi + 4 * h) = f32x4{dv1[4 * gi], dv1[4 * gi + 1], dv1[4 * gi + 2], dv1[4 * gi + 3]};
+      if constexpr (DH == 128) {
+        *reinterpret_cast<f32x4*>(pk + 64 + 8 * gi + 4 * h) = f32x4{dk2[4 * gi], dk2[4 * gi + 1], dk2[4 * gi + 2], dk2[4 * gi + 3]};
+        *reinterpret_cast<f32x4*>(pk + 96 + 8 * gi + 4 * h) = f32x4{dk3[4 * gi], dk3[4 * gi + 1], dk3[4 * gi + 2], dk3[4 * gi + 3]};
+        *reinterpret_cast<f32x4*>(pv2 + 64 + 8 * gi + 4 * h) = f32x4{dv2[4 * gi], dv2[4 * gi + 1], dv2[4 * gi + 2], dv2[4 * gi + 3]};
+        *reinterpret_cast<f32x4*>(pv2 + 96 + 8 * gi + 4 * h) = f32x4{dv3[4 * gi], dv3[4 * gi + 1], dv3[4 * gi + 2], dv3[4 * gi + 3]};
+      }
     }
     return;
   }
@@ -559,47 +624,67 @@ __global__ __launch_bounds__(256, ((sizeof(T) == 2 && !GRID) ? 2 : 1)) void attn
       }
       *reinterpret_cast<bf16x4*>(DK + d) = x; *reinterpret_cast<bf16x4*>(DK + 32 + d) = y;
       *reinterpret_cast<bf16x4*>(DV + d) = z; *reinterpret_cast<bf16x4*>(DV + 32 + d) = u;
+      if constexpr (DH == 128) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          x[j] = (__bf16)dk2[4 * gi + j]; y[j] = (__bf16)dk3[4 * gi + j];
+          z[j] = (__bf16)dv2[4 * gi + j]; u[j] = (__bf16)dv3[4 * gi + j];
+        }
+        *reinterpret_cast<bf16x4*>(DK + 64 + d) = x; *reinterpret_cast<bf16x4*>(DK + 96 + d) = y;
+        *reinterpret_cast<bf16x4*>(DV + 64 + d) = z; *reinterpret_cast<bf16x4*>(DV + 96 + d) = u;
+      }
     } else {
       *reinterpret_cast<f32x4*>(DK + d) = f32x4{dk0[4 * gi], dk0[4 * gi + 1], dk0[4 * gi + 2], dk0[4 * gi + 3]};
       *reinterpret_cast<f32x4*>(DK + 32 + d) = f32x4{dk1[4 * gi], dk1[4 * gi + 1], dk1[4 * gi + 2], dk1[4 * gi + 3]};
       *reinterpret_cast<f32x4*>(DV + d) = f32x4{dv0[4 * gi], dv0[4 * gi + 1], dv0[4 * gi + 2], dv0[4 * gi + 3]};
       *reinterpret_cast<f32x4*>(DV + 32 + d) = f32x4{dv1[4 * gi], dv1[4 * gi + 1], dv1[4 * gi + 2], dv1[4 * gi + 3]};
+      if constexpr (DH == 128) {
+        *reinterpret_cast<f32x4*>(DK + 64 + d) = f32x4{dk2[4 * gi], dk2[4 * gi + 1], dk2[4 * gi + 2], dk2[4 * gi + 3]};
+        *reinterpret_cast<f32x4*>(DK + 96 + d) = f32x4{dk3[4 * gi], dk3[4 * gi + 1], dk3[4 * gi + 2], dk3[4 * gi + 3]};
+        *reinterpret_cast<f32x4*>(DV + 64 + d) = f32x4{dv2[4 * gi], dv2[4 * gi + 1], dv2[4 * gi + 2], dv2[4 * gi + 3]};
+        *reinterpret_cast<f32x4*>(DV + 96 + d) = f32x4{dv3[4 * gi], dv3[4 * gi + 1], dv3[4 * gi + 2], dv3[4 * gi + 3]};
+      }
     }
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(64) void attn_bwd_dkv_combine_kernel(const BwdParams p) {
-  dkv_combine_row<T>(p, blockIdx.y, blockIdx.x, threadIdx.x);
+template <typename T, int DH>
+__global__ __launch_bounds__(DH) void attn_bwd_dkv_combine_kernel(const BwdParams p) {
+  dkv_combine_row<T, DH>(p, blockIdx.y, blockIdx.x, threadIdx.x);
 }
 
 // =========================================================================================
 // K4c: dE[id,n,:] = sum over the per-wave partials of head n (+ the rows of global tokens),
-// dbias likewise.  Fixed summation order: bitwise reproducible.  grid (Rp, N), 64 threads = d.
+// dbias likewise.  Fixed summation order: bitwise reproducible.  grid (Rp, N), 64 threads = d; at DH = 128 thread d
+// also sums column 64 + d (acc2), in the same order.
 // =========================================================================================
-template <typename T>
+template <typename T, int DH>
 __global__ __launch_bounds__(1024) void drel_reduce_kernel(const BwdParams p) {
-  __shared__ float red[16][64], redb[16];
+  __shared__ float red[16][DH], redb[16];
   const int id = blockIdx.x, n = blockIdx.y, d = threadIdx.x & 63, part = threadIdx.x >> 6;
   if (id >= p.Rp) {            // lean path: the dK/dV combine of the global rows rides along (16 rows per block)
-    const int pair = ((id - p.Rp) * p.N + n) * 16 + part;
-    if (pair < p.pat.ng * p.B * p.N) dkv_combine_row<T>(p, pair / p.pat.ng, pair % p.pat.ng, d);
+    if constexpr (DH == 64) {
+      const int pair = ((id - p.Rp) * p.N + n) * 16 + part;
+      if (pair < p.pat.ng * p.B * p.N) dkv_combine_row<T>(p, pair / p.pat.ng, pair % p.pat.ng, d);
+    }
     return;
   }
   if (id >= p.R) return;
-  const int per = p.Rp * 64 + p.Rp;
+  const int per = p.Rp * DH + p.Rp;
   const int waves_per_bn = p.red_per_plane;       // partial slots per plane (one per wave, or per workgroup)
   const int live = p.red_live;                    // slots past the end of the sequence were not written
   const int total = p.B * live;
   const int chunk = (total + 15) >> 4;
   const int lo = part * chunk, hi = min(total, lo + chunk);
   float acc = 0.f, bs = 0.f;
+  float acc2 = 0.f;                               // DH = 128: column 64 + d
 #pragma unroll 8
   for (int i = lo; i < hi; ++i) {
     const int b = i / live, w = i - b * live;
     const float* src = p.part_red + ((long)(b * p.N + n) * waves_per_bn + w) * per;
-    acc += src[id * 64 + d];
-    if (d == 0) bs += src[p.Rp * 64 + id];
+    acc += src[id * DH + d];
+    if constexpr (DH == 128) acc2 += src[id * DH + 64 + d];
+    if (d == 0) bs += src[p.Rp * DH + id];
   }
   if (p.n_gblk > 0) {                             // rows of global tokens (from the combine): dealt over the 16
     const int pairs = p.B * p.pat.ng;             // parts, so that no part walks a long chain of dependent loads
@@ -609,17 +694,24 @@ __global__ __launch_bounds__(1024) void drel_reduce_kernel(const BwdParams p) {
       const float x = p.drel[((long)(b * p.N + n) * p.pat.ng + g) * p.Rp + id];
       const T* Q = reinterpret_cast<const T*>(p.q) + (long)b * p.qs[0] + (long)n * p.qs[2];
       acc = fmaf(x, (float)Q[(long)(p.pat.g0 + g) * p.qs[1] + d], acc);
+      if constexpr (DH == 128) acc2 = fmaf(x, (float)Q[(long)(p.pat.g0 + g) * p.qs[1] + 64 + d], acc2);
       if (d == 0) bs += x;
     }
   }
   red[part][d] = acc;
+  if constexpr (DH == 128) red[part][64 + d] = acc2;
   if (d == 0) redb[part] = bs;
   __syncthreads();
   if (part == 0) {
     float a = 0.f, bsum = 0.f;
     for (int j = 0; j < 16; ++j) { a += red[j][d]; bsum += redb[j]; }
-    float* de = p.drel_emb + ((long)id * p.N + n) * 64 + d;
+    float* de = p.drel_emb + ((long)id * p.N + n) * DH + d;
     *de = p.drel_accum ? *de + a : a;
+    if constexpr (DH == 128) {
+      float a2 = 0.f;
+      for (int j = 0; j < 16; ++j) a2 += red[j][64 + d];
+      de[64] = p.drel_accum ? de[64] + a2 : a2;
+    }
     if (d == 0 && p.drel_bias) {
       float* db = p.drel_bias + (long)id * p.N + n;
       *db = p.drel_accum ? *db + bsum : bsum;
@@ -634,75 +726,78 @@ static void allow_lds(K kernel, int bytes) {
                                                    hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
-template <typename T, int MODE, int Rp, bool GEN, bool GRID>
+template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH>
 static hipError_t launch_bwd_one(const BwdParams& p_in, hipStream_t st) {
   BwdParams p = p_in;
   p.red_per_plane = ((p.S + 127) >> 7) * 4;               // one dE partial per wave (32 rows)
   p.red_live = (p.S + 31) >> 5;
   const int per_bn = (p.n_chunks * p.n_gblk + 3) / 4;
   dim3 grid(p.n_band_blocks + (MODE == kBand ? per_bn * p.B * p.N : 0));
-  const int lds_a = 4 * BwdLds<T, Rp>::kDq, lds_b = 4 * BwdLds<T, Rp>::kDkv;
-  allow_lds(attn_bwd_dq_kernel<T, MODE, Rp, GEN, GRID>, lds_a);
-  allow_lds(attn_bwd_dkv_kernel<T, MODE, Rp, GEN, GRID>, lds_b);
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<T, MODE, Rp, GEN, GRID>), grid, dim3(256), lds_a, st, p);
+  const int lds_a = 4 * BwdLds<T, Rp, DH>::kDq, lds_b = 4 * BwdLds<T, Rp, DH>::kDkv;
+  allow_lds(attn_bwd_dq_kernel<T, MODE, Rp, GEN, GRID, DH>, lds_a);
+  allow_lds(attn_bwd_dkv_kernel<T, MODE, Rp, GEN, GRID, DH>, lds_b);
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<T, MODE, Rp, GEN, GRID, DH>), grid, dim3(256), lds_a, st, p);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (MODE == kBand && p.n_gblk > 0) {
-    hipLaunchKernelGGL(attn_bwd_dq_combine_kernel<T>, dim3(p.pat.ng, p.B * p.N), dim3(64), 0, st, p);
+    hipLaunchKernelGGL((attn_bwd_dq_combine_kernel<T, DH>), dim3(p.pat.ng, p.B * p.N), dim3(DH), 0, st, p);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
-  hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, MODE, Rp, GEN, GRID>), grid, dim3(256), lds_b, st, p);
+  hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, MODE, Rp, GEN, GRID, DH>), grid, dim3(256), lds_b, st, p);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if (MODE == kBand && p.n_gblk > 0) {
-    hipLaunchKernelGGL(attn_bwd_dkv_combine_kernel<T>, dim3(p.pat.ng, p.B * p.N), dim3(64), 0, st, p);
+    hipLaunchKernelGGL((attn_bwd_dkv_combine_kernel<T, DH>), dim3(p.pat.ng, p.B * p.N), dim3(DH), 0, st, p);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   if (p.R > 0) {
-    hipLaunchKernelGGL(drel_reduce_kernel<T>, dim3(p.Rp, p.N), dim3(1024), 0, st, p);
+    hipLaunchKernelGGL((drel_reduce_kernel<T, DH>), dim3(p.Rp, p.N), dim3(1024), 0, st, p);
     e = hipGetLastError();
   }
   return e;
 }
 
-template <typename T, int MODE, bool GEN, bool GRID>
+template <typename T, int MODE, bool GEN, bool GRID, int DH>
 static hipError_t launch_bwd_rp(const BwdParams& p, hipStream_t st) {
-  if (p.Rp == 32) return launch_bwd_one<T, MODE, 32, GEN, GRID>(p, st);
-  if (p.Rp == 64) return launch_bwd_one<T, MODE, 64, GEN, GRID>(p, st);
-  return launch_bwd_one<T, MODE, 128, GEN, GRID>(p, st);
+  if (p.Rp == 32) return launch_bwd_one<T, MODE, 32, GEN, GRID, DH>(p, st);
+  if (p.Rp == 64) return launch_bwd_one<T, MODE, 64, GEN, GRID, DH>(p, st);
+  return launch_bwd_one<T, MODE, 128, GEN, GRID, DH>(p, st);
 }
 
-template <typename T>
+template <typename T, int DH>
 static hipError_t launch_bwd_t(const BwdParams& p, int mode, hipStream_t st) {
-  if (mode == kDense) return launch_bwd_rp<T, kDense, true, false>(p, st);
+  if (mode == kDense) return launch_bwd_rp<T, kDense, true, false, DH>(p, st);
   const bool gen = !(p.pat.id_mode == 0 || p.perm_1d);
   if (p.grid.ga > 0)                 // image grid: its own instantiations
-    return gen ? launch_bwd_rp<T, kBand, true, true>(p, st) : launch_bwd_rp<T, kBand, false, true>(p, st);
-  return gen ? launch_bwd_rp<T, kBand, true, false>(p, st) : launch_bwd_rp<T, kBand, false, false>(p, st);
+    return gen ? launch_bwd_rp<T, kBand, true, true, DH>(p, st) : launch_bwd_rp<T, kBand, false, true, DH>(p, st);
+  return gen ? launch_bwd_rp<T, kBand, true, false, DH>(p, st) : launch_bwd_rp<T, kBand, false, false, DH>(p, st);
 }
 
+// the lean path's stand-alone combine / reduce launches (attn_bwd_band.hip): head size 64 only
 hipError_t launch_bwd_dq_combine(const BwdParams& p, bool bf16, hipStream_t st) {
   dim3 grid(p.pat.ng, p.B * p.N);
-  if (bf16) hipLaunchKernelGGL(attn_bwd_dq_combine_kernel<__bf16>, grid, dim3(64), 0, st, p);
-  else hipLaunchKernelGGL(attn_bwd_dq_combine_kernel<float>, grid, dim3(64), 0, st, p);
+  if (bf16) hipLaunchKernelGGL((attn_bwd_dq_combine_kernel<__bf16, 64>), grid, dim3(64), 0, st, p);
+  else hipLaunchKernelGGL((attn_bwd_dq_combine_kernel<float, 64>), grid, dim3(64), 0, st, p);
   return hipGetLastError();
 }
 hipError_t launch_bwd_dkv_combine(const BwdParams& p, bool bf16, hipStream_t st) {
   dim3 grid(p.pat.ng, p.B * p.N);
-  if (bf16) hipLaunchKernelGGL(attn_bwd_dkv_combine_kernel<__bf16>, grid, dim3(64), 0, st, p);
-  else hipLaunchKernelGGL(attn_bwd_dkv_combine_kernel<float>, grid, dim3(64), 0, st, p);
+  if (bf16) hipLaunchKernelGGL((attn_bwd_dkv_combine_kernel<__bf16, 64>), grid, dim3(64), 0, st, p);
+  else hipLaunchKernelGGL((attn_bwd_dkv_combine_kernel<float, 64>), grid, dim3(64), 0, st, p);
   return hipGetLastError();
 }
 hipError_t launch_drel_reduce(const BwdParams& p, bool bf16, hipStream_t st) {
   int extra = 0;               // blocks (x >= Rp) that combine the dK/dV partials of the global rows, 16 rows each
   if (p.comb_in_next && p.n_gblk > 0) extra = (p.pat.ng * p.B * p.N + 16 * p.N - 1) / (16 * p.N);
-  if (bf16) hipLaunchKernelGGL(drel_reduce_kernel<__bf16>, dim3(p.Rp + extra, p.N), dim3(1024), 0, st, p);
-  else hipLaunchKernelGGL(drel_reduce_kernel<float>, dim3(p.Rp + extra, p.N), dim3(1024), 0, st, p);
+  if (bf16) hipLaunchKernelGGL((drel_reduce_kernel<__bf16, 64>), dim3(p.Rp + extra, p.N), dim3(1024), 0, st, p);
+  else hipLaunchKernelGGL((drel_reduce_kernel<float, 64>), dim3(p.Rp + extra, p.N), dim3(1024), 0, st, p);
   return hipGetLastError();
 }
 
 hipError_t launch_attn_bwd(const BwdParams& p, int mode, bool bf16, hipStream_t st) {
+  // head size 128 and the image grid: the general kernels only (the lean kernels are built for head size 64)
+  if (p.D == 128) return bf16 ? launch_bwd_t<__bf16, 128>(p, mode, st) : launch_bwd_t<float, 128>(p, mode, st);
   if (mode == kBand && bf16 && p.grid.ga == 0 && (p.pat.id_mode == 0 || (p.perm_1d && p.Rp <= 64) || p.lean2d)) return launch_attn_bwd_band_bf16(p, st);
-  return bf16 ? launch_bwd_t<__bf16>(p, mode, st) : launch_bwd_t<float>(p, mode, st);
+  return bf16 ? launch_bwd_t<__bf16, 64>(p, mode, st) : launch_bwd_t<float, 64>(p, mode, st);
 }
 
 }  // namespace mmt

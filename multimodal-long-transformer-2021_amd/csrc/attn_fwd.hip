@@ -25,15 +25,16 @@ namespace mmt {
 // vocabulary is smaller than 2m+1); GEN = false: no ids or 1-D ids with the permuted table.
 // GRID = true (kBand only): the pattern has the image-grid term -- the tile walk is GridWalk's union and the
 // per-element mask ORs in_grid; GRID = false instantiations (every pattern without a grid) are the kernels as before.
-template <typename T, int MODE, int Rp, bool GEN, bool GRID>
+// DH = head size, 64 or 128: fragments and V tile scale with it; DH = 128 adds the O accumulators o2, o3.
+template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r = lane & 31, h = lane >> 5;
-  unsigned char* wl = smem + wave * WaveLds<T, Rp>::kBytes;
+  unsigned char* wl = smem + wave * WaveLds<T, Rp, DH>::kBytes;
   float* tab = reinterpret_cast<float*>(wl);
-  unsigned char* vlds = wl + WaveLds<T, Rp>::kTBytesAligned;
+  unsigned char* vlds = wl + WaveLds<T, Rp, DH>::kTBytesAligned;
 
   // ---- which 32 query rows does this wave own? ------------------------------------
   const int n_tiles = (p.S + 31) >> 5;
@@ -97,12 +98,12 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
     t_cur = gw.next(0);
   }
 
-  Frag<T> qf;
+  Frag<T, DH> qf;
   qf.load_row(Q + (unsigned)min(q, p.S - 1) * qs1, h);
 
   // prefetch of the first tile overlaps the table construction
-  Frag<T> kf;
-  VTile<T> vt;
+  Frag<T, DH> kf;
+  VTile<T, DH> vt;
   {
     const int k0 = (GRID ? t_cur : tile_at(0)) * 32;
     kf.load_row(K + (unsigned)min(k0 + r, p.S - 1) * ks1, h);
@@ -112,12 +113,12 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
   // ---- relative-score table T[q][col(id)] = (q.E[id] + bias[id]) * tscale  (log2 domain) --
   const int id_mode = p.pat.id_mode, mdist = p.pat.m;
   if (p.R > 0) {
-    const T* E = reinterpret_cast<const T*>(p.emb) + (long)n * 64;
+    const T* E = reinterpret_cast<const T*>(p.emb) + (long)n * DH;
 #pragma unroll
     for (int rb = 0; rb < Rp / 32; ++rb) {
       const int rr = rb * 32 + r;
-      Frag<T> ef;
-      ef.load_row(E + (long)min(rr, p.R - 1) * p.N * 64, h);   // columns >= R are never read
+      Frag<T, DH> ef;
+      ef.load_row(E + (long)min(rr, p.R - 1) * p.N * DH, h);   // columns >= R are never read
       f32x16 c = {0};
       c = mma_rows(ef, qf, c);  // [id x q]
 #pragma unroll
@@ -134,6 +135,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
   __builtin_amdgcn_wave_barrier();
 
   f32x16 o0 = {0}, o1 = {0};
+  f32x16 o2 = {0}, o3 = {0};   // DH = 128: head dims 64 .. 127
   float m_run = -INFINITY, l_run = 0.f;
   const float* trow = tab + r * kTStride(Rp);
   // whole q-block on one side of valid_len?  (needed for the fast path)
@@ -147,7 +149,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
     f32x16 c = {0};
     c = mma_rows(kf, qf, c);
 
-    VTile<T> vcur;
+    VTile<T, DH> vcur;
     if constexpr (sizeof(T) == 4) vcur = vt;
     if constexpr (GRID) t_nxt = gw.next(t_cur + 1);
     if (GRID ? t_nxt != GridWalk::kEnd : it + 1 < n_it) {   // prefetch the next tile (registers) under this tile's math
@@ -235,7 +237,10 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
       m_run = m_new;
       l_run *= alpha;
 #pragma unroll
-      for (int i = 0; i < 16; ++i) { o0[i] *= alpha; o1[i] *= alpha; }
+      for (int i = 0; i < 16; ++i) {
+        o0[i] *= alpha; o1[i] *= alpha;
+        if constexpr (DH == 128) { o2[i] *= alpha; o3[i] *= alpha; }
+      }
     }
     float psum = 0.f;
     float pr[16];
@@ -256,20 +261,29 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
     }
 
     // ---- O^T[d x q] += V^T[d x key] . P^T[key x q] -------------------------------------------
-    if constexpr (sizeof(T) == 2) mma_xt(o0, o1, vt, vlds, pr, lane);
-    else mma_xt(o0, o1, vcur, vlds, pr, lane);
+    if constexpr (DH == 128) {
+      if constexpr (sizeof(T) == 2) mma_xt(o0, o1, o2, o3, vt, vlds, pr, lane);
+      else mma_xt(o0, o1, o2, o3, vcur, vlds, pr, lane);
+    } else {
+      if constexpr (sizeof(T) == 2) mma_xt(o0, o1, vt, vlds, pr, lane);
+      else mma_xt(o0, o1, vcur, vlds, pr, lane);
+    }
   }
 
   // ---- epilogue --------------------------------------------------------------------------
   const float l_tot = half_sum(l_run);
   if (rows_item) {
-    // partial, unnormalised: part_o[bn][rowblk][chunk][q 32][d 64], part_ml[...][2][32]
+    // partial, unnormalised: part_o[bn][rowblk][chunk][q 32][d DH], part_ml[...][2][32]
     const long slot = ((long)bn * p.n_rowblk + rowblk) * p.n_chunks + chunk;
-    float* po = p.part_o + slot * (32 * 64) + r * 64;
+    float* po = p.part_o + slot * (32 * DH) + r * DH;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       *reinterpret_cast<f32x4*>(po + 8 * g + 4 * h) = f32x4{o0[4 * g], o0[4 * g + 1], o0[4 * g + 2], o0[4 * g + 3]};
       *reinterpret_cast<f32x4*>(po + 32 + 8 * g + 4 * h) = f32x4{o1[4 * g], o1[4 * g + 1], o1[4 * g + 2], o1[4 * g + 3]};
+      if constexpr (DH == 128) {
+        *reinterpret_cast<f32x4*>(po + 64 + 8 * g + 4 * h) = f32x4{o2[4 * g], o2[4 * g + 1], o2[4 * g + 2], o2[4 * g + 3]};
+        *reinterpret_cast<f32x4*>(po + 96 + 8 * g + 4 * h) = f32x4{o3[4 * g], o3[4 * g + 1], o3[4 * g + 2], o3[4 * g + 3]};
+      }
     }
     if (h == 0) {
       p.part_ml[slot * 64 + r] = m_run;
@@ -290,20 +304,31 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
       for (int j = 0; j < 4; ++j) { a[j] = (__bf16)(o0[4 * g + j] * inv); c2[j] = (__bf16)(o1[4 * g + j] * inv); }
       *reinterpret_cast<bf16x4*>(O + d) = a;
       *reinterpret_cast<bf16x4*>(O + 32 + d) = c2;
+      if constexpr (DH == 128) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { a[j] = (__bf16)(o2[4 * g + j] * inv); c2[j] = (__bf16)(o3[4 * g + j] * inv); }
+        *reinterpret_cast<bf16x4*>(O + 64 + d) = a;
+        *reinterpret_cast<bf16x4*>(O + 96 + d) = c2;
+      }
     } else {
       *reinterpret_cast<f32x4*>(O + d) = f32x4{o0[4 * g] * inv, o0[4 * g + 1] * inv, o0[4 * g + 2] * inv, o0[4 * g + 3] * inv};
       *reinterpret_cast<f32x4*>(O + 32 + d) = f32x4{o1[4 * g] * inv, o1[4 * g + 1] * inv, o1[4 * g + 2] * inv, o1[4 * g + 3] * inv};
+      if constexpr (DH == 128) {
+        *reinterpret_cast<f32x4*>(O + 64 + d) = f32x4{o2[4 * g] * inv, o2[4 * g + 1] * inv, o2[4 * g + 2] * inv, o2[4 * g + 3] * inv};
+        *reinterpret_cast<f32x4*>(O + 96 + d) = f32x4{o3[4 * g] * inv, o3[4 * g + 1] * inv, o3[4 * g + 2] * inv, o3[4 * g + 3] * inv};
+      }
     }
   }
   if (p.lse && h == 0) p.lse[((long)b * p.N + n) * p.S + q] = (m_run + log2f(l_tot)) * kLn2;
 }
 
-// Combine the per-chunk partials of the global rows: one wave per (row, bn), lane = d.
+// Combine the per-chunk partials of the global rows: DH threads per (row, bn), thread = d (at DH = 128 each of the two
+// waves reduces the chunk statistics itself, in the same order: the same L and M).
 // The chunk statistics are fetched one chunk per LANE (one load instruction, wave reductions) and the
 // partial rows with all loads of a group of eight in flight -- a loop of dependent scalar loads made this
 // 2 KB-per-wave kernel take 10 us, one L2 latency per chunk.
-template <typename T>
-__global__ __launch_bounds__(64) void attn_rows_combine_kernel(const FwdParams p) {
+template <typename T, int DH>
+__global__ __launch_bounds__(DH) void attn_rows_combine_kernel(const FwdParams p) {
   const int bn = blockIdx.y;
   const int row = blockIdx.x;  // 0 .. ng-1
   const int d = threadIdx.x;
@@ -312,7 +337,7 @@ __global__ __launch_bounds__(64) void attn_rows_combine_kernel(const FwdParams p
   const long slot0 = ((long)bn * p.n_rowblk + rowblk) * p.n_chunks;
   float L = 0.f, acc = 0.f, M = -INFINITY;
   for (int c0 = 0; c0 < p.n_chunks; c0 += 64) {             // 64 chunks per pass (one pass in practice)
-    const int c = c0 + d;
+    const int c = c0 + (DH == 64 ? d : (d & 63));
     const bool live = c < p.n_chunks;
     const float mc = live ? p.part_ml[(slot0 + c) * 64 + rr] : -INFINITY;
     const float lc = live ? p.part_ml[(slot0 + c) * 64 + 32 + rr] : 0.f;
@@ -329,16 +354,16 @@ __global__ __launch_bounds__(64) void attn_rows_combine_kernel(const FwdParams p
     acc *= rescale;
     M = Mn;
     const int cnt = min(64, p.n_chunks - c0);
-    const float* po = p.part_o + (slot0 + c0) * (32 * 64) + rr * 64 + d;
+    const float* po = p.part_o + (slot0 + c0) * (32 * DH) + rr * DH + d;
     int i = 0;
     for (; i + 8 <= cnt; i += 8) {
       float v[8];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = po[(long)(i + u) * (32 * 64)];
+      for (int u = 0; u < 8; ++u) v[u] = po[(long)(i + u) * (32 * DH)];
 #pragma unroll
       for (int u = 0; u < 8; ++u) acc = fmaf(__shfl(wc, i + u, 64), v[u], acc);
     }
-    for (; i < cnt; ++i) acc = fmaf(__shfl(wc, i, 64), po[(long)i * (32 * 64)], acc);
+    for (; i < cnt; ++i) acc = fmaf(__shfl(wc, i, 64), po[(long)i * (32 * DH)], acc);
   }
   const int q = p.pat.g0 + row;
   T* O = reinterpret_cast<T*>(p.out) + (long)b * p.os[0] + (long)q * p.os[1] + (long)n * p.os[2];
@@ -347,43 +372,49 @@ __global__ __launch_bounds__(64) void attn_rows_combine_kernel(const FwdParams p
 }
 
 // ------------------------------------ launchers -----------------------------------------
-template <typename T, int MODE, int Rp, bool GEN, bool GRID>
+template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH>
 static hipError_t launch_one(const FwdParams& p, dim3 grid, hipStream_t st) {
-  const int lds = 4 * WaveLds<T, Rp>::kBytes;
-  if (lds > 64 * 1024)               // (the 128-wide table: relative vocabularies of 65..128 ids)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<T, MODE, Rp, GEN, GRID>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  hipLaunchKernelGGL((attn_fwd_kernel<T, MODE, Rp, GEN, GRID>), grid, dim3(256), lds, st, p);
+  const int lds = 4 * WaveLds<T, Rp, DH>::kBytes;
+  if (lds > 64 * 1024)               // (the 128-wide table: relative vocabularies of 65..128 ids; DH = 128 from Rp = 64)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<T, MODE, Rp, GEN, GRID, DH>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  hipLaunchKernelGGL((attn_fwd_kernel<T, MODE, Rp, GEN, GRID, DH>), grid, dim3(256), lds, st, p);
   return hipGetLastError();
 }
 
-template <typename T, int MODE, bool GEN, bool GRID>
+template <typename T, int MODE, bool GEN, bool GRID, int DH>
 static hipError_t launch_rp(const FwdParams& p, dim3 grid, hipStream_t st) {
-  if (p.R <= 32) return launch_one<T, MODE, 32, GEN, GRID>(p, grid, st);
-  if (p.R <= 64) return launch_one<T, MODE, 64, GEN, GRID>(p, grid, st);
-  return launch_one<T, MODE, 128, GEN, GRID>(p, grid, st);
+  if (p.R <= 32) return launch_one<T, MODE, 32, GEN, GRID, DH>(p, grid, st);
+  if (p.R <= 64) return launch_one<T, MODE, 64, GEN, GRID, DH>(p, grid, st);
+  return launch_one<T, MODE, 128, GEN, GRID, DH>(p, grid, st);
 }
 
-template <typename T>
+template <typename T, int DH>
 static hipError_t launch_t(const FwdParams& p, int mode, dim3 grid, hipStream_t st) {
-  if (mode == kDense) return launch_rp<T, kDense, true, false>(p, grid, st);
+  if (mode == kDense) return launch_rp<T, kDense, true, false, DH>(p, grid, st);
   const bool gen = !(p.pat.id_mode == 0 || p.perm_1d);
   if (p.grid.ga > 0)                 // image grid: its own instantiations (the others carry no trace of it)
-    return gen ? launch_rp<T, kBand, true, true>(p, grid, st) : launch_rp<T, kBand, false, true>(p, grid, st);
-  return gen ? launch_rp<T, kBand, true, false>(p, grid, st) : launch_rp<T, kBand, false, false>(p, grid, st);
+    return gen ? launch_rp<T, kBand, true, true, DH>(p, grid, st) : launch_rp<T, kBand, false, true, DH>(p, grid, st);
+  return gen ? launch_rp<T, kBand, true, false, DH>(p, grid, st) : launch_rp<T, kBand, false, false, DH>(p, grid, st);
 }
 
 hipError_t launch_attn_fwd(const FwdParams& p, int mode, bool bf16, hipStream_t st) {
   // band items first, then (kBand only) the global-row items of the same launch
   const int per_bn = (p.n_chunks * p.n_rowblk + 3) / 4;
   dim3 grid(p.n_band_blocks + (mode == kBand ? per_bn * p.B * p.N : 0));
-  return bf16 ? launch_t<__bf16>(p, mode, grid, st) : launch_t<float>(p, mode, grid, st);
+  if (p.D == 128) return bf16 ? launch_t<__bf16, 128>(p, mode, grid, st) : launch_t<float, 128>(p, mode, grid, st);
+  return bf16 ? launch_t<__bf16, 64>(p, mode, grid, st) : launch_t<float, 64>(p, mode, grid, st);
+}
+
+template <int DH>
+static hipError_t launch_rows_combine_dh(const FwdParams& p, bool bf16, hipStream_t st) {
+  dim3 grid(p.pat.ng, p.B * p.N);
+  if (bf16) hipLaunchKernelGGL((attn_rows_combine_kernel<__bf16, DH>), grid, dim3(DH), 0, st, p);
+  else hipLaunchKernelGGL((attn_rows_combine_kernel<float, DH>), grid, dim3(DH), 0, st, p);
+  return hipGetLastError();
 }
 
 hipError_t launch_rows_combine(const FwdParams& p, bool bf16, hipStream_t st) {
-  dim3 grid(p.pat.ng, p.B * p.N);
-  if (bf16) hipLaunchKernelGGL(attn_rows_combine_kernel<__bf16>, grid, dim3(64), 0, st, p);
-  else hipLaunchKernelGGL(attn_rows_combine_kernel<float>, grid, dim3(64), 0, st, p);
-  return hipGetLastError();
+  return p.D == 128 ? launch_rows_combine_dh<128>(p, bf16, st) : launch_rows_combine_dh<64>(p, bf16, st);
 }
 
 }  // namespace mmt

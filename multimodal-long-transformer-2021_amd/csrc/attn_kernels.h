@@ -47,6 +47,7 @@ struct FwdParams {
   long long* dbg;     // -DMMT_STAMP diagnostic builds only: in-kernel s_memtime stamps (never set in the product)
   int dbg_mode, dbg_sleep;   // -DMMT_STAMP builds only: ablations (1 = no tile loop, 2 = no DMA), start delay of the second resident round
   GridDev grid;       // image-grid term (general kernels only; last, so that no other field moves)
+  int D;              // head size (64 | 128): the launchers' choice of instantiation; 128 runs the general kernels only
 };
 
 hipError_t launch_attn_fwd(const FwdParams& p, int mode, bool bf16, hipStream_t st);
@@ -68,7 +69,7 @@ struct BwdParams {
   const int32_t *att_mask, *rel_ids;
   const int32_t* valid_len;
   void *dq, *dk, *dv;
-  float *drel_emb, *drel_bias;        // outputs [R,N,64], [R,N] fp32
+  float *drel_emb, *drel_bias;        // outputs [R,N,D], [R,N] fp32
   int drel_accum;                     // != 0: add to them instead of overwriting
   int red_per_plane, red_live;        // dE partials per (b,n) plane in part_red: slots, and how many of them are written
   int dstride;                        // lean dQ kernel: row stride (floats) of the per-wave dRel table in LDS
@@ -85,14 +86,15 @@ struct BwdParams {
   uint32_t drop_thresh, seed_lo, seed_hi;
   const unsigned long long* epoch;      // as FwdParams
   float inv_keep;
+  int D;             // head size (64 | 128), as FwdParams (in the padding in front of `delta`: no field moves)
   // workspace
   float* delta;      // [B,N,S]       rowsum(dO * O)
   float* relfar;     // [B,N,S,2]     clipped-id relative scores of each row (log2 domain), lean path
   float* drel;       // [B*N, n_global, Rp]  d(relall) rows of the global tokens, id order
-  float* part_dq;    // [B*N, n_gblk, n_chunks, 32, 64]   global-row partials
+  float* part_dq;    // [B*N, n_gblk, n_chunks, 32, D]   global-row partials
   float* part_dtab;  // [B*N, n_gblk, n_chunks, 32, Rp]
-  float* part_dkv;   // [B*N, n_gblk, dkv_slots, 2, 32, 64] global-key partials
-  float* part_red;   // [B*N * ceil(S/128) * 4 waves, Rp*64 + Rp]  per-wave dE^T / dbias partials
+  float* part_dkv;   // [B*N, n_gblk, dkv_slots, 2, 32, D] global-key partials
+  float* part_red;   // [B*N * ceil(S/128) * 4 waves, Rp*D + Rp]  per-wave dE^T / dbias partials
   int n_band_blocks, n_chunks, chunk_tiles, n_gblk, n_split;
   int peel_gkeys;       // bit 0, dQ pass: the (<= 8) global keys outside a wave's band tiles as a peeled quarter-tile step; bit 1, dK/dV pass: the global query rows likewise
   // P hand-over (lean bf16 path, attn_bwd_band.hip): the dQ pass stores every tile's probabilities as bf16 (sign bit =

@@ -1,10 +1,13 @@
 // Tile-level building blocks shared by the forward and backward attention kernels (gfx950).
 #pragma once
+#include <type_traits>
+
 #include "attn_kernels.h"
 
 namespace mmt {
 
-template <typename T> struct Frag;
+// DH = head size (64 | 128).  Every DH = 64 form below is the code the lean kernels were written against.
+template <typename T, int DH = 64> struct Frag;
 
 // Tile walk of a 32-row block at x0 under a pattern with the image-grid term (grid.ga > 0): the ascending union of
 //   the band's tiles, the global tokens' tiles, and, for each image-row offset dr in [-a, a], the tiles of
@@ -49,42 +52,44 @@ struct GridWalk {
 };
 
 // ------------------------------- bf16: 32x32x16 MFMA ---------------------------------
-// MFMA k-index (8h + j) of step s is mapped to head-dim d = 32h + 8s + j, so each lane
-// loads 64 contiguous bytes of its row (4 x 16 B).
-template <> struct Frag<__bf16> {
-  bf16x8 v[4];
+// MFMA k-index (8h + j) of step s is mapped to head-dim d = (DH/2)h + 8s + j, so each lane
+// loads DH contiguous bytes of its row (DH/16 x 16 B).
+template <int DH> struct Frag<__bf16, DH> {
+  bf16x8 v[DH / 16];
   __device__ __forceinline__ void load_row(const __bf16* row, int h) {
 #pragma unroll
-    for (int s = 0; s < 4; ++s) v[s] = *reinterpret_cast<const bf16x8*>(row + 32 * h + 8 * s);
+    for (int s = 0; s < DH / 16; ++s) v[s] = *reinterpret_cast<const bf16x8*>(row + (DH / 2) * h + 8 * s);
   }
 };
-__device__ __forceinline__ f32x16 mma_rows(const Frag<__bf16>& a, const Frag<__bf16>& b, f32x16 c) {
+template <int DH>
+__device__ __forceinline__ f32x16 mma_rows(const Frag<__bf16, DH>& a, const Frag<__bf16, DH>& b, f32x16 c) {
 #pragma unroll
-  for (int s = 0; s < 4; ++s) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v[s], b.v[s], c, 0, 0, 0);
+  for (int s = 0; s < DH / 16; ++s) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v[s], b.v[s], c, 0, 0, 0);
   return c;
 }
 
 // ------------------------------- f32: 32x32x2 MFMA (exact f32) -----------------------
-// MFMA k-index h of step s is mapped to d = 32h + s: each lane loads 128 contiguous bytes.
-template <> struct Frag<float> {
-  float v[32];
+// MFMA k-index h of step s is mapped to d = (DH/2)h + s: each lane loads 2 DH contiguous bytes.
+template <int DH> struct Frag<float, DH> {
+  float v[DH / 2];
   __device__ __forceinline__ void load_row(const float* row, int h) {
 #pragma unroll
-    for (int s = 0; s < 32; s += 4) {
-      f32x4 t = *reinterpret_cast<const f32x4*>(row + 32 * h + s);
+    for (int s = 0; s < DH / 2; s += 4) {
+      f32x4 t = *reinterpret_cast<const f32x4*>(row + (DH / 2) * h + s);
       v[s] = t[0]; v[s + 1] = t[1]; v[s + 2] = t[2]; v[s + 3] = t[3];
     }
   }
 };
-__device__ __forceinline__ f32x16 mma_rows(const Frag<float>& a, const Frag<float>& b, f32x16 c) {
+template <int DH>
+__device__ __forceinline__ f32x16 mma_rows(const Frag<float, DH>& a, const Frag<float, DH>& b, f32x16 c) {
 #pragma unroll
-  for (int s = 0; s < 32; ++s) c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.v[s], b.v[s], c, 0, 0, 0);
+  for (int s = 0; s < DH / 2; ++s) c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.v[s], b.v[s], c, 0, 0, 0);
   return c;
 }
 
 // V rows of one tile held in registers between the global load and their use.
-template <typename T> struct VTile;
-template <> struct VTile<__bf16> {   // 4 x 16-B chunks per lane -> written to the LDS tile
+template <typename T, int DH = 64> struct VTile;
+template <> struct VTile<__bf16, 64> {   // 4 x 16-B chunks per lane -> written to the LDS tile
   bf16x8 c[4];
   __device__ __forceinline__ void load(const __bf16* V, unsigned vs1, int k0, int S, int lane, int) {
 #pragma unroll
@@ -105,7 +110,7 @@ template <> struct VTile<__bf16> {   // 4 x 16-B chunks per lane -> written to t
     }
   }
 };
-template <> struct VTile<float> {    // A operand of the 32x32x2 PV product, straight from L2
+template <> struct VTile<float, 64> {    // A operand of the 32x32x2 PV product, straight from L2
   float a0[16], a1[16];
   __device__ __forceinline__ void load(const float* V, unsigned vs1, int k0, int S, int lane, int) {
     const int r = lane & 31, h = lane >> 5;
@@ -119,6 +124,62 @@ template <> struct VTile<float> {    // A operand of the 32x32x2 PV product, str
   __device__ __forceinline__ void to_lds(unsigned char*, int) const {}
 };
 
+// DH = 128, bf16: 32 rows x 256 B.  A 256-B row spans all 64 banks, so the 128-B rows' half swap cannot work; the
+// 16-B slot c of row r is stored at slot c ^ g(r), g(r) = 4 (r & 3) + ((r >> 2) & 3).  Bank pattern:
+//  - ds_read_b64_tr_b16 (mma_xt): a 32-lane half reads rows 4i .. 4i+3, the same 64-B d-block db of each; the block of
+//    row 4i + j lands in quarter db ^ j and its four slots are permuted by the constant i & 3 -- four quarters x four
+//    slots x two 8-B halves = all 64 banks once: conflict-free;
+//  - ds_read_b128 (frag_from_tile, one slot per lane): the rows of a 16-lane group, {0-3, 12-15, 20-27} or
+//    {4-11, 16-19, 28-31}, have 16 distinct g(r): 16 distinct slots = 64 banks, conflict-free;
+//  - ds_write_b128 (to_lds, bank = (a/4) mod 32): 8 consecutive lanes write slots c .. c+7 of one row, still distinct
+//    mod 8 after the XOR: conflict-free.
+__device__ __forceinline__ int swz256(int row, int slot) {
+  return row * 256 + ((slot ^ (((row & 3) << 2) | ((row >> 2) & 3))) << 4);
+}
+template <> struct VTile<__bf16, 128> {   // 8 x 16-B chunks per lane (16 lanes per row) -> the LDS tile
+  bf16x8 c[8];
+  __device__ __forceinline__ void load(const __bf16* V, unsigned vs1, int k0, int S, int lane, int) {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int ci = lane + 64 * u, row = ci >> 4, ch = ci & 15;
+      const unsigned kk = (unsigned)min(k0 + row, S - 1);  // rows past the end repeat the last row; their p is 0
+      c[u] = *reinterpret_cast<const bf16x8*>(V + (kk * vs1 + (unsigned)ch * 8u));
+    }
+  }
+  __device__ __forceinline__ void to_lds(unsigned char* vlds, int lane) const {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int ci = lane + 64 * u, row = ci >> 4, ch = ci & 15;
+      *reinterpret_cast<bf16x8*>(vlds + swz256(row, ch)) = c[u];
+    }
+  }
+};
+template <> struct VTile<float, 128> {   // A operand of the 32x32x2 products, four 32-column blocks
+  float a[4][16];
+  __device__ __forceinline__ void load(const float* V, unsigned vs1, int k0, int S, int lane, int) {
+    const int r = lane & 31, h = lane >> 5;
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+      const unsigned kk = (unsigned)min(k0 + kap(s, h), S - 1);
+      const float* vr = V + kk * vs1;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) a[j][s] = vr[32 * j + r];
+    }
+  }
+  __device__ __forceinline__ void to_lds(unsigned char*, int) const {}
+};
+// DH = 128, bf16, staged through a 32 x 128 B buffer: the two 64-column halves as DH = 64 tiles, written to the LDS
+// one after the other by the product itself (mma_xt below).  For the dQ pass at Rp = 128, whose four waves' full
+// 256-B tiles would pass the CU's 160 KiB (BwdLds).
+struct HalfTile {
+  VTile<__bf16, 64> lo, hi;
+  __device__ __forceinline__ void load(const __bf16* V, unsigned vs1, int k0, int S, int lane, int) {
+    lo.load(V, vs1, k0, S, lane, 0);
+    hi.load(V + 64, vs1, k0, S, lane, 0);
+  }
+  __device__ __forceinline__ void to_lds(unsigned char*, int) const {}
+};
+
 // Row fragment (MFMA A/B operand, row = lane & 31) read back from a wave-private LDS tile that
 // was written with VTile<__bf16>::to_lds: saves the second, fragment-shaped global load.
 __device__ __forceinline__ void frag_from_tile(Frag<__bf16>& f, const unsigned char* lds, int lane) {
@@ -126,6 +187,12 @@ __device__ __forceinline__ void frag_from_tile(Frag<__bf16>& f, const unsigned c
   const unsigned char* row = lds + r * 128 + ((h ^ ((r >> 1) & 1)) << 6);
 #pragma unroll
   for (int s = 0; s < 4; ++s) f.v[s] = *reinterpret_cast<const bf16x8*>(row + s * 16);
+}
+
+__device__ __forceinline__ void frag_from_tile(Frag<__bf16, 128>& f, const unsigned char* lds, int lane) {
+  const int r = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int s = 0; s < 8; ++s) f.v[s] = *reinterpret_cast<const bf16x8*>(lds + swz256(r, 8 * h + s));
 }
 
 __device__ __forceinline__ float half_xchg(float x) { return __shfl_xor(x, 32, 64); }
@@ -146,11 +213,11 @@ __device__ __forceinline__ float half_sum(float x) { float a, b; half_pair(x, a,
 constexpr int kTStride(int Rp) { return Rp + 2; }
 constexpr float kRescaleThr = 6.0f;
 
-// LDS carve per wave: T table [32][kTStride] f32, then (bf16 only) V tile 32 x 128 B.
-template <typename T, int Rp> struct WaveLds {
+// LDS carve per wave: T table [32][kTStride] f32, then (bf16 only) V tile 32 x 2 DH B.
+template <typename T, int Rp, int DH = 64> struct WaveLds {
   static constexpr int kTBytes = 32 * kTStride(Rp) * 4;
   static constexpr int kTBytesAligned = (kTBytes + 15) & ~15;
-  static constexpr int kVBytes = sizeof(T) == 2 ? 32 * 128 : 0;
+  static constexpr int kVBytes = sizeof(T) == 2 ? 32 * 2 * DH : 0;
   static constexpr int kBytes = kTBytesAligned + kVBytes;
 };
 
@@ -231,6 +298,64 @@ __device__ __forceinline__ void mma_xt_hilo(f32x16& a0, f32x16& a1, const VTile<
 __device__ __forceinline__ void mma_xt_hilo(f32x16& a0, f32x16& a1, const VTile<float>& x,
                                             const unsigned char* xlds, const float (&vals)[16], int lane) {
   mma_xt(a0, a1, x, xlds, vals, lane);
+}
+
+// DH = 128: the products into four accumulators a0 .. a3 (head dims 32j .. 32j+31 in a_j).
+// bf16: as the DH = 64 form, four d-blocks (64-B quarters of the 256-B rows, swz256) per key step.
+__device__ __forceinline__ void mma_xt(f32x16& a0, f32x16& a1, f32x16& a2, f32x16& a3, const VTile<__bf16, 128>&,
+                                       const unsigned char* xlds, const float (&vals)[16], int lane) {
+  const int h = lane >> 5, li = lane & 15, cb = (lane >> 4) & 1;
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    const bf16x8 pf = pack8_bf16(vals + 8 * s);
+#pragma unroll
+    for (int db = 0; db < 4; ++db) {
+      const int row = 16 * s + 4 * h + (li >> 2);
+      const int slot = 4 * db + 2 * cb + ((li & 3) >> 1), byte = 8 * (li & 1);   // 8 B at 32 cb + 8 (li & 3) of the block
+      s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+          (__attribute__((address_space(3))) s16x4*)(xlds + swz256(row, slot) + byte));
+      s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+          (__attribute__((address_space(3))) s16x4*)(xlds + swz256(row + 8, slot) + byte));
+      bf16x8 vf;
+      bf16x4 lo4 = __builtin_bit_cast(bf16x4, lo), hi4 = __builtin_bit_cast(bf16x4, hi);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { vf[j] = lo4[j]; vf[4 + j] = hi4[j]; }
+      f32x16& a = db == 0 ? a0 : (db == 1 ? a1 : (db == 2 ? a2 : a3));
+      a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, a, 0, 0, 0);
+    }
+  }
+}
+__device__ __forceinline__ void mma_xt(f32x16& a0, f32x16& a1, f32x16& a2, f32x16& a3, const VTile<float, 128>& x,
+                                       const unsigned char*, const float (&vals)[16], int) {
+#pragma unroll
+  for (int s = 0; s < 16; ++s) {
+    a0 = __builtin_amdgcn_mfma_f32_32x32x2f32(x.a[0][s], vals[s], a0, 0, 0, 0);
+    a1 = __builtin_amdgcn_mfma_f32_32x32x2f32(x.a[1][s], vals[s], a1, 0, 0, 0);
+    a2 = __builtin_amdgcn_mfma_f32_32x32x2f32(x.a[2][s], vals[s], a2, 0, 0, 0);
+    a3 = __builtin_amdgcn_mfma_f32_32x32x2f32(x.a[3][s], vals[s], a3, 0, 0, 0);
+  }
+}
+// HalfTile: each half written to the 32 x 128 B buffer right before its product (LDS accesses of one wave complete in
+// order: the high half's stores follow the low half's reads)
+__device__ __forceinline__ void mma_xt(f32x16& a0, f32x16& a1, f32x16& a2, f32x16& a3, const HalfTile& x,
+                                       unsigned char* xlds, const float (&vals)[16], int lane) {
+  x.lo.to_lds(xlds, lane);
+  mma_xt(a0, a1, x.lo, xlds, vals, lane);
+  x.hi.to_lds(xlds, lane);
+  mma_xt(a2, a3, x.hi, xlds, vals, lane);
+}
+template <typename X>
+__device__ __forceinline__ void mma_xt_hilo(f32x16& a0, f32x16& a1, f32x16& a2, f32x16& a3, const X& x,
+                                            unsigned char* xlds, const float (&vals)[16], int lane) {
+  if constexpr (std::is_same<X, VTile<float, 128>>::value) {
+    mma_xt(a0, a1, a2, a3, x, xlds, vals, lane);
+  } else {
+    float hi[16], lo[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { hi[i] = (float)(__bf16)vals[i]; lo[i] = vals[i] - hi[i]; }
+    mma_xt(a0, a1, a2, a3, x, xlds, hi, lane);
+    mma_xt(a0, a1, a2, a3, x, xlds, lo, lane);
+  }
 }
 
 }  // namespace mmt

@@ -48,7 +48,7 @@ struct Plan {
 // P / dS hand-over between the two backward passes (lean bf16 kernels, 1-D or no relative ids): shapes it is built for.
 // The global tokens, if any, must be the peeled kind (<= 8, contiguous); the band at most 8 tiles wide.
 int handover_slots(const mmt_attn_desc* d, bool dense) {
-  if (dense || d->dtype != MMT_BF16 || (d->mask.image_grid & 0xFF)) return 0;     // (an image grid: the general kernels)
+  if (dense || d->dtype != MMT_BF16 || (d->mask.image_grid & 0xFF) || d->D != 64) return 0;     // (an image grid, head size 128: the general kernels)
   if (d->mask.global_index || d->mask.n_global > 8) return 0;
   const int W = d->mask.local_radius > d->S ? d->S : d->mask.local_radius;
   const int slots = 2 * ((W + 31) / 32) + 1;
@@ -75,7 +75,7 @@ int check_grid(const mmt_mask_desc& m, int S) {
 int check_desc(const mmt_attn_desc* d) {
   if (!d) return fail(MMT_E_INVALID, "desc is NULL");
   if (d->B <= 0 || d->S <= 0 || d->N <= 0) return fail(MMT_E_INVALID, "B,S,N must be positive");
-  if (d->D != 64) return fail(MMT_E_UNSUPPORTED, "D=%d: only head size 64 is built", d->D);
+  if (d->D != 64 && d->D != 128) return fail(MMT_E_UNSUPPORTED, "D=%d: head size 64 or 128 is built", d->D);
   if (d->R < 0 || d->R > 128) return fail(MMT_E_UNSUPPORTED, "R=%d: relative vocab must be in [0,128]", d->R);
   if (d->dtype != MMT_F32 && d->dtype != MMT_BF16) return fail(MMT_E_INVALID, "bad dtype %d", d->dtype);
   const int64_t* st[4] = {d->q_stride, d->k_stride, d->v_stride, d->o_stride};
@@ -129,10 +129,12 @@ Plan make_plan(const mmt_attn_desc* d, bool dense) {
   pl.split_rows = !dense && d->mask.n_global > 0 && d->mask.local_radius < d->S;
   pl.n_rowblk = pl.split_rows ? (d->mask.n_global + 31) / 32 : 0;
   pl.n_chunks = pl.split_rows ? (n_tiles + kChunkTiles - 1) / kChunkTiles : 0;
-  pl.fwd_ws = (size_t)d->B * d->N * pl.n_rowblk * pl.n_chunks * (32 * 64 + 64) * sizeof(float);
-  if (pl.split_rows && d->mask.n_global <= 16)     // window kernel: the row groups' parts (<= 2 groups x 4 parts of 8 x 66 floats per plane)
+  // head size 128 runs the general kernels only: none of the window / plane-walk / sliding-window workspace below
+  const bool d64 = d->D == 64;
+  pl.fwd_ws = (size_t)d->B * d->N * pl.n_rowblk * pl.n_chunks * (32 * d->D + 64) * sizeof(float);
+  if (d64 && pl.split_rows && d->mask.n_global <= 16)     // window kernel: the row groups' parts (<= 2 groups x 4 parts of 8 x 66 floats per plane)
     pl.fwd_ws = std::max(pl.fwd_ws, (size_t)d->B * d->N * 2 * 4 * 8 * 66 * sizeof(float));
-  if (pl.split_rows && d->mask.n_global <= 8) {    // plane-walk / sliding-window kernels: partials of the global rows per run
+  if (d64 && pl.split_rows && d->mask.n_global <= 8) {    // plane-walk / sliding-window kernels: partials of the global rows per run
     pl.fwd_ws = std::max(pl.fwd_ws, mmt::fwd_walk_workspace_bytes(d->B, d->N, d->S));
     pl.fwd_ws = std::max(pl.fwd_ws, mmt::fwd_pwin_workspace_bytes(d->B, d->N, d->S, 2 * 256));
   }
@@ -143,10 +145,11 @@ Plan make_plan(const mmt_attn_desc* d, bool dense) {
   pl.off_relfar = pl.off_delta + bn * d->S;
   pl.off_drel = pl.off_relfar + bn * d->S * 2;
   pl.off_pdq = pl.off_drel + bn * (size_t)d->mask.n_global * Rp;
-  pl.off_pdtab = pl.off_pdq + bn * pl.n_rowblk * pl.n_chunks * (32 * 64);
+  const size_t D = (size_t)d->D;
+  pl.off_pdtab = pl.off_pdq + bn * pl.n_rowblk * pl.n_chunks * (32 * D);
   pl.off_pdkv = pl.off_pdtab + bn * pl.n_rowblk * pl.n_chunks * (32 * Rp);
-  pl.off_red = pl.off_pdkv + bn * pl.n_rowblk * (pl.n_chunks + 1) * (2 * 32 * 64);      // (+ 1: the hand-over's band slot)
-  pl.off_ho = (pl.off_red + bn * ((d->S + 127) / 128) * 4 * (Rp * 64 + Rp) + 3) & ~(size_t)3;
+  pl.off_red = pl.off_pdkv + bn * pl.n_rowblk * (pl.n_chunks + (d64 ? 1 : 0)) * (2 * 32 * D);      // (+ 1: the hand-over's band slot)
+  pl.off_ho = (pl.off_red + bn * ((d->S + 127) / 128) * 4 * (Rp * D + Rp) + 3) & ~(size_t)3;
   pl.ho_slots = handover_slots(d, dense);
   const size_t ho_bytes = pl.ho_slots ? bn * n_tiles * ((size_t)pl.ho_slots * 2048 + 1024) : 0;
   pl.bwd_ws = pl.off_ho * sizeof(float) + ho_bytes;
@@ -158,8 +161,8 @@ Plan make_plan(const mmt_attn_desc* d, bool dense) {
 // below R (small images: P = 4, m = 3 gives 31 / 32 against R = 49); never more than R (ids >= R contribute 0 under
 // the one-hot lookup).  0 = not eligible (the general kernels of attn_fwd.hip / attn_bwd.hip take
 // the call).
-int lean2d_width(const mmt::PatternDev& pat, const mmt::GridDev& grid, int R, bool dense) {
-  if (dense || pat.id_mode != MMT_IDS_2D || R <= 0 || grid.ga > 0) return 0;
+int lean2d_width(const mmt::PatternDev& pat, const mmt::GridDev& grid, int R, int D, bool dense) {
+  if (dense || pat.id_mode != MMT_IDS_2D || R <= 0 || grid.ga > 0 || D != 64) return 0;
   const int d = 2 * pat.r + 1, n2 = d + 2;
   if (n2 * n2 > 256) return 0;                       // look-up table of the clamped (dx, dy) grid
   int need = std::max(d * d + 8, 2 * pat.m + 1);
@@ -171,7 +174,7 @@ int lean2d_width(const mmt::PatternDev& pat, const mmt::GridDev& grid, int R, bo
 void fill_common(mmt::FwdParams& p, const mmt_attn_desc* d) {
   std::memset(&p, 0, sizeof(p));
   p.rows_parts = 1;
-  p.B = d->B; p.S = d->S; p.N = d->N; p.R = d->R;
+  p.B = d->B; p.S = d->S; p.N = d->N; p.R = d->R; p.D = d->D;
   for (int i = 0; i < 3; ++i) {
     p.qs[i] = d->q_stride[i]; p.ks[i] = d->k_stride[i];
     p.vs[i] = d->v_stride[i]; p.os[i] = d->o_stride[i];
@@ -249,12 +252,12 @@ int mmt_attn_fwd(const mmt_attn_desc* desc, const void* q, const void* k, const 
   if (pl.split_rows) {
     p.n_rowblk = pl.n_rowblk; p.n_chunks = pl.n_chunks; p.chunk_tiles = kChunkTiles;
     p.part_o = reinterpret_cast<float*>(workspace);
-    p.part_ml = p.part_o + (size_t)desc->B * desc->N * pl.n_rowblk * pl.n_chunks * (32 * 64);
+    p.part_ml = p.part_o + (size_t)desc->B * desc->N * pl.n_rowblk * pl.n_chunks * (32 * desc->D);
   }
-  p.lean_rp = lean2d_width(p.pat, p.grid, desc->R, dense);
-  // an image grid (p.grid.ga > 0) is served by the general kernels only (attn_fwd.hip): every lean / window / walk kernel
-  // below needs `lean`, so no tuning switch can route a grid pattern past its grid term
-  const bool lean = bf16 && p.grid.ga == 0 && (p.pat.id_mode == 0 || (p.perm_1d && desc->R <= 64) || p.lean_rp);   // attn_fwd_band.hip (tables up to 64 wide)
+  p.lean_rp = lean2d_width(p.pat, p.grid, desc->R, desc->D, dense);
+  // an image grid (p.grid.ga > 0) and head size 128 are served by the general kernels only (attn_fwd.hip): every lean /
+  // window / walk kernel below needs `lean`, so no tuning switch can route them past it
+  const bool lean = bf16 && p.grid.ga == 0 && desc->D == 64 && (p.pat.id_mode == 0 || (p.perm_1d && desc->R <= 64) || p.lean_rp);   // attn_fwd_band.hip (tables up to 64 wide)
   p.part_scale = (lean && p.drop_thresh) ? p.inv_keep : 1.f;
   // window kernel (attn_fwd_win.hip): K / V staged once per workgroup, global keys as a peeled quarter-tile step,
   // rows of up to 16 global tokens by flipped-orientation workgroups of the same launch (no workspace, no combine
@@ -372,7 +375,7 @@ int mmt_attn_bwd(const mmt_attn_desc* desc, const void* q, const void* k, const 
   p.q = q; p.k = k; p.v = v; p.emb = rel_emb; p.bias = rel_bias; p.out = out; p.dout = dout; p.lse = lse;
   p.att_mask = att_mask; p.rel_ids = rel_ids; p.valid_len = f.valid_len;
   p.dq = dq; p.dk = dk; p.dv = dv; p.drel_emb = drel_emb; p.drel_bias = rel_bias ? drel_bias : nullptr;
-  p.B = f.B; p.S = f.S; p.N = f.N; p.R = f.R; p.Rp = desc->R <= 32 ? 32 : (desc->R <= 64 ? 64 : 128);
+  p.B = f.B; p.S = f.S; p.N = f.N; p.R = f.R; p.D = f.D; p.Rp = desc->R <= 32 ? 32 : (desc->R <= 64 ? 64 : 128);
   for (int i = 0; i < 3; ++i) { p.qs[i] = f.qs[i]; p.ks[i] = f.ks[i]; p.vs[i] = f.vs[i]; p.os[i] = f.os[i]; }
   p.sscale = f.sscale; p.tscale = f.tscale; p.mask_add = f.mask_add;
   p.gscale = desc->scale;
@@ -384,7 +387,7 @@ int mmt_attn_bwd(const mmt_attn_desc* desc, const void* q, const void* k, const 
   p.perm_1d = (!dense && p.pat.id_mode == MMT_IDS_1D && desc->R >= 2 * p.pat.m + 1) ? 1 : 0;
   p.drop_thresh = f.drop_thresh; p.seed_lo = f.seed_lo; p.seed_hi = f.seed_hi; p.inv_keep = f.inv_keep; p.epoch = f.epoch;
   if (desc->dtype == MMT_BF16) {
-    if (const int w2 = lean2d_width(p.pat, p.grid, desc->R, dense)) {      // lean 2-D path: the kernels run at the narrowed table width
+    if (const int w2 = lean2d_width(p.pat, p.grid, desc->R, desc->D, dense)) {      // lean 2-D path: the kernels run at the narrowed table width
       p.lean2d = 1;
       p.Rp = w2;
     }
@@ -400,7 +403,7 @@ int mmt_attn_bwd(const mmt_attn_desc* desc, const void* q, const void* k, const 
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (p.lean2d && p.R > p.Rp && !p.drel_accum) {
     // ids in [Rp, R) cannot occur (lean2d_width): their gradient rows are zero, and the dE reduce covers ids < Rp only
-    (void)hipMemsetAsync(drel_emb + (size_t)p.Rp * p.N * 64, 0, (size_t)(p.R - p.Rp) * p.N * 64 * sizeof(float), st);
+    (void)hipMemsetAsync(drel_emb + (size_t)p.Rp * p.N * p.D, 0, (size_t)(p.R - p.Rp) * p.N * p.D * sizeof(float), st);
     if (p.drel_bias) (void)hipMemsetAsync(p.drel_bias + (size_t)p.Rp * p.N, 0, (size_t)(p.R - p.Rp) * p.N * sizeof(float), st);
   }
   p.dq_plane_major = (desc->tuning & MMT_TUNE_BWD_DQ_PLANE_MAJOR) ? 1 : 0;
@@ -408,13 +411,13 @@ int mmt_attn_bwd(const mmt_attn_desc* desc, const void* q, const void* k, const 
   // peeled global keys need clipped relative ids only: every peeled key lies beyond the radius, hence beyond max_dist
   p.peel_gkeys = (!dense && pl.split_rows && p.pat.ng <= 8 && (p.pat.id_mode == 0 || (p.perm_1d && p.pat.radius >= p.pat.m))) ? 3 : 0;
   if (!dense && pl.split_rows && p.pat.ng <= 8 && p.lean2d) p.peel_gkeys = 1;      // 2-D ids: the dQ pass's peeled step looks its columns up (the recomputing dK/dV pass keeps its tile visit)
-  if (p.grid.ga > 0) p.peel_gkeys = 0;                                   // an image grid: the general kernels, no peeled steps
+  if (p.grid.ga > 0 || p.D != 64) p.peel_gkeys = 0;                     // an image grid, head size 128: the general kernels, no peeled steps
   if (desc->tuning & MMT_TUNE_BWD_NO_PEEL_DQ) p.peel_gkeys &= ~1;       // bit 0: dQ pass, bit 1: dK/dV pass
   if (desc->tuning & MMT_TUNE_BWD_NO_PEEL_DKV) p.peel_gkeys &= ~2;
   p.dkv_slots = p.n_chunks;
   {   // P / dS hand-over: the dK/dV pass reads what the dQ pass computed (needs the peeled kind of global tokens, if any)
     const bool on = !(desc->tuning & MMT_TUNE_BWD_NO_HANDOVER);
-    const bool lean = desc->dtype == MMT_BF16 && !dense && p.grid.ga == 0 && (p.pat.id_mode == 0 || (p.perm_1d && p.Rp <= 64) || p.lean2d);
+    const bool lean = desc->dtype == MMT_BF16 && !dense && p.grid.ga == 0 && p.D == 64 && (p.pat.id_mode == 0 || (p.perm_1d && p.Rp <= 64) || p.lean2d);
     if (on && lean && pl.ho_slots > 0 && (p.pat.ng == 0 || !pl.split_rows || (p.peel_gkeys & 1))) {
       p.ho = reinterpret_cast<unsigned char*>(ws + pl.off_ho);
       p.ho_slots = pl.ho_slots;

@@ -45,6 +45,8 @@ def make_train_step_bench(cfg: dict, device, rank: int, world: int, dtype=torch.
                          'relative_att_num_core_layers': cfg.get('core', 0),     # > 0: 2-D ids (*_2d*.yaml)
                          'num_global_tokens': cfg['ng']},
       }})
+  if cfg.get('D', 64) != 64:    # another head size: hidden size H over N heads (the BASELINE configurations keep the defaults)
+    exp.override({'task': {'model': {'encoder': {'mmt': {'hidden_size': cfg['H'], 'num_attention_heads': cfg['N']}}}}})
   strategy = distribute.DataParallelStrategy(torch.distributed.get_backend() if _exchanging(world) else None)
   task = tasks.PretrainingTask(exp.task, compute_dtype=dtype, num_replicas=world)
   torch.manual_seed(0)

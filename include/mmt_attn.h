@@ -55,6 +55,13 @@ enum {
 /* flags */
 #define MMT_FLAG_SCALE_BEFORE_ADD 1u /* s = content*scale + rel  (default: (content+rel)*scale) */
 #define MMT_FLAG_ACCUM_REL_GRADS 2u  /* backward: drel_emb / drel_bias += (fp32 master gradients) instead of = */
+#define MMT_FLAG_EXAMPLE_IDS 4u      /* packed examples: mask.valid_len names int32 [B,S] EXAMPLE IDS on the device instead of [B]
+                                        lengths, and segmented(q,k) = ids[b,q] == ids[b,k] -- the reference's
+                                        make_segmented_att_mask over cumsum(long_breakpoints, reverse) (data_utils.py:305-332);
+                                        any ids, no contiguity needed.  Structured calls only (with a dense att_mask the flag is
+                                        ignored like the rest of desc->mask); the general kernels; refused with an image grid (it
+                                        names one image per row) and, as ever, with a listed global set.  Relative ids are
+                                        untouched: they do not depend on the mask.  ids = 1 on [0, vl), 0 after, is valid_len = vl. */
 
 /* Kernel-selection switches (mmt_attn_desc.tuning; ABI 4).  0 = the library's defaults.  They choose between kernels
  * that compute the same result (parity tests flip them to reach every kernel; they replace the MMT_* environment
@@ -72,7 +79,8 @@ enum {
 
 /* Attention pattern + id generator.  With local_radius >= S, n_global == 0 and no image grid the
  * pattern is exactly the reference's segmented mask (data_utils.py:321-322):
- *   mask(q,k) = (q < valid_len[b]) == (k < valid_len[b])
+ *   mask(q,k) = segmented(q,k) = (q < valid_len[b]) == (k < valid_len[b]),
+ *   or, with MMT_FLAG_EXAMPLE_IDS in mmt_attn_desc.flags (packed examples): example_ids[b,q] == example_ids[b,k]
  * otherwise (build-defined):
  *   mask(q,k) = segmented(q,k) && (|q-k| <= local_radius || global(q) || global(k) || grid(q,k)),
  *   global(x) = global_start <= x < global_start + n_global, or -- with global_index --
@@ -86,7 +94,8 @@ enum {
 #define MMT_IMAGE_GRID(a, g) ((int32_t)(((uint32_t)(a) & 0xFFu) | (((uint32_t)(g) & 0x7FFFFFu) << 8)))
 typedef struct mmt_mask_desc {
   const int32_t* valid_len; /* [B] device ints (num_image_wordpieces + num_text_wordpieces),
-                               NULL = every position valid                            */
+                               NULL = every position valid.  With MMT_FLAG_EXAMPLE_IDS: the
+                               [B,S] device ints of example ids instead (must not be NULL) */
   int32_t local_radius;     /* >= 0; values >= S mean "no band restriction"          */
   int32_t global_start;
   int32_t n_global;         /* contiguous range of global tokens; 0 = none           */

@@ -11,6 +11,7 @@ extern const unsigned char* g_ws_lo;
 extern const unsigned char* g_ws_hi;
 extern int g_launches, g_last_kind, g_last_handover;
 extern const void* g_last_epoch;
+extern int g_last_pack;
 
 #define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "asan driver: %s:%d: %s (last error: %s)\n", __FILE__, __LINE__, #cond, mmt_last_error()); return 1; } } while (0)
 
@@ -150,6 +151,74 @@ int main(void) {
       CHECK(mmt_workspace_bytes(&d) == 0);
       CHECK(strstr(mmt_last_error(), "head size 64") != NULL);
     }
+  }
+
+  /* ---- packed examples (MMT_FLAG_EXAMPLE_IDS): mask.valid_len names [B,S] example ids; the general kernels, forward and
+   *      backward, whatever the tuning switches; exact-size workspaces; the argument errors ---- */
+  {
+    static const int shapes[][8] = {   /* B, S, N, R, n_global, dtype, 2-D ids, D */
+        {4, 4096, 12, 32, 8, MMT_BF16, 0, 64}, {2, 300, 3, 32, 0, MMT_F32, 0, 64}, {2, 1024, 2, 49, 8, MMT_BF16, 1, 64},
+        {1, 520, 1, 100, 40, MMT_BF16, 1, 128}, {1, 96, 1, 0, 0, MMT_BF16, 0, 64}, {1, 1000, 2, 32, 8, MMT_F32, 0, 128}};
+    const uint32_t tunings[] = {0u, MMT_TUNE_FWD_WALK, MMT_TUNE_FWD_PWIN, MMT_TUNE_FWD_ROWS_ONE_WG, MMT_TUNE_FWD_NO_WIN, MMT_TUNE_FWD_FORCE_WIN,
+                                MMT_TUNE_BWD_NO_HANDOVER, MMT_TUNE_BWD_HO_PER_WAVE, MMT_TUNE_BWD_NO_PEEL_DQ, MMT_TUNE_BWD_NO_PEEL_DKV,
+                                MMT_TUNE_BWD_DQ_PLANE_MAJOR};
+    for (unsigned i = 0; i < sizeof(shapes) / sizeof(shapes[0]); ++i) {
+      for (unsigned t = 0; t < sizeof(tunings) / sizeof(tunings[0]); ++t) {
+        const int* s = shapes[i];
+        d = base_desc(s[0], s[1], s[2], s[3], s[5]);
+        d.D = s[7];
+        const int64_t st[3] = {(int64_t)s[1] * s[2] * s[7], (int64_t)s[2] * s[7], s[7]};
+        for (int j = 0; j < 3; ++j) d.q_stride[j] = d.k_stride[j] = d.v_stride[j] = d.o_stride[j] = st[j];
+        d.mask.n_global = s[4]; d.mask.global_start = s[4] ? s[1] / 2 - s[4] / 2 : 0;
+        if (s[6]) { d.mask.id_mode = MMT_IDS_2D; d.mask.patches_per_row = 16; d.mask.core_layers = 1; }
+        d.flags = MMT_FLAG_EXAMPLE_IDS | (t & 1 ? MMT_FLAG_SCALE_BEFORE_ADD : 0u);
+        d.mask.valid_len = (const int32_t*)dummy;      /* the [B,S] ids (never read on the host) */
+        d.tuning = tunings[t];
+        uint32_t sync[48] = {0};
+        d.sync = sync; d.sync_words = 48;
+        const size_t need = mmt_workspace_bytes(&d);
+        CHECK(need > 0);
+        unsigned char* ws = (unsigned char*)malloc(need);
+        CHECK(ws != NULL);
+        g_ws_lo = ws; g_ws_hi = ws + need;
+        CHECK(mmt_attn_fwd(&d, dummy, dummy, dummy, s[3] ? dummy : NULL, NULL, NULL, NULL, dummy, (float*)dummy, ws, need, NULL) == MMT_OK);
+        CHECK(g_last_kind == (s[4] ? 4 : 1) && g_last_pack == 1);   /* the general kernel (+ its global-rows combine) */
+        CHECK(mmt_attn_bwd(&d, dummy, dummy, dummy, s[3] ? dummy : NULL, NULL, NULL, NULL, dummy, dummy, (const float*)dummy, dummy, dummy, dummy,
+                           s[3] ? (float*)dummy : NULL, NULL, ws, need, NULL) == MMT_OK);
+        CHECK(g_last_kind == 5 && g_last_handover == 0 && g_last_pack == 1);
+        CHECK(mmt_attn_bwd(&d, dummy, dummy, dummy, s[3] ? dummy : NULL, NULL, NULL, NULL, dummy, dummy, (const float*)dummy, dummy, dummy, dummy,
+                           s[3] ? (float*)dummy : NULL, NULL, ws, need - 1, NULL) == MMT_E_WORKSPACE);
+        /* with a dense att_mask the flag is ignored like the rest of desc->mask */
+        CHECK(mmt_attn_fwd(&d, dummy, dummy, dummy, s[3] ? dummy : NULL, NULL, (const int32_t*)dummy, NULL, dummy, (float*)dummy, ws, need, NULL) == MMT_OK);
+        CHECK(g_last_kind == 1 && g_last_pack == 0);
+        CHECK(mmt_attn_bwd(&d, dummy, dummy, dummy, s[3] ? dummy : NULL, NULL, (const int32_t*)dummy, NULL, dummy, dummy, (const float*)dummy, dummy, dummy, dummy,
+                           s[3] ? (float*)dummy : NULL, NULL, ws, need, NULL) == MMT_OK);
+        CHECK(g_last_pack == 0);
+        free(ws);
+      }
+    }
+    const int before = g_launches;
+    d = base_desc(2, 300, 3, 32, MMT_BF16);
+    d.flags = MMT_FLAG_EXAMPLE_IDS;                 /* flag without the ids */
+    CHECK(mmt_workspace_bytes(&d) == 0);
+    CHECK(strstr(mmt_last_error(), "example ids") != NULL);
+    CHECK(mmt_attn_fwd(&d, dummy, dummy, dummy, dummy, NULL, NULL, NULL, dummy, NULL, dummy, 64, NULL) == MMT_E_INVALID);
+    CHECK(strstr(mmt_last_error(), "example ids") != NULL);
+    CHECK(mmt_attn_bwd(&d, dummy, dummy, dummy, dummy, NULL, NULL, NULL, dummy, dummy, (const float*)dummy, dummy, dummy, dummy,
+                       (float*)dummy, NULL, dummy, 64, NULL) == MMT_E_INVALID);
+    d.mask.valid_len = (const int32_t*)dummy;       /* ids with an image grid */
+    d.mask.patches_per_row = 16; d.mask.image_grid = MMT_IMAGE_GRID(1, 2);
+    CHECK(mmt_workspace_bytes(&d) == 0);
+    CHECK(mmt_attn_fwd(&d, dummy, dummy, dummy, dummy, NULL, NULL, NULL, dummy, NULL, dummy, 64, NULL) == MMT_E_UNSUPPORTED);
+    CHECK(strstr(mmt_last_error(), "image grid") != NULL);
+    CHECK(mmt_attn_bwd(&d, dummy, dummy, dummy, dummy, NULL, NULL, NULL, dummy, dummy, (const float*)dummy, dummy, dummy, dummy,
+                       (float*)dummy, NULL, dummy, 64, NULL) == MMT_E_UNSUPPORTED);
+    d.mask.image_grid = 0;                          /* ids with a listed global set: refused as without them */
+    int32_t listed[3] = {3, 9, 200};
+    d.mask.global_index = listed; d.mask.n_global = 3;
+    CHECK(mmt_attn_fwd(&d, dummy, dummy, dummy, dummy, NULL, NULL, NULL, dummy, NULL, dummy, 64, NULL) == MMT_E_UNSUPPORTED);
+    CHECK(strstr(mmt_last_error(), "listed global-token set") != NULL);
+    CHECK(g_launches == before);
   }
 
   /* ---- side inputs: the reference generator's argument errors (feature_utils.py:60-65) ---- */

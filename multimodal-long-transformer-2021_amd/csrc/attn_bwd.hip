@@ -58,9 +58,10 @@ __device__ __forceinline__ TileWalk band_walk(const PatternDev& pat, int x0, int
 }
 
 // Mask bit and relative-table column of one (q,k) pair (col < 0: no relative term).
-template <int MODE, bool GEN, bool GRID, typename P>
+// PACK (packed examples, kBand without a grid): the segmented term is `seg_ids`, the caller's compare of the two example ids.
+template <int MODE, bool GEN, bool GRID, bool PACK = false, typename P>
 __device__ __forceinline__ void pair_mask_col(const P& p, int b, int valid_len, int q, int k,
-                                              bool& keep, int& col) {
+                                              bool& keep, int& col, bool seg_ids = false) {
   int id = -1;
   col = -1;
   if (MODE == kDense) {
@@ -69,14 +70,15 @@ __device__ __forceinline__ void pair_mask_col(const P& p, int b, int valid_len, 
     if (p.rel_ids) id = p.rel_ids[off];
     if ((unsigned)id < (unsigned)p.R) col = id;
   } else if (GEN) {
-    keep = pattern_mask<GRID>(p.pat, p.grid, valid_len, q, k);
+    if constexpr (PACK) keep = pattern_mask_packed(p.pat, seg_ids, q, k);
+    else keep = pattern_mask<GRID>(p.pat, p.grid, valid_len, q, k);
     if (p.pat.id_mode) id = rel_id(p.pat, q, k);
     if ((unsigned)id < (unsigned)p.R) col = id;
   } else {
     const int d = k - q;
     const unsigned W = (unsigned)p.pat.radius;
     const bool near = (unsigned)(d + (int)W) <= 2u * W;
-    const bool seg = (k < valid_len) == (q < valid_len);
+    const bool seg = PACK ? seg_ids : (k < valid_len) == (q < valid_len);
     keep = (int)seg & ((int)near | (int)is_global(p.pat, k) | (int)is_global(p.pat, q) | (int)(GRID && in_grid(p.pat, p.grid, q, k)));
     if (p.pat.id_mode == 1) col = min(max(d, -p.pat.m), p.pat.m) + p.pat.m;
   }
@@ -144,7 +146,9 @@ __device__ __forceinline__ void build_table(const P& p, int n, const Frag<T, DH>
 // GRID: as attn_fwd_kernel (attn_fwd.hip) -- GridWalk's union and the grid term in the mask, for image-grid patterns only.
 // DH = 128 (head size): four dQ accumulators (a2, a3: head dims 64 .. 127), one workgroup per CU (at two the bf16 form
 // spills to scratch); XT = the K / Q / E tile, whole or in halves (BwdLds::kDqHalf).
-template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH>
+// PACK: as attn_fwd_kernel -- p.valid_len names the [B,S] example ids, PackWalk leaves out the key tiles with no id in the
+// row block's range.  A chunk of the global rows with no tile left writes zero partials, which the combine sums.
+template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH, bool PACK = false>
 __global__ __launch_bounds__(256, (sizeof(T) == 2 && DH == 64 ? 2 : 1)) void attn_bwd_dq_kernel(const BwdParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x & 63;
@@ -181,7 +185,8 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && DH == 64 ? 2 : 1)) void att
   const int q = q0 + r;
   const bool q_ok = q < p.S;
   const unsigned qc = (unsigned)min(q, p.S - 1);
-  const int valid_len = p.valid_len ? p.valid_len[b] : p.S;
+  const int valid_len = PACK ? 0 : (p.valid_len ? p.valid_len[b] : p.S);
+  constexpr bool CUR = GRID || PACK;      // the walk is a cursor (t_cur, t_nxt), not a count
   const T* Q = reinterpret_cast<const T*>(p.q) + (long)b * p.qs[0] + (long)n * p.qs[2];
   const T* K = reinterpret_cast<const T*>(p.k) + (long)b * p.ks[0] + (long)n * p.ks[2];
   const T* V = reinterpret_cast<const T*>(p.v) + (long)b * p.vs[0] + (long)n * p.vs[2];
@@ -200,6 +205,15 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && DH == 64 ? 2 : 1)) void att
     if (split_item) gw.init_chunk(w.b0, w.b0 + w.lenB - 1);
     else gw.init_band(p.pat, p.grid, q0, p.S);
     t_cur = gw.next(0);
+  }
+  PackWalk pw;                    // PACK: own id, cursor over the tiles that can hold an allowed pair, id r of the current / next tile
+  int qid = 0, kid = 0, kid_nxt = 0;
+  if constexpr (PACK) {
+    const int32_t* ids = p.valid_len + (long)b * p.S;
+    qid = ids[qc];
+    pw.init(ids, qid, p.S, w.count(), true);
+    t_cur = pw.next([&](int c) { return w.at(c); }, lane);
+    if (t_cur != PackWalk::kEnd) kid = pw.id_at(t_cur * 32 + r);
   }
 
   Frag<T, DH> qf, dof;
@@ -243,13 +257,13 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && DH == 64 ? 2 : 1)) void att
   Frag<T, DH> kf, vf;
   XT kt;
   {
-    const int k0 = (GRID ? t_cur : w.at(0)) * 32;
+    const int k0 = (PACK && t_cur == PackWalk::kEnd) ? 0 : (CUR ? t_cur : w.at(0)) * 32;
     kf.load_row(K + (unsigned)min(k0 + r, p.S - 1) * ks1, h);
     vf.load_row(V + (unsigned)min(k0 + r, p.S - 1) * vs1, h);
     kt.load(K, ks1, k0, p.S, lane, 0);
   }
-  for (int it = 0; GRID ? t_cur != GridWalk::kEnd : it < n_it; ++it, t_cur = t_nxt) {
-    const int k0 = (GRID ? t_cur : w.at(it)) * 32;
+  for (int it = 0; CUR ? t_cur != GridWalk::kEnd : it < n_it; ++it, t_cur = t_nxt, kid = kid_nxt) {
+    const int k0 = (CUR ? t_cur : w.at(it)) * 32;
     kt.to_lds(xlds, lane);
     XT kcur;                     // (a HalfTile is staged by the product at the end: it keeps the tile across the prefetch)
     if constexpr (sizeof(T) == 4 || L::kDqHalf) kcur = kt;
@@ -257,11 +271,13 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && DH == 64 ? 2 : 1)) void att
     c = mma_rows(kf, qf, c);     // S^T  [key x q]
     dp = mma_rows(vf, dof, dp);  // dP^T [key x q]
     if constexpr (GRID) t_nxt = gw.next(t_cur + 1);
-    if (GRID ? t_nxt != GridWalk::kEnd : it + 1 < n_it) {         // next tile's operands arrive under this tile's math
-      const int k1 = (GRID ? t_nxt : w.at(it + 1)) * 32;
+    if constexpr (PACK) t_nxt = pw.next([&](int c) { return w.at(c); }, lane);
+    if (CUR ? t_nxt != GridWalk::kEnd : it + 1 < n_it) {         // next tile's operands arrive under this tile's math
+      const int k1 = (CUR ? t_nxt : w.at(it + 1)) * 32;
       kf.load_row(K + (unsigned)min(k1 + r, p.S - 1) * ks1, h);
       vf.load_row(V + (unsigned)min(k1 + r, p.S - 1) * vs1, h);
       kt.load(K, ks1, k1, p.S, lane, 0);
+      if constexpr (PACK) kid_nxt = pw.id_at(k1 + r);
     }
     // phase 1: mask bits, table columns and the gathered relative scores (reads only)
     int cols[16];
@@ -271,7 +287,8 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && DH == 64 ? 2 : 1)) void att
     for (int i = 0; i < 16; ++i) {
       const int kk = k0 + kap(i, h);
       bool keep;
-      pair_mask_col<MODE, GEN, GRID>(p, b, valid_len, q, kk, keep, cols[i]);
+      if constexpr (PACK) pair_mask_col<MODE, GEN, GRID, true>(p, b, valid_len, q, kk, keep, cols[i], __shfl(kid, kap(i, h), 64) == qid);
+      else pair_mask_col<MODE, GEN, GRID>(p, b, valid_len, q, kk, keep, cols[i]);
       keepm |= (unsigned)keep << i;
       existm |= (unsigned)(kk < p.S && q_ok) << i;
       rel[i] = cols[i] >= 0 ? trow[cols[i]] : 0.f;
@@ -445,8 +462,9 @@ __global__ __launch_bounds__(DH) void attn_bwd_dq_combine_kernel(const BwdParams
 // =========================================================================================
 // GRID instantiations are built for one workgroup per CU: at two the bf16 form spills to scratch (as the GRID = false
 // ones do, whose figures are kept as they were).  So are the DH = 128 ones (dk2, dk3, dv2, dv3: head dims 64 .. 127).
-template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH>
-__global__ __launch_bounds__(256, ((sizeof(T) == 2 && !GRID && DH == 64) ? 2 : 1)) void attn_bwd_dkv_kernel(const BwdParams p) {
+// PACK: the same walk over query tiles against the key block's id range (the pattern is symmetric); built like the GRID ones.
+template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH, bool PACK = false>
+__global__ __launch_bounds__(256, ((sizeof(T) == 2 && !GRID && !PACK && DH == 64) ? 2 : 1)) void attn_bwd_dkv_kernel(const BwdParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -481,7 +499,8 @@ __global__ __launch_bounds__(256, ((sizeof(T) == 2 && !GRID && DH == 64) ? 2 : 1
   const int k = k0 + r;
   const bool k_ok = k < p.S;
   const unsigned kc = (unsigned)min(k, p.S - 1);
-  const int valid_len = p.valid_len ? p.valid_len[b] : p.S;
+  const int valid_len = PACK ? 0 : (p.valid_len ? p.valid_len[b] : p.S);
+  constexpr bool CUR = GRID || PACK;      // the walk is a cursor (t_cur, t_nxt), not a count
   const T* Q = reinterpret_cast<const T*>(p.q) + (long)b * p.qs[0] + (long)n * p.qs[2];
   const T* K = reinterpret_cast<const T*>(p.k) + (long)b * p.ks[0] + (long)n * p.ks[2];
   const T* V = reinterpret_cast<const T*>(p.v) + (long)b * p.vs[0] + (long)n * p.vs[2];
@@ -502,6 +521,15 @@ __global__ __launch_bounds__(256, ((sizeof(T) == 2 && !GRID && DH == 64) ? 2 : 1
     else gw.init_band(p.pat, p.grid, k0, p.S);
     t_cur = gw.next(0);
   }
+  PackWalk pw;                    // PACK: the key's id, cursor over the query tiles, id r of the current / next query tile
+  int kid = 0, qid = 0, qid_nxt = 0;
+  if constexpr (PACK) {
+    const int32_t* ids = p.valid_len + (long)b * p.S;
+    kid = ids[kc];
+    pw.init(ids, kid, p.S, w.count(), true);
+    t_cur = pw.next([&](int c) { return w.at(c); }, lane);
+    if (t_cur != PackWalk::kEnd) qid = pw.id_at(t_cur * 32 + r);
+  }
 
   Frag<T, DH> kf, vf;
   kf.load_row(K + kc * ks1, h);
@@ -514,19 +542,23 @@ __global__ __launch_bounds__(256, ((sizeof(T) == 2 && !GRID && DH == 64) ? 2 : 1
   const int n_it = w.count();
   VTile<T, DH> qt, dot;
   if constexpr (sizeof(T) == 2) {            // first tile's rows (prefetch registers)
-    qt.load(Q, qs1, (GRID ? t_cur : w.at(0)) * 32, p.S, lane, 0);
-    dot.load(DO, os1, (GRID ? t_cur : w.at(0)) * 32, p.S, lane, 0);
+    qt.load(Q, qs1, (PACK && t_cur == PackWalk::kEnd) ? 0 : (CUR ? t_cur : w.at(0)) * 32, p.S, lane, 0);    // (kEnd: no tile at all, nothing to prefetch)
+    dot.load(DO, os1, (PACK && t_cur == PackWalk::kEnd) ? 0 : (CUR ? t_cur : w.at(0)) * 32, p.S, lane, 0);
   }
-  for (int it = 0; GRID ? t_cur != GridWalk::kEnd : it < n_it; ++it, t_cur = t_nxt) {
-    const int q0 = (GRID ? t_cur : w.at(it)) * 32;
+  for (int it = 0; CUR ? t_cur != GridWalk::kEnd : it < n_it; ++it, t_cur = t_nxt, qid = qid_nxt) {
+    const int q0 = (CUR ? t_cur : w.at(it)) * 32;
     if constexpr (GRID) t_nxt = gw.next(t_cur + 1);
+    if constexpr (PACK) {
+      t_nxt = pw.next([&](int c) { return w.at(c); }, lane);
+      if (t_nxt != PackWalk::kEnd) qid_nxt = pw.id_at(t_nxt * 32 + r);
+    }
     Frag<T, DH> qf, dof;
     if constexpr (sizeof(T) == 2) {
       qt.to_lds(qlds, lane);
       dot.to_lds(dolds, lane);
-      if (GRID ? t_nxt != GridWalk::kEnd : it + 1 < n_it) {                   // next tile's rows arrive under this tile's math
-        qt.load(Q, qs1, (GRID ? t_nxt : w.at(it + 1)) * 32, p.S, lane, 0);
-        dot.load(DO, os1, (GRID ? t_nxt : w.at(it + 1)) * 32, p.S, lane, 0);
+      if (CUR ? t_nxt != GridWalk::kEnd : it + 1 < n_it) {                   // next tile's rows arrive under this tile's math
+        qt.load(Q, qs1, (CUR ? t_nxt : w.at(it + 1)) * 32, p.S, lane, 0);
+        dot.load(DO, os1, (CUR ? t_nxt : w.at(it + 1)) * 32, p.S, lane, 0);
       }
     } else {
       qf.load_row(Q + (unsigned)min(q0 + r, p.S - 1) * qs1, h);
@@ -551,7 +583,8 @@ __global__ __launch_bounds__(256, ((sizeof(T) == 2 && !GRID && DH == 64) ? 2 : 1
     for (int i = 0; i < 16; ++i) {
       const int qq = q0 + kap(i, h);
       bool keep;
-      pair_mask_col<MODE, GEN, GRID>(p, b, valid_len, qq, k, keep, cols[i]);
+      if constexpr (PACK) pair_mask_col<MODE, GEN, GRID, true>(p, b, valid_len, qq, k, keep, cols[i], __shfl(qid, kap(i, h), 64) == kid);
+      else pair_mask_col<MODE, GEN, GRID>(p, b, valid_len, qq, k, keep, cols[i]);
       keepm |= (unsigned)keep << i;
       existm |= (unsigned)(qq < p.S && k_ok) << i;
       rel[i] = cols[i] >= 0 ? tab[kap(i, h) * kTStride(Rp) + cols[i]] : 0.f;
@@ -726,7 +759,7 @@ static void allow_lds(K kernel, int bytes) {
                                                    hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
-template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH>
+template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH, bool PACK>
 static hipError_t launch_bwd_one(const BwdParams& p_in, hipStream_t st) {
   BwdParams p = p_in;
   p.red_per_plane = ((p.S + 127) >> 7) * 4;               // one dE partial per wave (32 rows)
@@ -734,16 +767,16 @@ static hipError_t launch_bwd_one(const BwdParams& p_in, hipStream_t st) {
   const int per_bn = (p.n_chunks * p.n_gblk + 3) / 4;
   dim3 grid(p.n_band_blocks + (MODE == kBand ? per_bn * p.B * p.N : 0));
   const int lds_a = 4 * BwdLds<T, Rp, DH>::kDq, lds_b = 4 * BwdLds<T, Rp, DH>::kDkv;
-  allow_lds(attn_bwd_dq_kernel<T, MODE, Rp, GEN, GRID, DH>, lds_a);
-  allow_lds(attn_bwd_dkv_kernel<T, MODE, Rp, GEN, GRID, DH>, lds_b);
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<T, MODE, Rp, GEN, GRID, DH>), grid, dim3(256), lds_a, st, p);
+  allow_lds(attn_bwd_dq_kernel<T, MODE, Rp, GEN, GRID, DH, PACK>, lds_a);
+  allow_lds(attn_bwd_dkv_kernel<T, MODE, Rp, GEN, GRID, DH, PACK>, lds_b);
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<T, MODE, Rp, GEN, GRID, DH, PACK>), grid, dim3(256), lds_a, st, p);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (MODE == kBand && p.n_gblk > 0) {
     hipLaunchKernelGGL((attn_bwd_dq_combine_kernel<T, DH>), dim3(p.pat.ng, p.B * p.N), dim3(DH), 0, st, p);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
-  hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, MODE, Rp, GEN, GRID, DH>), grid, dim3(256), lds_b, st, p);
+  hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, MODE, Rp, GEN, GRID, DH, PACK>), grid, dim3(256), lds_b, st, p);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if (MODE == kBand && p.n_gblk > 0) {
     hipLaunchKernelGGL((attn_bwd_dkv_combine_kernel<T, DH>), dim3(p.pat.ng, p.B * p.N), dim3(DH), 0, st, p);
@@ -756,17 +789,19 @@ static hipError_t launch_bwd_one(const BwdParams& p_in, hipStream_t st) {
   return e;
 }
 
-template <typename T, int MODE, bool GEN, bool GRID, int DH>
+template <typename T, int MODE, bool GEN, bool GRID, int DH, bool PACK = false>
 static hipError_t launch_bwd_rp(const BwdParams& p, hipStream_t st) {
-  if (p.Rp == 32) return launch_bwd_one<T, MODE, 32, GEN, GRID, DH>(p, st);
-  if (p.Rp == 64) return launch_bwd_one<T, MODE, 64, GEN, GRID, DH>(p, st);
-  return launch_bwd_one<T, MODE, 128, GEN, GRID, DH>(p, st);
+  if (p.Rp == 32) return launch_bwd_one<T, MODE, 32, GEN, GRID, DH, PACK>(p, st);
+  if (p.Rp == 64) return launch_bwd_one<T, MODE, 64, GEN, GRID, DH, PACK>(p, st);
+  return launch_bwd_one<T, MODE, 128, GEN, GRID, DH, PACK>(p, st);
 }
 
 template <typename T, int DH>
-static hipError_t launch_bwd_t(const BwdParams& p, int mode, hipStream_t st) {
+static hipError_t launch_bwd_t(const BwdParams& p, int mode, bool pack, hipStream_t st) {
   if (mode == kDense) return launch_bwd_rp<T, kDense, true, false, DH>(p, st);
   const bool gen = !(p.pat.id_mode == 0 || p.perm_1d);
+  if (pack)                          // packed examples (never with a grid): their own instantiations too
+    return gen ? launch_bwd_rp<T, kBand, true, false, DH, true>(p, st) : launch_bwd_rp<T, kBand, false, false, DH, true>(p, st);
   if (p.grid.ga > 0)                 // image grid: its own instantiations
     return gen ? launch_bwd_rp<T, kBand, true, true, DH>(p, st) : launch_bwd_rp<T, kBand, false, true, DH>(p, st);
   return gen ? launch_bwd_rp<T, kBand, true, false, DH>(p, st) : launch_bwd_rp<T, kBand, false, false, DH>(p, st);
@@ -793,11 +828,13 @@ hipError_t launch_drel_reduce(const BwdParams& p, bool bf16, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t launch_attn_bwd(const BwdParams& p, int mode, bool bf16, hipStream_t st) {
-  // head size 128 and the image grid: the general kernels only (the lean kernels are built for head size 64)
-  if (p.D == 128) return bf16 ? launch_bwd_t<__bf16, 128>(p, mode, st) : launch_bwd_t<float, 128>(p, mode, st);
-  if (mode == kBand && bf16 && p.grid.ga == 0 && (p.pat.id_mode == 0 || (p.perm_1d && p.Rp <= 64) || p.lean2d)) return launch_attn_bwd_band_bf16(p, st);
-  return bf16 ? launch_bwd_t<__bf16, 64>(p, mode, st) : launch_bwd_t<float, 64>(p, mode, st);
+hipError_t launch_attn_bwd(const BwdParams& p, int mode, bool bf16, bool pack, hipStream_t st) {
+  // head size 128, the image grid and packed examples: the general kernels only (the lean kernels are built for head size
+  // 64 and for valid_len as the segmented term)
+  pack = pack && mode == kBand;
+  if (p.D == 128) return bf16 ? launch_bwd_t<__bf16, 128>(p, mode, pack, st) : launch_bwd_t<float, 128>(p, mode, pack, st);
+  if (mode == kBand && bf16 && !pack && p.grid.ga == 0 && (p.pat.id_mode == 0 || (p.perm_1d && p.Rp <= 64) || p.lean2d)) return launch_attn_bwd_band_bf16(p, st);
+  return bf16 ? launch_bwd_t<__bf16, 64>(p, mode, pack, st) : launch_bwd_t<float, 64>(p, mode, pack, st);
 }
 
 }  // namespace mmt

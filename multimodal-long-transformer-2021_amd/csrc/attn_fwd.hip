@@ -26,7 +26,10 @@ namespace mmt {
 // GRID = true (kBand only): the pattern has the image-grid term -- the tile walk is GridWalk's union and the
 // per-element mask ORs in_grid; GRID = false instantiations (every pattern without a grid) are the kernels as before.
 // DH = head size, 64 or 128: fragments and V tile scale with it; DH = 128 adds the O accumulators o2, o3.
-template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH>
+// PACK = true (kBand without a grid only): packed examples -- p.valid_len names the [B,S] example ids, the segmented term
+// is ids[q] == ids[k], and the walk is PackWalk's: key tiles with no id in the row block's id range are never fetched.
+// PACK = false instantiations are the kernels as before.
+template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH, bool PACK = false>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x & 63;
@@ -59,7 +62,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
   const int b = bn / p.N, n = bn - b * p.N;
   const int q = q0 + r;
   const bool q_ok = q < p.S;
-  const int valid_len = p.valid_len ? p.valid_len[b] : p.S;
+  const int valid_len = PACK ? 0 : (p.valid_len ? p.valid_len[b] : p.S);
+  constexpr bool CUR = GRID || PACK;      // the walk is a cursor (t_cur, t_nxt), not a count
 
   const T* Q = reinterpret_cast<const T*>(p.q) + (long)b * p.qs[0] + (long)n * p.qs[2];
   const T* K = reinterpret_cast<const T*>(p.k) + (long)b * p.ks[0] + (long)n * p.ks[2];
@@ -97,6 +101,18 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
     else gw.init_band(p.pat, p.grid, q0, p.S);
     t_cur = gw.next(0);
   }
+  // PACK: the row's own id, the cursor over the tiles that can hold an allowed pair, and id r of the current / next tile.
+  // A chunk of the global rows may have no such tile: its partial is then the empty one (max = -inf, sum = 0, O = 0),
+  // which the combine takes as long as all chunks are reduced in one pass (<= 64 of them); beyond, nothing is left out.
+  PackWalk pw;
+  int qid = 0, kid = 0, kid_nxt = 0;
+  if constexpr (PACK) {
+    const int32_t* ids = p.valid_len + (long)b * p.S;
+    qid = ids[min(q, p.S - 1)];
+    pw.init(ids, qid, p.S, n_it, !rows_item || p.n_chunks <= 64);
+    t_cur = pw.next(tile_at, lane);
+    if (t_cur != PackWalk::kEnd) kid = pw.id_at(t_cur * 32 + r);
+  }
 
   Frag<T, DH> qf;
   qf.load_row(Q + (unsigned)min(q, p.S - 1) * qs1, h);
@@ -105,7 +121,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
   Frag<T, DH> kf;
   VTile<T, DH> vt;
   {
-    const int k0 = (GRID ? t_cur : tile_at(0)) * 32;
+    const int k0 = (PACK && t_cur == PackWalk::kEnd) ? 0 : (CUR ? t_cur : tile_at(0)) * 32;
     kf.load_row(K + (unsigned)min(k0 + r, p.S - 1) * ks1, h);
     vt.load(V, vs1, k0, p.S, lane, 0);
   }
@@ -142,8 +158,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
   const bool qblk_valid = q0 + 31 < valid_len, qblk_pad = q0 >= valid_len;
   const bool qblk_plain = q0 + 31 < p.S && !(p.pat.ng > 0 && q0 + 31 >= p.pat.g0 && q0 < p.pat.g0 + p.pat.ng);
 
-  for (int it = 0; GRID ? t_cur != GridWalk::kEnd : it < n_it; ++it, t_cur = t_nxt) {
-    const int k0 = (GRID ? t_cur : tile_at(it)) * 32;
+  for (int it = 0; CUR ? t_cur != GridWalk::kEnd : it < n_it; ++it, t_cur = t_nxt, kid = kid_nxt) {
+    const int k0 = (CUR ? t_cur : tile_at(it)) * 32;
     vt.to_lds(vlds, lane);
 
     f32x16 c = {0};
@@ -152,10 +168,12 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
     VTile<T, DH> vcur;
     if constexpr (sizeof(T) == 4) vcur = vt;
     if constexpr (GRID) t_nxt = gw.next(t_cur + 1);
-    if (GRID ? t_nxt != GridWalk::kEnd : it + 1 < n_it) {   // prefetch the next tile (registers) under this tile's math
-      const int k1 = (GRID ? t_nxt : tile_at(it + 1)) * 32;
+    if constexpr (PACK) t_nxt = pw.next(tile_at, lane);
+    if (CUR ? t_nxt != GridWalk::kEnd : it + 1 < n_it) {   // prefetch the next tile (registers) under this tile's math
+      const int k1 = (CUR ? t_nxt : tile_at(it + 1)) * 32;
       kf.load_row(K + (unsigned)min(k1 + r, p.S - 1) * ks1, h);
       vt.load(V, vs1, k1, p.S, lane, 0);
+      if constexpr (PACK) kid_nxt = pw.id_at(k1 + r);
     }
 
     // ---- scores in the log2 domain --------------------------------------------------------
@@ -164,7 +182,9 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
     bool fast = false;
     if (MODE == kBand) {
       // wave-uniform classification: every (q,k) of the tile unmasked and 1-D (or no) ids
-      const bool seg_all = (qblk_valid && k0 + 31 < valid_len) || (qblk_pad && k0 >= valid_len);
+      bool seg_all;
+      if constexpr (PACK) seg_all = pw.lo == pw.hi && __all(kid == pw.lo);    // one example in the rows and in the keys
+      else seg_all = (qblk_valid && k0 + 31 < valid_len) || (qblk_pad && k0 >= valid_len);
       const bool band_all = (k0 - (q0 + 31) >= -p.pat.radius) && (k0 + 31 - q0 <= p.pat.radius);
       fast = !GEN && seg_all && band_all && qblk_plain && k0 + 31 < p.S;
     }
@@ -194,7 +214,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
         const int kk = kb + ci, d = d0 + ci;
         const bool near = (unsigned)(d + (int)W) <= 2u * W;
         const bool gk = (unsigned)(kk - p.pat.g0) < (unsigned)p.pat.ng;
-        const bool seg = (kk < valid_len) == qv;
+        const bool seg = PACK ? __shfl(kid, 4 * h + ci, 64) == qid : (kk < valid_len) == qv;
         const bool keep = (int)seg & ((int)near | (int)gk | (int)gq | (int)(GRID && in_grid(p.pat, p.grid, q, kk)));
         float rel = 0.f;
         if (id_mode == 1) rel = trow[min(max(d, -mdist), mdist) + mdist];
@@ -215,7 +235,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
           keep = p.att_mask ? p.att_mask[off] != 0 : true;
           if (p.rel_ids) id = p.rel_ids[off];
         } else {
-          keep = pattern_mask<GRID>(p.pat, p.grid, valid_len, q, kk);
+          if constexpr (PACK) keep = pattern_mask_packed(p.pat, __shfl(kid, kap(i, h), 64) == qid, q, kk);
+          else keep = pattern_mask<GRID>(p.pat, p.grid, valid_len, q, kk);
           if (id_mode) id = rel_id(p.pat, q, kk);
         }
         float rel = 0.f;
@@ -372,37 +393,39 @@ __global__ __launch_bounds__(DH) void attn_rows_combine_kernel(const FwdParams p
 }
 
 // ------------------------------------ launchers -----------------------------------------
-template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH>
+template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH, bool PACK>
 static hipError_t launch_one(const FwdParams& p, dim3 grid, hipStream_t st) {
   const int lds = 4 * WaveLds<T, Rp, DH>::kBytes;
   if (lds > 64 * 1024)               // (the 128-wide table: relative vocabularies of 65..128 ids; DH = 128 from Rp = 64)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<T, MODE, Rp, GEN, GRID, DH>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  hipLaunchKernelGGL((attn_fwd_kernel<T, MODE, Rp, GEN, GRID, DH>), grid, dim3(256), lds, st, p);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<T, MODE, Rp, GEN, GRID, DH, PACK>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  hipLaunchKernelGGL((attn_fwd_kernel<T, MODE, Rp, GEN, GRID, DH, PACK>), grid, dim3(256), lds, st, p);
   return hipGetLastError();
 }
 
-template <typename T, int MODE, bool GEN, bool GRID, int DH>
+template <typename T, int MODE, bool GEN, bool GRID, int DH, bool PACK = false>
 static hipError_t launch_rp(const FwdParams& p, dim3 grid, hipStream_t st) {
-  if (p.R <= 32) return launch_one<T, MODE, 32, GEN, GRID, DH>(p, grid, st);
-  if (p.R <= 64) return launch_one<T, MODE, 64, GEN, GRID, DH>(p, grid, st);
-  return launch_one<T, MODE, 128, GEN, GRID, DH>(p, grid, st);
+  if (p.R <= 32) return launch_one<T, MODE, 32, GEN, GRID, DH, PACK>(p, grid, st);
+  if (p.R <= 64) return launch_one<T, MODE, 64, GEN, GRID, DH, PACK>(p, grid, st);
+  return launch_one<T, MODE, 128, GEN, GRID, DH, PACK>(p, grid, st);
 }
 
 template <typename T, int DH>
-static hipError_t launch_t(const FwdParams& p, int mode, dim3 grid, hipStream_t st) {
+static hipError_t launch_t(const FwdParams& p, int mode, bool pack, dim3 grid, hipStream_t st) {
   if (mode == kDense) return launch_rp<T, kDense, true, false, DH>(p, grid, st);
   const bool gen = !(p.pat.id_mode == 0 || p.perm_1d);
+  if (pack)                          // packed examples (never with a grid: refused on the host): their own instantiations too
+    return gen ? launch_rp<T, kBand, true, false, DH, true>(p, grid, st) : launch_rp<T, kBand, false, false, DH, true>(p, grid, st);
   if (p.grid.ga > 0)                 // image grid: its own instantiations (the others carry no trace of it)
     return gen ? launch_rp<T, kBand, true, true, DH>(p, grid, st) : launch_rp<T, kBand, false, true, DH>(p, grid, st);
   return gen ? launch_rp<T, kBand, true, false, DH>(p, grid, st) : launch_rp<T, kBand, false, false, DH>(p, grid, st);
 }
 
-hipError_t launch_attn_fwd(const FwdParams& p, int mode, bool bf16, hipStream_t st) {
+hipError_t launch_attn_fwd(const FwdParams& p, int mode, bool bf16, bool pack, hipStream_t st) {
   // band items first, then (kBand only) the global-row items of the same launch
   const int per_bn = (p.n_chunks * p.n_rowblk + 3) / 4;
   dim3 grid(p.n_band_blocks + (mode == kBand ? per_bn * p.B * p.N : 0));
-  if (p.D == 128) return bf16 ? launch_t<__bf16, 128>(p, mode, grid, st) : launch_t<float, 128>(p, mode, grid, st);
-  return bf16 ? launch_t<__bf16, 64>(p, mode, grid, st) : launch_t<float, 64>(p, mode, grid, st);
+  if (p.D == 128) return bf16 ? launch_t<__bf16, 128>(p, mode, pack, grid, st) : launch_t<float, 128>(p, mode, pack, grid, st);
+  return bf16 ? launch_t<__bf16, 64>(p, mode, pack, grid, st) : launch_t<float, 64>(p, mode, pack, grid, st);
 }
 
 template <int DH>

@@ -51,6 +51,59 @@ struct GridWalk {
   }
 };
 
+// Packed examples (MMT_FLAG_EXAMPLE_IDS): tile walk of a 32-row block whose segmented term is ids[x] == ids[y].
+// The candidates are the tiles of the plain walk (`at(0 .. n_it)`: band, global tiles or a chunk); a candidate none of
+// whose 32 ids lies in [lo, hi], the id range of the block's own rows, cannot hold an allowed pair and is left out
+// BEFORE anything of it is fetched -- valid for any ids, effective for ids that came from breakpoints (monotone along
+// the row).  Eight candidates are judged per step: lane (r, h) reads id r of candidates base + 2j + h, j = 0..3 (four
+// independent coalesced 128-byte loads per half, one latency), a ballot per j gives the two hit bits.  Everything kept
+// here is wave-uniform.  Positions >= S never hit.
+struct PackWalk {
+  static constexpr int kEnd = 0x7fffffff;
+  const int32_t* ids;     // [S] example ids of the batch row
+  int lo, hi;             // id range of the block's rows
+  bool all;               // visit every candidate (no tile is left out)
+  int S, n_it;
+  int base;               // candidates [base, base + 8) have been judged
+  unsigned hits;          // ... and these of them are still to visit
+  // id of position x of the row (clamped to the sequence: callers mask x >= S themselves)
+  __device__ __forceinline__ int id_at(int x) const { return ids[min(x, S - 1)]; }
+  // [lo, hi] over the 32 rows x0 .. x0 + 31 (own = id of row x0 + (lane & 31), the same in both halves)
+  __device__ __forceinline__ void init(const int32_t* row_ids, int own, int S_, int n_it_, bool skip) {
+    ids = row_ids; S = S_; n_it = n_it_; base = -8; hits = 0;
+    int mn = own, mx = own;
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) {
+      mn = min(mn, __shfl_xor(mn, o, 64));
+      mx = max(mx, __shfl_xor(mx, o, 64));
+    }
+    lo = __builtin_amdgcn_readfirstlane(mn);
+    hi = __builtin_amdgcn_readfirstlane(mx);
+    all = !skip;
+  }
+  // next tile to visit (kEnd: none left); `at` maps a candidate number to its tile
+  template <typename At>
+  __device__ __forceinline__ int next(const At& at, int lane) {
+    const int r = lane & 31, h = lane >> 5;
+    while (hits == 0) {
+      base += 8;
+      if (base >= n_it) return kEnd;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = base + 2 * j + h;
+        const int x = at(min(c, n_it - 1)) * 32 + r;
+        const int id = id_at(x);
+        const bool hit = c < n_it && x < S && (all || (id >= lo && id <= hi));
+        const unsigned long long m = __ballot(hit);
+        hits |= ((unsigned)m != 0u ? 1u : 0u) << (2 * j) | ((unsigned)(m >> 32) != 0u ? 1u : 0u) << (2 * j + 1);
+      }
+    }
+    const int j = __builtin_ctz(hits);
+    hits &= hits - 1;
+    return at(base + j);
+  }
+};
+
 // ------------------------------- bf16: 32x32x16 MFMA ---------------------------------
 // MFMA k-index (8h + j) of step s is mapped to head-dim d = (DH/2)h + 8s + j, so each lane
 // loads DH contiguous bytes of its row (DH/16 x 16 B).

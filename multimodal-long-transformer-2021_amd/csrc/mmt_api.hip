@@ -49,6 +49,7 @@ struct Plan {
 // The global tokens, if any, must be the peeled kind (<= 8, contiguous); the band at most 8 tiles wide.
 int handover_slots(const mmt_attn_desc* d, bool dense) {
   if (dense || d->dtype != MMT_BF16 || (d->mask.image_grid & 0xFF) || d->D != 64) return 0;     // (an image grid, head size 128: the general kernels)
+  if (d->flags & MMT_FLAG_EXAMPLE_IDS) return 0;                                                 // (packed examples: likewise)
   if (d->mask.global_index || d->mask.n_global > 8) return 0;
   const int W = d->mask.local_radius > d->S ? d->S : d->mask.local_radius;
   const int slots = 2 * ((W + 31) / 32) + 1;
@@ -96,6 +97,16 @@ int check_desc(const mmt_attn_desc* d) {
     if ((int64_t)m.patches_per_row * m.patches_per_row > d->S) return fail(MMT_E_INVALID, "image part longer than the sequence");
   }
   return check_grid(m, d->S);
+}
+
+// MMT_FLAG_EXAMPLE_IDS (mask.valid_len names the [B,S] example ids): its argument errors.  Asked for structured calls and
+// by mmt_workspace_bytes only -- with a dense att_mask the flag is ignored like the rest of desc->mask.
+int check_packed(const mmt_attn_desc* d) {
+  if (!(d->flags & MMT_FLAG_EXAMPLE_IDS)) return MMT_OK;
+  if (!d->mask.valid_len) return fail(MMT_E_INVALID, "MMT_FLAG_EXAMPLE_IDS: mask.valid_len must name the [B,S] example ids, it is NULL");
+  if (grid_radius(d->mask) > 0)
+    return fail(MMT_E_UNSUPPORTED, "example ids with an image grid: the grid names one image per row, packed rows have several (materialise att_mask and use the dense operator)");
+  return MMT_OK;
 }
 
 mmt::PatternDev make_pattern(const mmt_mask_desc& m, int S) {
@@ -161,8 +172,8 @@ Plan make_plan(const mmt_attn_desc* d, bool dense) {
 // below R (small images: P = 4, m = 3 gives 31 / 32 against R = 49); never more than R (ids >= R contribute 0 under
 // the one-hot lookup).  0 = not eligible (the general kernels of attn_fwd.hip / attn_bwd.hip take
 // the call).
-int lean2d_width(const mmt::PatternDev& pat, const mmt::GridDev& grid, int R, int D, bool dense) {
-  if (dense || pat.id_mode != MMT_IDS_2D || R <= 0 || grid.ga > 0 || D != 64) return 0;
+int lean2d_width(const mmt::PatternDev& pat, const mmt::GridDev& grid, int R, int D, bool dense, bool pack) {
+  if (dense || pack || pat.id_mode != MMT_IDS_2D || R <= 0 || grid.ga > 0 || D != 64) return 0;
   const int d = 2 * pat.r + 1, n2 = d + 2;
   if (n2 * n2 > 256) return 0;                       // look-up table of the clamped (dx, dy) grid
   int need = std::max(d * d + 8, 2 * pat.m + 1);
@@ -213,7 +224,7 @@ int mmt_write_step_scalars(uint64_t* dropout_epoch, float* adamw_hyper, uint64_t
 const char* mmt_last_error(void) { return g_err; }
 
 size_t mmt_workspace_bytes(const mmt_attn_desc* desc) {
-  if (check_desc(desc) != MMT_OK) return 0;
+  if (check_desc(desc) != MMT_OK || check_packed(desc) != MMT_OK) return 0;
   Plan pl = make_plan(desc, false);   // the structured plan is a superset of the dense one
   return pl.fwd_ws > pl.bwd_ws ? pl.fwd_ws : pl.bwd_ws;
 }
@@ -228,6 +239,8 @@ int mmt_attn_fwd(const mmt_attn_desc* desc, const void* q, const void* k, const 
   const bool dense = att_mask != nullptr || rel_ids != nullptr;
   if (!dense && desc->mask.global_index && desc->mask.n_global > 0)
     return fail(MMT_E_UNSUPPORTED, "a listed global-token set has no structured kernel: materialise att_mask with mmt_side_inputs(materialize_pattern = 1) and pass it (dense operator)");
+  const bool pack = !dense && (desc->flags & MMT_FLAG_EXAMPLE_IDS);
+  if (pack) if (int rc = check_packed(desc)) return rc;
   const Plan pl = make_plan(desc, dense);
   if (pl.fwd_ws > 0 && (!workspace || workspace_bytes < pl.fwd_ws))
     return fail(MMT_E_WORKSPACE, "workspace too small: need %zu bytes, got %zu", pl.fwd_ws, workspace_bytes);
@@ -244,7 +257,7 @@ int mmt_attn_fwd(const mmt_attn_desc* desc, const void* q, const void* k, const 
 
   hipError_t e;
   if (dense) {
-    e = mmt::launch_attn_fwd(p, mmt::kDense, bf16, st);
+    e = mmt::launch_attn_fwd(p, mmt::kDense, bf16, false, st);
     if (e != hipSuccess) return fail(MMT_E_LAUNCH, "dense forward launch: %s", hipGetErrorString(e));
     return MMT_OK;
   }
@@ -254,10 +267,11 @@ int mmt_attn_fwd(const mmt_attn_desc* desc, const void* q, const void* k, const 
     p.part_o = reinterpret_cast<float*>(workspace);
     p.part_ml = p.part_o + (size_t)desc->B * desc->N * pl.n_rowblk * pl.n_chunks * (32 * desc->D);
   }
-  p.lean_rp = lean2d_width(p.pat, p.grid, desc->R, desc->D, dense);
-  // an image grid (p.grid.ga > 0) and head size 128 are served by the general kernels only (attn_fwd.hip): every lean /
+  p.lean_rp = lean2d_width(p.pat, p.grid, desc->R, desc->D, dense, pack);
+  // an image grid (p.grid.ga > 0), head size 128 and packed examples (MMT_FLAG_EXAMPLE_IDS: valid_len holds ids there, which
+  // only the PACK instantiations read as such) are served by the general kernels only (attn_fwd.hip): every lean /
   // window / walk kernel below needs `lean`, so no tuning switch can route them past it
-  const bool lean = bf16 && p.grid.ga == 0 && desc->D == 64 && (p.pat.id_mode == 0 || (p.perm_1d && desc->R <= 64) || p.lean_rp);   // attn_fwd_band.hip (tables up to 64 wide)
+  const bool lean = bf16 && !pack && p.grid.ga == 0 && desc->D == 64 && (p.pat.id_mode == 0 || (p.perm_1d && desc->R <= 64) || p.lean_rp);   // attn_fwd_band.hip (tables up to 64 wide)
   p.part_scale = (lean && p.drop_thresh) ? p.inv_keep : 1.f;
   // window kernel (attn_fwd_win.hip): K / V staged once per workgroup, global keys as a peeled quarter-tile step,
   // rows of up to 16 global tokens by flipped-orientation workgroups of the same launch (no workspace, no combine
@@ -343,7 +357,7 @@ int mmt_attn_fwd(const mmt_attn_desc* desc, const void* q, const void* k, const 
     p.n_rowblk = n_rowblk_items;
     p.rows_only = 1;
   }
-  e = lean ? mmt::launch_attn_fwd_band_bf16(p, st) : mmt::launch_attn_fwd(p, mmt::kBand, bf16, st);
+  e = lean ? mmt::launch_attn_fwd_band_bf16(p, st) : mmt::launch_attn_fwd(p, mmt::kBand, bf16, pack, st);
   if (e != hipSuccess) return fail(MMT_E_LAUNCH, "band forward launch: %s", hipGetErrorString(e));
   if (pl.split_rows) {
     e = mmt::launch_rows_combine(p, bf16, st);
@@ -364,6 +378,8 @@ int mmt_attn_bwd(const mmt_attn_desc* desc, const void* q, const void* k, const 
   const bool dense = att_mask != nullptr || rel_ids != nullptr;
   if (!dense && desc->mask.global_index && desc->mask.n_global > 0)
     return fail(MMT_E_UNSUPPORTED, "a listed global-token set has no structured kernel: materialise att_mask with mmt_side_inputs(materialize_pattern = 1) and pass it (dense operator)");
+  const bool pack = !dense && (desc->flags & MMT_FLAG_EXAMPLE_IDS);
+  if (pack) if (int rc = check_packed(desc)) return rc;
   const Plan pl = make_plan(desc, dense);
   if (!workspace || workspace_bytes < pl.bwd_ws)
     return fail(MMT_E_WORKSPACE, "workspace too small: need %zu bytes, got %zu", pl.bwd_ws, workspace_bytes);
@@ -387,7 +403,7 @@ int mmt_attn_bwd(const mmt_attn_desc* desc, const void* q, const void* k, const 
   p.perm_1d = (!dense && p.pat.id_mode == MMT_IDS_1D && desc->R >= 2 * p.pat.m + 1) ? 1 : 0;
   p.drop_thresh = f.drop_thresh; p.seed_lo = f.seed_lo; p.seed_hi = f.seed_hi; p.inv_keep = f.inv_keep; p.epoch = f.epoch;
   if (desc->dtype == MMT_BF16) {
-    if (const int w2 = lean2d_width(p.pat, p.grid, desc->R, desc->D, dense)) {      // lean 2-D path: the kernels run at the narrowed table width
+    if (const int w2 = lean2d_width(p.pat, p.grid, desc->R, desc->D, dense, pack)) {      // lean 2-D path: the kernels run at the narrowed table width
       p.lean2d = 1;
       p.Rp = w2;
     }
@@ -411,13 +427,13 @@ int mmt_attn_bwd(const mmt_attn_desc* desc, const void* q, const void* k, const 
   // peeled global keys need clipped relative ids only: every peeled key lies beyond the radius, hence beyond max_dist
   p.peel_gkeys = (!dense && pl.split_rows && p.pat.ng <= 8 && (p.pat.id_mode == 0 || (p.perm_1d && p.pat.radius >= p.pat.m))) ? 3 : 0;
   if (!dense && pl.split_rows && p.pat.ng <= 8 && p.lean2d) p.peel_gkeys = 1;      // 2-D ids: the dQ pass's peeled step looks its columns up (the recomputing dK/dV pass keeps its tile visit)
-  if (p.grid.ga > 0 || p.D != 64) p.peel_gkeys = 0;                     // an image grid, head size 128: the general kernels, no peeled steps
+  if (p.grid.ga > 0 || p.D != 64 || pack) p.peel_gkeys = 0;             // an image grid, head size 128, packed examples: the general kernels, no peeled steps
   if (desc->tuning & MMT_TUNE_BWD_NO_PEEL_DQ) p.peel_gkeys &= ~1;       // bit 0: dQ pass, bit 1: dK/dV pass
   if (desc->tuning & MMT_TUNE_BWD_NO_PEEL_DKV) p.peel_gkeys &= ~2;
   p.dkv_slots = p.n_chunks;
   {   // P / dS hand-over: the dK/dV pass reads what the dQ pass computed (needs the peeled kind of global tokens, if any)
     const bool on = !(desc->tuning & MMT_TUNE_BWD_NO_HANDOVER);
-    const bool lean = desc->dtype == MMT_BF16 && !dense && p.grid.ga == 0 && p.D == 64 && (p.pat.id_mode == 0 || (p.perm_1d && p.Rp <= 64) || p.lean2d);
+    const bool lean = desc->dtype == MMT_BF16 && !dense && !pack && p.grid.ga == 0 && p.D == 64 && (p.pat.id_mode == 0 || (p.perm_1d && p.Rp <= 64) || p.lean2d);
     if (on && lean && pl.ho_slots > 0 && (p.pat.ng == 0 || !pl.split_rows || (p.peel_gkeys & 1))) {
       p.ho = reinterpret_cast<unsigned char*>(ws + pl.off_ho);
       p.ho_slots = pl.ho_slots;
@@ -428,7 +444,7 @@ int mmt_attn_bwd(const mmt_attn_desc* desc, const void* q, const void* k, const 
   if (const char* v = std::getenv("MMT_DBG_PTR")) p.dbg = reinterpret_cast<long long*>(std::strtoull(v, nullptr, 0));
   if (const char* v = std::getenv("MMT_DBG_MODE")) p.dbg_mode = std::atoi(v);
 #endif
-  hipError_t e = mmt::launch_attn_bwd(p, dense ? mmt::kDense : mmt::kBand, desc->dtype == MMT_BF16, st);
+  hipError_t e = mmt::launch_attn_bwd(p, dense ? mmt::kDense : mmt::kBand, desc->dtype == MMT_BF16, pack, st);
   if (e != hipSuccess) return fail(MMT_E_LAUNCH, "backward launch: %s", hipGetErrorString(e));
   return MMT_OK;
 }

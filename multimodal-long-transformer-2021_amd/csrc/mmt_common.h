@@ -109,6 +109,11 @@ __device__ __forceinline__ bool pattern_mask(const PatternDev& p, const GridDev&
   const bool near = abs(q - k) <= p.radius;
   return seg && (near || is_global(p, q) || is_global(p, k) || (GRID && in_grid(p, g, q, k)));
 }
+// Packed examples (MMT_FLAG_EXAMPLE_IDS): segmented(q,k) = example_ids[b,q] == example_ids[b,k], compared by the caller
+// (the reference's make_segmented_att_mask; any ids, no contiguity needed).  No grid term: a grid names one image per row.
+__device__ __forceinline__ bool pattern_mask_packed(const PatternDev& p, bool seg, int q, int k) {
+  return seg && (abs(q - k) <= p.radius || is_global(p, q) || is_global(p, k));
+}
 
 // ---------------------------------------------------------------------------------------
 // Dropout keep decision shared by forward and backward (and restated on the CPU in the

@@ -18,6 +18,7 @@ MMT_F32, MMT_BF16 = 0, 1
 MMT_IDS_NONE, MMT_IDS_1D, MMT_IDS_2D = 0, 1, 2
 MMT_FLAG_SCALE_BEFORE_ADD = 1
 MMT_FLAG_ACCUM_REL_GRADS = 2
+MMT_FLAG_EXAMPLE_IDS = 4      # mask.valid_len names int32 [B,S] example ids (packed rows) instead of [B] lengths
 
 
 def image_grid(radius: int, start: int) -> int:

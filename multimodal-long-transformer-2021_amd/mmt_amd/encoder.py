@@ -139,11 +139,12 @@ class MmtEncoder(nn.Module):
 
   def forward(self, word_ids, segment_ids=None, att_mask=None, relative_att_ids=None,
               patch_embeddings=None, training: Optional[bool] = None,
-              attention_pattern: Optional[AttentionPattern] = None, valid_len=None):
+              attention_pattern: Optional[AttentionPattern] = None, valid_len=None, example_ids=None):
     training = bool(training)
     emb = self.embed(word_ids, segment_ids, patch_embeddings, training).to(self.compute_dtype)
     out = self._transformer_layers(inputs=emb, att_mask=att_mask, relative_att_ids=relative_att_ids,
                                    training=training, pattern=attention_pattern, valid_len=valid_len,
+                                   example_ids=example_ids,
                                    dropout_seed=(fused.next_seed(0) >> 24) if training else 0)
     outputs = {'sequence_output': out}
     if hasattr(self, '_pooler_weight'):

@@ -54,6 +54,31 @@ def attention_pattern_from_config(data_cfg, encoder_cfg=None) -> AttentionPatter
       grid_radius=a, grid_start=2)                    # the patches sit behind [CLS][PATCH]
 
 
+def example_ids_from_breakpoints(long_breakpoints) -> torch.Tensor:
+  """Example ids of packed rows from their ending breakpoints (1 at the last position of every example, 0 elsewhere):
+  the reverse cumulative sum of `src/data/data_utils.py:321`, int32, same shape and device.  Positions of one example
+  share an id; ids fall along the row and the padding after the last breakpoint gets 0."""
+  bp = torch.as_tensor(long_breakpoints)
+  return torch.flip(torch.cumsum(torch.flip(bp.to(torch.int64), [-1]), -1), [-1]).to(torch.int32)
+
+
+def example_ids_from_lengths(lengths, S: int, device=None) -> torch.Tensor:
+  """int32 [B,S] example ids of rows packed with examples of the given lengths (one list of lengths per row): the ids
+  `example_ids_from_breakpoints` gives for breakpoints at the examples' last positions -- they fall from the row's
+  example count to 1, and the tail after the last example is 0."""
+  rows = []
+  for row in lengths:
+    row = [int(n) for n in row]
+    if any(n <= 0 for n in row) or sum(row) > S:
+      raise ValueError('example lengths must be positive and sum to at most S')
+    bp = torch.zeros(S, dtype=torch.int32)
+    if row:
+      bp[torch.cumsum(torch.tensor(row), 0) - 1] = 1
+    rows.append(bp)
+  ids = example_ids_from_breakpoints(torch.stack(rows))
+  return ids if device is None else ids.to(device)
+
+
 def synthetic_batch(data_cfg, batch_size: int, device, generator: Optional[torch.Generator] = None,
                     vocab_size: int = 30522, dense_side_inputs: bool = False,
                     ragged: bool = False, task: str = 'pretrain'):

@@ -38,11 +38,12 @@ class MmtPretrainingModel(nn.Module):
 
   def forward(self, word_ids, segment_ids=None, att_mask=None, relative_att_ids=None,
               patch_embeddings=None, mlm_positions=None, mpp_positions=None, training=None,
-              attention_pattern=None, valid_len=None):
+              attention_pattern=None, valid_len=None, example_ids=None):
     outputs = dict(self.encoder(word_ids=word_ids, segment_ids=segment_ids, att_mask=att_mask,
                                 relative_att_ids=relative_att_ids,
                                 patch_embeddings=patch_embeddings, training=training,
-                                attention_pattern=attention_pattern, valid_len=valid_len))
+                                attention_pattern=attention_pattern, valid_len=valid_len,
+                                example_ids=example_ids))
     seq = outputs['sequence_output']
     # every head reads a few rows of the sequence output: pick them with one merged gather
     B = seq.shape[0]
@@ -83,11 +84,12 @@ class MmtClassificationModel(nn.Module):
     _check_unique(self.classification_heads)
 
   def forward(self, word_ids, segment_ids=None, att_mask=None, relative_att_ids=None,
-              patch_embeddings=None, training=None, attention_pattern=None, valid_len=None):
+              patch_embeddings=None, training=None, attention_pattern=None, valid_len=None, example_ids=None):
     outputs = dict(self.encoder(word_ids=word_ids, segment_ids=segment_ids, att_mask=att_mask,
                                 relative_att_ids=relative_att_ids,
                                 patch_embeddings=patch_embeddings, training=training,
-                                attention_pattern=attention_pattern, valid_len=valid_len))
+                                attention_pattern=attention_pattern, valid_len=valid_len,
+                                example_ids=example_ids))
     for head in self.classification_heads:
       outputs[f'{head.name}_logits'] = head(outputs['sequence_output'], training=bool(training))
     return outputs

@@ -8,6 +8,11 @@ src/modeling/models/mmt_encoder.py:220-224; math SURVEY.md App. A.3).  Two input
               them (literal operator);
   * pattern : an `AttentionPattern` descriptor -- mask and ids are generated in-kernel and
               never materialised (the long-sequence fast path).
+
+The segmented term of a pattern comes from `valid_len` (int32 [B]: one example and a padding tail per row) or from
+`example_ids` (int32 [B,S]: packed rows, positions attend each other only inside one example -- the reference's
+`make_segmented_att_mask` over `cumsum(long_breakpoints, reverse=True)`, src/data/data_utils.py:305-332; see
+`input_utils.example_ids_from_breakpoints`).  The two are mutually exclusive.
 """
 from __future__ import annotations
 
@@ -98,22 +103,28 @@ def _index_list(idx: tuple, device) -> torch.Tensor:
 _DENSE_CACHE = {}
 
 
-def _materialized(pattern: 'AttentionPattern', valid_len, B: int, S: int, device):
-  """(att_mask, relative_att_ids) int32 [B,S,S] of a pattern with a listed global set, through `mmt_side_inputs`;
+def _materialized(pattern: 'AttentionPattern', valid_len, B: int, S: int, device, example_ids=None):
+  """(att_mask, relative_att_ids) int32 [B,S,S] of a pattern the structured kernels do not take (a listed global set;
+  with example ids also an image grid), through `mmt_side_inputs`;
   the last result is kept, so that the layers of one encoder pass (same pattern, same valid_len tensor) share it.
   The entry is tied to the valid_len tensor OBJECT (a weak reference + its version counter), never to its address:
   a later batch's tensor that the caching allocator places at the same address is a different object and misses;
-  when the tensor dies the entry (two B*S*S int32 tensors) is dropped with it."""
-  key = (pattern, B, S, str(device))
+  when the tensor dies the entry (two B*S*S int32 tensors) is dropped with it.
+  With `example_ids` the pattern mask is built without a length and `ids[:, :, None] == ids[:, None, :]` is ANDed into
+  it on the device; the entry is then tied to the ids tensor in the same way."""
+  packed = example_ids is not None
+  if packed:
+    valid_len = example_ids           # the tensor the entry is tied to
+  key = (pattern, B, S, str(device), packed)
   hit = _DENSE_CACHE.get('last')
   if hit is not None and hit[0] == key:
     ref, ver = hit[3]
     if (valid_len is None and ref is None) or (ref is not None and valid_len is not None and ref() is valid_len
                                                and ver == valid_len._version):
       return hit[1], hit[2]
-  if any(i >= S for i in pattern.global_index):
+  if pattern.global_index is not None and any(i >= S for i in pattern.global_index):
     raise ValueError('global_index position outside the sequence')
-  img = valid_len if valid_len is not None else torch.full((B,), S, dtype=torch.int32, device=device)
+  img = valid_len if (valid_len is not None and not packed) else torch.full((B,), S, dtype=torch.int32, device=device)
   txt = torch.zeros(B, dtype=torch.int32, device=device)
   mask = torch.empty((B, S, S), dtype=torch.int32, device=device)
   ids = torch.empty((B, S, S), dtype=torch.int32, device=device) if pattern.id_mode != _lib.MMT_IDS_NONE else None
@@ -121,6 +132,8 @@ def _materialized(pattern: 'AttentionPattern', valid_len, B: int, S: int, device
   with torch.cuda.device(device):
     _lib.check(_lib.lib().mmt_side_inputs(desc, B, S, img.data_ptr(), txt.data_ptr(), 1, mask.data_ptr(),
                                           None if ids is None else ids.data_ptr(), None, _stream_ptr(device)))
+  if packed:
+    mask &= (example_ids[:, :, None] == example_ids[:, None, :]).to(torch.int32)
   if valid_len is None:
     tie = (None, 0)
   else:
@@ -136,16 +149,20 @@ def clear_pattern_cache() -> None:
   _INDEX_LISTS.clear()
 
 
-def _resolve_pattern(pattern, att_mask, rel_ids, valid_len, q):
-  """Listed global sets: contiguous runs become the range form, anything else the dense operator's inputs."""
-  if pattern is None or pattern.global_index is None:
+def _resolve_pattern(pattern, att_mask, rel_ids, valid_len, q, example_ids=None):
+  """Listed global sets: contiguous runs become the range form, anything else the dense operator's inputs.  So does,
+  with example ids, a pattern with an image grid (the structured kernels refuse that pair)."""
+  if example_ids is not None and (att_mask is not None or rel_ids is not None):
+    raise ValueError('example_ids go with a pattern: dense att_mask/relative_att_ids already hold the segmented mask')
+  if pattern is None:
     return pattern, att_mask, rel_ids
-  pattern = pattern.normalized()
-  if pattern.global_index is None:
+  if pattern.global_index is not None:
+    pattern = pattern.normalized()
+  if pattern.global_index is None and not (example_ids is not None and pattern.grid_radius > 0):
     return pattern, att_mask, rel_ids
   if att_mask is not None or rel_ids is not None:
     raise ValueError('pass either dense att_mask/relative_att_ids or a pattern, not both')
-  mask, ids = _materialized(pattern, valid_len, q.shape[0], q.shape[1], q.device)
+  mask, ids = _materialized(pattern, valid_len, q.shape[0], q.shape[1], q.device, example_ids)
   return None, mask, ids
 
 
@@ -184,7 +201,7 @@ def _sync_words(device, stream_ptr: int, words: int) -> torch.Tensor:
 
 
 def _make_desc(q, k, v, out, R, pattern, valid_len, scale, mask_value, scale_before_add,
-               dropout_p, dropout_seed, tuning=0) -> _lib.AttnDesc:
+               dropout_p, dropout_seed, tuning=0, example_ids=None) -> _lib.AttnDesc:
   B, S, N, D = q.shape
   d = _lib.AttnDesc()
   d.B, d.S, d.N, d.D, d.R = B, S, N, D, R
@@ -197,6 +214,9 @@ def _make_desc(q, k, v, out, R, pattern, valid_len, scale, mask_value, scale_bef
   d.dropout_p = float(dropout_p)
   d.dropout_seed = (int(dropout_seed) + step_scalars.host_epoch(q.device)) & ((1 << 64) - 1)
   d.dropout_epoch = step_scalars.epoch_ptr(q.device) if dropout_p else None
+  if example_ids is not None:        # packed examples: the ids travel in the valid_len slot, named by the flag
+    d.flags |= _lib.MMT_FLAG_EXAMPLE_IDS
+    valid_len = example_ids
   d.mask = (pattern or AttentionPattern(id_mode=_lib.MMT_IDS_NONE)).to_desc(valid_len, q.device)
   d.tuning = int(tuning)
   sync = _sync_words(q.device, _stream_ptr(q.device), B * N)
@@ -204,7 +224,7 @@ def _make_desc(q, k, v, out, R, pattern, valid_len, scale, mask_value, scale_bef
   return d
 
 
-def _check_inputs(q, k, v, rel_emb, rel_bias, att_mask, rel_ids, valid_len):
+def _check_inputs(q, k, v, rel_emb, rel_bias, att_mask, rel_ids, valid_len, example_ids=None):
   if not q.is_cuda:
     raise RuntimeError('relative_attention runs on the GPU only (no CPU fallback)')
   for t in (k, v):
@@ -227,6 +247,12 @@ def _check_inputs(q, k, v, rel_emb, rel_bias, att_mask, rel_ids, valid_len):
   if valid_len is not None and (valid_len.dtype != torch.int32 or valid_len.shape != (B,)
                                 or not valid_len.is_contiguous()):
     raise ValueError('valid_len must be contiguous int32 [B]')
+  if example_ids is not None:
+    if valid_len is not None:
+      raise ValueError('pass valid_len or example_ids, not both (ids 1 on [0, vl) and 0 after are valid_len = vl)')
+    if (not torch.is_tensor(example_ids) or example_ids.dtype != torch.int32 or example_ids.shape != (B, S)
+        or not example_ids.is_contiguous() or example_ids.device != q.device):
+      raise ValueError('example_ids must be a contiguous int32 [B,S] tensor on the device of q')
   return R
 
 
@@ -234,11 +260,12 @@ def relative_attention_forward(q, k, v, rel_emb=None, rel_bias=None, *, att_mask
                                relative_att_ids=None, pattern: Optional[AttentionPattern] = None,
                                valid_len=None, scale=None, mask_value=-10000.0,
                                scale_before_add=False, dropout_p=0.0, dropout_seed=0,
-                               return_lse=True, tuning=0):
+                               return_lse=True, tuning=0, example_ids=None):
   """Forward only.  Returns (out [B,S,N,D] in q.dtype, lse fp32 [B,N,S]).  `tuning`: `_lib.MMT_TUNE_*` kernel-selection
-  switches (0 = the library's defaults; the parity tests use them to reach every kernel)."""
-  R = _check_inputs(q, k, v, rel_emb, rel_bias, att_mask, relative_att_ids, valid_len)
-  pattern, att_mask, relative_att_ids = _resolve_pattern(pattern, att_mask, relative_att_ids, valid_len, q)
+  switches (0 = the library's defaults; the parity tests use them to reach every kernel).  `example_ids`: contiguous
+  int32 [B,S] on the device of q, instead of `valid_len` (packed rows; module docstring)."""
+  R = _check_inputs(q, k, v, rel_emb, rel_bias, att_mask, relative_att_ids, valid_len, example_ids)
+  pattern, att_mask, relative_att_ids = _resolve_pattern(pattern, att_mask, relative_att_ids, valid_len, q, example_ids)
   dense = att_mask is not None or relative_att_ids is not None
   if dense and pattern is not None:
     raise ValueError('pass either dense att_mask/relative_att_ids or a pattern, not both')
@@ -246,7 +273,7 @@ def relative_attention_forward(q, k, v, rel_emb=None, rel_bias=None, *, att_mask
   out = torch.empty((B, S, N, D), dtype=q.dtype, device=q.device)
   lse = torch.empty((B, N, S), dtype=torch.float32, device=q.device) if return_lse else None
   desc = _make_desc(q, k, v, out, R, pattern, valid_len, scale, mask_value, scale_before_add,
-                    dropout_p, dropout_seed, tuning)
+                    dropout_p, dropout_seed, tuning, None if dense else example_ids)
   L = _lib.lib()
   ws_bytes = 0 if dense else L.mmt_workspace_bytes(desc)
   ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=q.device)
@@ -288,7 +315,7 @@ def relative_attention_backward(dout, q, k, v, rel_emb, rel_bias, out, lse, *, a
                                 relative_att_ids=None, pattern: Optional[AttentionPattern] = None,
                                 valid_len=None, scale=None, mask_value=-10000.0,
                                 scale_before_add=False, dropout_p=0.0, dropout_seed=0, grads_out=None,
-                                rel_grads_accum=None, tuning=0):
+                                rel_grads_accum=None, tuning=0, example_ids=None):
   """Backward of `relative_attention_forward` (recomputes P from `lse`).
 
   Returns (dq, dk, dv, drel_emb, drel_bias); the table gradients are fp32.  `grads_out` may
@@ -296,8 +323,10 @@ def relative_attention_backward(dout, q, k, v, rel_emb, rel_bias, out, lse, *, a
   fused [B,S,3,N,D] gradient buffer.  `rel_grads_accum` = (demb [R,N,D], dbias [R,N] | None), fp32
   and contiguous: the table gradients are ADDED to these buffers (the fp32 master gradients) and
   returned as such."""
-  R = _check_inputs(q, k, v, rel_emb, rel_bias, att_mask, relative_att_ids, valid_len)
-  pattern, att_mask, relative_att_ids = _resolve_pattern(pattern, att_mask, relative_att_ids, valid_len, q)
+  R = _check_inputs(q, k, v, rel_emb, rel_bias, att_mask, relative_att_ids, valid_len, example_ids)
+  pattern, att_mask, relative_att_ids = _resolve_pattern(pattern, att_mask, relative_att_ids, valid_len, q, example_ids)
+  if att_mask is not None or relative_att_ids is not None:
+    example_ids = None              # the dense operator: the materialised mask holds the ids' term
   B, S, N, D = q.shape
   dout = dout if dout.stride() == out.stride() else dout.contiguous()
   if out.stride() != dout.stride():
@@ -310,7 +339,7 @@ def relative_attention_backward(dout, q, k, v, rel_emb, rel_bias, out, lse, *, a
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
     dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
   desc = _make_desc(q, k, v, out, R, pattern, valid_len, scale, mask_value, scale_before_add,
-                    dropout_p, dropout_seed, tuning)
+                    dropout_p, dropout_seed, tuning, example_ids)
   if rel_grads_accum is not None and R:
     drel_emb, drel_bias = rel_grads_accum
     for t, shape in ((drel_emb, (R, N, D)), (drel_bias, (R, N))):
@@ -356,7 +385,7 @@ class _RelativeAttentionFn(torch.autograd.Function):
 
 def relative_attention(q, k, v, rel_emb=None, rel_bias=None, **kw):
   """Differentiable QkvRelativeAttention (see module docstring); kwargs as
-  `relative_attention_forward` (att_mask / relative_att_ids or pattern / valid_len, scale,
+  `relative_attention_forward` (att_mask / relative_att_ids or pattern / valid_len or example_ids, scale,
   mask_value, scale_before_add, dropout_p, dropout_seed)."""
   kw.pop('return_lse', None)
   return _RelativeAttentionFn.apply(q, k, v, rel_emb, rel_bias, kw)

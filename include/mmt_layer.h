@@ -292,6 +292,38 @@ int mmt_ffn_gelu_gemm(const void* x, int64_t ldx, const void* w, int64_t ldw, co
 int mmt_ffn_dgelu_gemm(const void* dy, int64_t lddy, const void* w, int64_t ldw, const void* u, int64_t ldu,
                        const float* bias, void* du, int64_t lddu, int64_t M, int64_t N, int64_t K, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Image front end of the data layer: decoded uint8 RGB images of mixed sizes -> patch features, in one launch
+ * (csrc/image_patches.hip).  The tensor half of the reference's `decode_fn` (src/data/data_utils.py:195-222):
+ *   x = u8 / 255;   r = bilinear resize of x to image_size x image_size with tf.image.resize's TF2 defaults
+ *   (half-pixel centres, no antialiasing, 2x2 taps:  src = (dst + 0.5) * in / out - 0.5,  lo = max(floor(src), 0),
+ *   hi = min(ceil(src), in - 1),  t = src - floor(src);  horizontal lerp, then vertical);
+ *   unnormalised = r;   normalised = (r - mean) / mean   (the reference's line 204 divides by the MEAN);
+ *   flip[b] != 0: both outputs take column image_size - 1 - x (after the resize, :209-211);
+ *   patches: P = image_size / patch_size, the remainder rows / columns dropped (VALID), raster order over patches,
+ *   (row, column, channel) inside one: outputs are [B, P*P, patch_size^2 * 3];
+ *   label ids [B, P*P] (masked-patch prediction, :448-481): the channel means of the unnormalised patch, times 255,
+ *   in 2^channel_bits equal bins, combined as digits of base 2^channel_bits with channel 0 the least significant.
+ * Example b is heights[b] x widths[b] x 3 bytes, row-major, starting at pixels + offsets[b].  pixels, offsets (int64
+ * [B]), heights, widths (int32 [B]) and flip (uint8 [B], or NULL: no flip) are DEVICE memory, so the call can be
+ * recorded into a graph.  normalised_out is `out_dtype`; unnormalised_out (fp32) and label_ids_out may each be NULL
+ * and are then not computed; ids also need channel_bits > 0.  Ids are summed in a fixed order (no atomics): bitwise
+ * reproducible.  The kernel never reads outside [pixels, pixels + pixels_bytes): taps are clamped to the image,
+ * heights / widths below 1 count as 1, offsets and every byte address are clamped into the buffer -- wrong metadata
+ * gives wrong pixels, not a fault.  B * P * P and patch_size^2 * 3 must each stay below 2^31. */
+typedef struct mmt_image_desc {
+  int32_t B;             /* examples                                                     */
+  int32_t image_size;    /* output height = width                                        */
+  int32_t patch_size;    /* <= image_size                                                */
+  int32_t out_dtype;     /* MMT_F32 | MMT_BF16: normalised_out                           */
+  int32_t channel_bits;  /* 1..8: bits per channel of the label ids; 0: no ids           */
+  float mean[3];         /* per channel, non-zero; (0.485, 0.456, 0.406) in the reference */
+} mmt_image_desc;
+
+int mmt_image_patches(const mmt_image_desc* desc, const uint8_t* pixels, int64_t pixels_bytes, const int64_t* offsets,
+                      const int32_t* heights, const int32_t* widths, const uint8_t* flip, void* normalised_out,
+                      float* unnormalised_out, int32_t* label_ids_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

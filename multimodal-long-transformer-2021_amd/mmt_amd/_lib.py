@@ -43,7 +43,8 @@ EXPORTS = ('mmt_abi_version', 'mmt_last_error', 'mmt_write_step_scalars', 'mmt_w
            'mmt_layer_workspace_bytes', 'mmt_ln_fwd', 'mmt_ln_bwd', 'mmt_residual_block_fwd',
            'mmt_residual_block_bwd', 'mmt_bias_gelu_fwd', 'mmt_bias_gelu_bwd', 'mmt_colsum_reduce', 'mmt_colsum_reduce_batch', 'mmt_accumulate_grad', 'mmt_grad_clip_scale', 'mmt_adamw_step', 'mmt_wgrad_accumulate',
            'mmt_wgrad_bias_accumulate', 'mmt_wgrad_grouped', 'mmt_wgrad_group_workspace_bytes', 'mmt_wgrad_workspace_bytes', 'mmt_wgrad_set_cu_budget', 'mmt_embed_fwd', 'mmt_embed_bwd',
-           'mmt_embed_workspace_bytes', 'mmt_xent_fwd', 'mmt_xent_fwd_argmax', 'mmt_xent_bwd', 'mmt_xent_bwd_scaled', 'mmt_weighted_loss', 'mmt_colsum', 'mmt_colsum_workspace_bytes', 'mmt_ln_bwd_add', 'mmt_ffn_gelu_gemm', 'mmt_ffn_dgelu_gemm', 'mmt_ffn_set_cu_budget')
+           'mmt_embed_workspace_bytes', 'mmt_xent_fwd', 'mmt_xent_fwd_argmax', 'mmt_xent_bwd', 'mmt_xent_bwd_scaled', 'mmt_weighted_loss', 'mmt_colsum', 'mmt_colsum_workspace_bytes', 'mmt_ln_bwd_add', 'mmt_ffn_gelu_gemm', 'mmt_ffn_dgelu_gemm', 'mmt_ffn_set_cu_budget',
+           'mmt_image_patches')
 
 
 class EmbedDesc(ctypes.Structure):
@@ -85,6 +86,11 @@ class AdamwDesc(ctypes.Structure):
               ('beta2', ctypes.c_float), ('eps', ctypes.c_float), ('bias_correction1', ctypes.c_float),
               ('bias_correction2', ctypes.c_float), ('zero_grad', ctypes.c_int32),
               ('reserved', ctypes.c_int32), ('hyper', ctypes.c_void_p)]
+
+
+class ImageDesc(ctypes.Structure):
+  _fields_ = [('B', ctypes.c_int32), ('image_size', ctypes.c_int32), ('patch_size', ctypes.c_int32),
+              ('out_dtype', ctypes.c_int32), ('channel_bits', ctypes.c_int32), ('mean', ctypes.c_float * 3)]
 
 
 class WgradProblem(ctypes.Structure):
@@ -217,6 +223,8 @@ def lib() -> ctypes.CDLL:
                                     ctypes.c_float, vp, vp, vp, ctypes.c_size_t, vp]
   L.mmt_accumulate_grad.restype = ctypes.c_int
   L.mmt_accumulate_grad.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int64, vp]
+  L.mmt_image_patches.restype = ctypes.c_int
+  L.mmt_image_patches.argtypes = [ctypes.POINTER(ImageDesc), vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
   L.mmt_write_step_scalars.restype = ctypes.c_int
   L.mmt_write_step_scalars.argtypes = [vp, vp, ctypes.c_uint64, ctypes.c_float, ctypes.c_float, ctypes.c_float, vp]
   if L.mmt_abi_version() != MMT_ABI_VERSION:

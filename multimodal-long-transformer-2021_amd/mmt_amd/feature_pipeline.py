@@ -2,6 +2,8 @@
 tensor transforms the reference runs inside tf.data on the host, as batched torch ops on the GPU
 (integer / byte work: gathers, reshapes, bucketize -- nothing here is a GEMM).
 
+  images_to_patch_features   src/data/data_utils.py:195-222  (decoded uint8 images of mixed sizes: /255, bilinear resize,
+                                                              (im - MEAN) / MEAN, flip, patches, MPP colour ids -- one HIP kernel)
   convert_image_to_patches   src/data/data_utils.py:147-180  (tf.image.extract_patches 16x16 VALID + raster order)
   make_mpp_label_ids         src/data/data_utils.py:448-481  (mean colour per channel -> 2^bits bins -> base-2^bits id)
   make_matching_features     src/data/data_utils.py:642-712  (in-batch negatives for ITM: tile images, roll texts)
@@ -12,6 +14,8 @@ from __future__ import annotations
 from typing import Dict
 
 import torch
+
+IMAGENET_DEFAULT_MEAN = (0.485, 0.456, 0.406)    # src/data/data_utils.py: the reference's normalisation constant
 
 
 def convert_image_to_patches(images: torch.Tensor, patch_size: int) -> torch.Tensor:
@@ -41,6 +45,146 @@ def make_mpp_label_ids(mpp_embeddings: torch.Tensor, patch_size: int, channels: 
   digit = torch.bucketize(avg, bins, right=True)             # boundaries[i-1] <= x < boundaries[i]
   weight = (2 ** output_channel_bits) ** torch.arange(channels, device=avg.device)
   return (digit * weight).sum(-1).to(torch.int32)
+
+
+# ---------------------------------------------------------------------------------------------------
+# Image front end (`decode_fn`, src/data/data_utils.py:195-222): decoded uint8 images -> patch features.
+# ---------------------------------------------------------------------------------------------------
+def _resize_axis(n_in: int, n_out: int, device):
+  """Taps of tf.image.resize (TF2 defaults: half-pixel centres, no antialiasing) on one axis:
+  src = (dst + 0.5) * in / out - 0.5, lo = max(floor(src), 0), hi = min(ceil(src), in - 1), t = src - floor(src).
+  The coordinate is formed in float64, as the kernel does, so that t carries one float32 rounding only."""
+  src = (torch.arange(n_out, dtype=torch.float64, device=device) + 0.5) * (float(n_in) / float(n_out)) - 0.5
+  fl = torch.floor(src)
+  lo = fl.clamp(min=0).to(torch.int64)
+  hi = torch.ceil(src).clamp(max=n_in - 1).to(torch.int64)
+  return lo, hi, (src - fl).to(torch.float32)
+
+
+def _resize_bilinear_u8(image: torch.Tensor, size: int) -> torch.Tensor:
+  """uint8 [h, w, 3] -> float32 [size, size, 3] in [0, 1]: /255 (tf.io.decode_image(dtype=float32)), then the 2x2-tap
+  bilinear resize, horizontal lerp first."""
+  x = image.to(torch.float32) / 255.0
+  y0, y1, ty = _resize_axis(image.shape[0], size, image.device)
+  x0, x1, tx = _resize_axis(image.shape[1], size, image.device)
+  tx, ty = tx[None, :, None], ty[:, None, None]
+  top_rows, bot_rows = x[y0], x[y1]
+  top = top_rows[:, x0] + (top_rows[:, x1] - top_rows[:, x0]) * tx
+  bot = bot_rows[:, x0] + (bot_rows[:, x1] - bot_rows[:, x0]) * tx
+  return top + (bot - top) * ty
+
+
+def _pack_images(images):
+  """list of uint8 [h, w, 3] tensors -> (pixels [sum h*w*3] uint8, offsets int64 [B], heights, widths int32 [B])."""
+  if len(images) == 0:
+    raise ValueError('images is empty')
+  dev = images[0].device
+  hs, ws, offs, n = [], [], [], 0
+  for i, im in enumerate(images):
+    if not isinstance(im, torch.Tensor) or im.dtype != torch.uint8:
+      raise ValueError(f'images[{i}] must be a uint8 tensor (decoded pixels)')
+    if im.dim() != 3 or im.shape[2] != 3:
+      raise ValueError(f'images[{i}] must be [height, width, 3], got {tuple(im.shape)}')
+    if im.shape[0] < 1 or im.shape[1] < 1:
+      raise ValueError(f'images[{i}] is empty: {tuple(im.shape)}')
+    if im.device != dev:
+      raise ValueError('all images must live on one device')
+    hs.append(im.shape[0]); ws.append(im.shape[1]); offs.append(n)
+    n += im.numel()
+  pixels = torch.cat([im.reshape(-1) for im in images])
+  meta = lambda v, dt: torch.tensor(v, dtype=dt).to(dev)
+  return pixels, meta(offs, torch.int64), meta(hs, torch.int32), meta(ws, torch.int32)
+
+
+def _check_packed(packed):
+  if len(packed) != 4:
+    raise ValueError('packed images are a (pixels, offsets, heights, widths) tuple')
+  pixels, offsets, heights, widths = packed
+  if pixels.dtype != torch.uint8 or pixels.dim() != 1 or pixels.numel() < 1:
+    raise ValueError('pixels must be a non-empty 1-D uint8 tensor')
+  B = offsets.shape[0] if offsets.dim() == 1 else -1
+  if B < 1 or offsets.dtype != torch.int64:
+    raise ValueError('offsets must be int64 [B], B >= 1')
+  for name, t in (('heights', heights), ('widths', widths)):
+    if t.dtype != torch.int32 or t.shape != (B,):
+      raise ValueError(f'{name} must be int32 [B]')
+  if any(t.device != pixels.device for t in (offsets, heights, widths)):
+    raise ValueError('pixels, offsets, heights and widths must live on one device')
+  if not pixels.is_cuda:         # on the device the values are not read back: the kernel clamps them (include/mmt_layer.h)
+    if int(heights.min()) < 1 or int(widths.min()) < 1:
+      raise ValueError('heights and widths must be positive')
+    end = offsets + heights.to(torch.int64) * widths.to(torch.int64) * 3
+    if int(offsets.min()) < 0 or int(end.max()) > pixels.numel():
+      raise ValueError('an image leaves the pixel buffer')
+  return pixels.contiguous(), offsets.contiguous(), heights.contiguous(), widths.contiguous()
+
+
+def images_to_patch_features(images, image_size: int, patch_size: int, *, flip: torch.Tensor = None,
+                             out_dtype: torch.dtype = torch.float32, keep_unnormalized: bool = False,
+                             output_channel_bits: int = 0, mean=IMAGENET_DEFAULT_MEAN) -> Dict[str, torch.Tensor]:
+  """The tensor half of `decode_fn` (src/data/data_utils.py:195-222) for a batch of decoded RGB images of any sizes.
+
+  images: list of uint8 [h, w, 3] tensors, or an already packed (pixels uint8 [n], offsets int64 [B], heights int32
+  [B], widths int32 [B]) tuple (example b is heights[b] x widths[b] x 3 bytes, row-major, from pixels[offsets[b]]).
+  Per example: x = u8 / 255; bilinear resize to image_size x image_size (tf.image.resize, TF2 defaults);
+  patch_embeddings from (r - mean) / mean -- the reference's line 204 divides by the MEAN -- and
+  unnormalized_patch_embeddings from r; flip [B] (bool / uint8; the reference's training-time coin, :209-211, as an
+  explicit input) mirrors both left-right after the resize; patches as `convert_image_to_patches`; mpp_label_ids as
+  `make_mpp_label_ids(unnormalized, patch_size, 3, output_channel_bits)` (0: none).
+  Returns patch_embeddings [B, P*P, patch_size^2 * 3] in `out_dtype` (float32 | bfloat16), num_image_wordpieces
+  (2 + P*P: [CLS], [PATCH] and the patches, :239) and, when asked for, unnormalized_patch_embeddings (float32) and
+  mpp_label_ids [B, P*P] int32.  On the GPU all of it is one launch of mmt_image_patches; CPU tensors go through the
+  same arithmetic in torch ops."""
+  image_size, patch_size, bits = int(image_size), int(patch_size), int(output_channel_bits)
+  if image_size < 1 or patch_size < 1:
+    raise ValueError('image_size and patch_size must be positive')
+  if patch_size > image_size:
+    raise ValueError(f'patch_size {patch_size} exceeds image_size {image_size}: no whole patch')
+  if out_dtype not in (torch.float32, torch.bfloat16):
+    raise ValueError(f'out_dtype must be float32 or bfloat16, got {out_dtype}')
+  if not 0 <= bits <= 8:
+    raise ValueError('output_channel_bits must be in [0, 8]')
+  if len(mean) != 3 or any(float(m) == 0.0 for m in mean):
+    raise ValueError('mean must be three non-zero numbers')
+  pixels, offsets, heights, widths = _check_packed(images) if isinstance(images, tuple) else _pack_images(list(images))
+  B, dev = offsets.shape[0], pixels.device
+  if flip is not None:
+    if flip.shape != (B,) or flip.dtype not in (torch.bool, torch.uint8) or flip.device != dev:
+      raise ValueError('flip must be a bool or uint8 [B] tensor on the images\' device')
+    flip = flip.to(torch.uint8).contiguous()
+  P = image_size // patch_size
+  E = patch_size * patch_size * 3
+  out = {'num_image_wordpieces': 2 + P * P}
+  if pixels.is_cuda:
+    from . import _lib
+    d = _lib.ImageDesc()
+    d.B, d.image_size, d.patch_size, d.channel_bits = B, image_size, patch_size, bits
+    d.out_dtype = _lib.MMT_F32 if out_dtype == torch.float32 else _lib.MMT_BF16
+    d.mean[:] = [float(m) for m in mean]
+    norm = torch.empty(B, P * P, E, dtype=out_dtype, device=dev)
+    unnorm = torch.empty(B, P * P, E, dtype=torch.float32, device=dev) if keep_unnormalized else None
+    ids = torch.empty(B, P * P, dtype=torch.int32, device=dev) if bits else None
+    ptr = lambda t: None if t is None else t.data_ptr()
+    _lib.check(_lib.lib().mmt_image_patches(d, pixels.data_ptr(), pixels.numel(), offsets.data_ptr(), heights.data_ptr(),
+                                            widths.data_ptr(), ptr(flip), norm.data_ptr(), ptr(unnorm), ptr(ids),
+                                            torch.cuda.current_stream(dev).cuda_stream))
+  else:
+    rows = []
+    for b in range(B):
+      h, w, o = int(heights[b]), int(widths[b]), int(offsets[b])
+      r = _resize_bilinear_u8(pixels[o:o + h * w * 3].reshape(h, w, 3), image_size)
+      rows.append(torch.flip(r, dims=(1,)) if flip is not None and bool(flip[b]) else r)
+    r = convert_image_to_patches(torch.stack(rows), patch_size)
+    m = torch.tensor([float(v) for v in mean], dtype=torch.float32).repeat(patch_size * patch_size)
+    norm = ((r - m) / m).to(out_dtype)
+    unnorm = r if keep_unnormalized else None
+    ids = make_mpp_label_ids(r, patch_size, 3, bits) if bits else None
+  out['patch_embeddings'] = norm
+  if keep_unnormalized:
+    out['unnormalized_patch_embeddings'] = unnorm
+  if bits:
+    out['mpp_label_ids'] = ids
+  return out
 
 
 def make_matching_features(features: Dict[str, torch.Tensor], image_keys: torch.Tensor,

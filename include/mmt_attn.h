@@ -111,7 +111,11 @@ typedef struct mmt_mask_desc {
                                is ignored).  ABI 2.                                     */
 } mmt_mask_desc;
 
-/* One attention call: q,k,v,out are [B,S,N,D] views with element strides (D contiguous). */
+/* One attention call: q,k,v,out are [B,S,N,D] views with element strides (D contiguous).  Strides are non-negative
+ * multiples of 16 bytes (8 bf16 / 4 fp32 elements; 0 = broadcast, inputs only).  32 * ceil(S / 32) * stride_s must stay
+ * below 2^31 elements (MMT_E_UNSUPPORTED otherwise): the kernels address the rows of whole 32-row tiles with 32-bit byte
+ * offsets.  Batch and head strides have no such limit.  Rows S .. 32 * ceil(S / 32) - 1 of a plane are never written;
+ * they may be read (and ignored) where they lie inside the caller's allocation. */
 typedef struct mmt_attn_desc {
   int32_t B, S, N, D;   /* D must be 64 or 128 (128: the general kernels only)         */
   int32_t R;            /* rows of relative_emb_table (relative_vocab_size); 0 = none; at most 128 (above 64: the general kernels) */

@@ -84,8 +84,13 @@ int check_desc(const mmt_attn_desc* d) {
   for (int t = 0; t < 4; ++t)
     for (int i = 0; i < 3; ++i)
       if (st[t][i] < 0 || st[t][i] % align) return fail(MMT_E_INVALID, "strides must be non-negative multiples of %d elements", align);
+  // The lean kernels load whole 32-row tiles through buffer descriptors with 32-bit BYTE offsets (row * stride_s * 2) and
+  // leave the rows past S to the descriptor's range check: the offsets of the last tile's tail rows must not wrap round
+  // 2^32 (they would land inside the buffer again and read whatever lies between two rows), so S counts in whole tiles.
+  const int64_t tile_rows = ((int64_t)d->S + 31) / 32 * 32;
   for (int t = 0; t < 4; ++t)
-    if ((int64_t)d->S * st[t][1] >= (int64_t)1 << 31) return fail(MMT_E_UNSUPPORTED, "S * stride_s must stay below 2^31 elements");
+    if (tile_rows * st[t][1] >= (int64_t)1 << 31)
+      return fail(MMT_E_UNSUPPORTED, "S * stride_s must stay below 2^31 elements (S rounded up to a multiple of 32)");
   if (!(d->dropout_p >= 0.f && d->dropout_p < 1.f)) return fail(MMT_E_INVALID, "dropout_p must be in [0,1)");
   const mmt_mask_desc& m = d->mask;
   if (m.local_radius < 0) return fail(MMT_E_INVALID, "local_radius must be >= 0");

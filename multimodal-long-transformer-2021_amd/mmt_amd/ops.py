@@ -320,7 +320,8 @@ def relative_attention_backward(dout, q, k, v, rel_emb, rel_bias, out, lse, *, a
 
   Returns (dq, dk, dv, drel_emb, drel_bias); the table gradients are fp32.  `grads_out` may
   give preallocated (dq, dk, dv) with the strides of (q, k, v) -- e.g. the three slices of one
-  fused [B,S,3,N,D] gradient buffer.  `rel_grads_accum` = (demb [R,N,D], dbias [R,N] | None), fp32
+  fused [B,S,3,N,D] gradient buffer; they are written in place, and buffers of other strides raise
+  ValueError.  `rel_grads_accum` = (demb [R,N,D], dbias [R,N] | None), fp32
   and contiguous: the table gradients are ADDED to these buffers (the fp32 master gradients) and
   returned as such."""
   R = _check_inputs(q, k, v, rel_emb, rel_bias, att_mask, relative_att_ids, valid_len, example_ids)
@@ -333,11 +334,15 @@ def relative_attention_backward(dout, q, k, v, rel_emb, rel_bias, out, lse, *, a
     out = out.contiguous()
   if grads_out is not None:
     dq, dk, dv = grads_out
+    for g, t in ((dq, q), (dk, k), (dv, v)):       # the caller's buffers are written or the call fails: never replaced
+      if g.shape != t.shape or g.dtype != t.dtype or g.device != t.device or g.stride() != t.stride():
+        raise ValueError('grads_out must be (dq, dk, dv) with the shape, dtype, device and strides of (q, k, v)')
   else:
     dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-  if dq.stride() != q.stride() or dk.stride() != k.stride() or dv.stride() != v.stride():
-    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    if dq.stride() != q.stride() or dk.stride() != k.stride() or dv.stride() != v.stride():
+      # views that are not dense (fused-qkv slices, padded rows, expanded operands): gradients of their own layout
+      q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+      dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
   desc = _make_desc(q, k, v, out, R, pattern, valid_len, scale, mask_value, scale_before_add,
                     dropout_p, dropout_seed, tuning, example_ids)
   if rel_grads_accum is not None and R:

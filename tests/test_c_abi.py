@@ -147,6 +147,93 @@ def test_argument_errors_without_gpu(lib):
   assert b'`num_patch_per_row` must be positive.' in L.mmt_last_error()
 
 
+def _stride_desc(lib, dtype, S=64, N=2, D=64):
+  """A valid structured descriptor on contiguous [1,S,N,D] operands (no pointer is followed: the checks are host code)."""
+  d = lib.AttnDesc()
+  d.B, d.S, d.N, d.D, d.R, d.dtype = 1, S, N, D, 0, dtype
+  for arr in (d.q_stride, d.k_stride, d.v_stride, d.o_stride):
+    arr[:] = (S * N * D, N * D, D)
+  d.scale, d.mask_value = 0.125, -10000.0
+  d.mask.local_radius = 8
+  return d
+
+
+def _refused(lib, d, code, message):
+  L = lib.lib()
+  assert L.mmt_workspace_bytes(d) == 0 and message in L.mmt_last_error(), L.mmt_last_error()
+  assert L.mmt_attn_fwd(d, 1, 1, 1, None, None, None, None, 1, None, None, 0, None) == code
+  assert message in L.mmt_last_error(), L.mmt_last_error()
+
+
+STRIDE_ARRAYS = ('q_stride', 'k_stride', 'v_stride', 'o_stride')
+
+
+@pytest.mark.parametrize('which', STRIDE_ARRAYS)
+def test_row_stride_limit_is_refused_at_2_31_elements_and_accepted_just_below(lib, which):
+  """include/mmt_attn.h: 32 * ceil(S / 32) * stride_s must stay below 2^31 elements, for each of q, k, v and out (the
+  kernels address whole 32-row tiles with 32-bit byte offsets; until this bound counted S in whole tiles the tail rows
+  of the last tile wrapped round 2^32 and read the gaps between the first rows).  Refused: MMT_E_UNSUPPORTED and the
+  standing message; accepted: 2^31 - stride_s exactly where S is a tile multiple, one alignment unit below the bound
+  where it is not."""
+  L = lib.lib()
+  message = b'S * stride_s must stay below 2^31 elements'
+
+  def accepted(d):
+    assert L.mmt_workspace_bytes(d) > 0, L.mmt_last_error()
+    # the forward takes the descriptor and goes on to its next check (q is NULL)
+    assert L.mmt_attn_fwd(d, None, None, None, None, None, None, None, None, None, None, 0, None) == -1
+    assert b'must not be NULL' in L.mmt_last_error()
+
+  for dtype in (lib.MMT_F32, lib.MMT_BF16):
+    # S a tile multiple: S * stride_s == 2^31 refused, 2^31 - stride_s accepted
+    for S, stride_s in ((1024, 1 << 21), (64, 1 << 25), (32, 1 << 26)):
+      d = _stride_desc(lib, dtype, S=S)
+      getattr(d, which)[1] = stride_s
+      _refused(lib, d, -2, message)
+      getattr(d, which)[1] = stride_s - 8
+      accepted(d)
+    d = _stride_desc(lib, dtype, S=1024 - 32)
+    getattr(d, which)[1] = 1 << 21
+    assert d.S * (1 << 21) == (1 << 31) - 32 * (1 << 21)
+    accepted(d)
+    # S = 1000 counts as 1024 rows: the documented product S * stride_s alone no longer decides
+    d = _stride_desc(lib, dtype, S=1000)
+    getattr(d, which)[1] = 2147480                      # S * stride_s = 2 147 480 000 < 2^31, 1024 * stride_s is not
+    _refused(lib, d, -2, message)
+    getattr(d, which)[1] = 1 << 21                      # 1024 * 2^21 == 2^31
+    _refused(lib, d, -2, message)
+    getattr(d, which)[1] = (1 << 21) - 8                # one alignment unit less: 2 147 475 456
+    accepted(d)
+    for S in (993, 1023):                               # every length of that last tile has the same bound
+      d = _stride_desc(lib, dtype, S=S)
+      getattr(d, which)[1] = 1 << 21
+      _refused(lib, d, -2, message)
+      getattr(d, which)[1] = (1 << 21) - 8
+      accepted(d)
+  # batch and head strides carry no such limit (64-bit plane offsets)
+  d = _stride_desc(lib, lib.MMT_BF16)
+  getattr(d, which)[0] = (1 << 31) + 64
+  getattr(d, which)[2] = (1 << 33) + 8
+  assert L.mmt_workspace_bytes(d) > 0, L.mmt_last_error()
+
+
+@pytest.mark.parametrize('pos', [0, 1, 2], ids=['b', 's', 'n'])
+@pytest.mark.parametrize('which', STRIDE_ARRAYS)
+def test_negative_and_misaligned_strides_are_refused(lib, which, pos):
+  """Strides are non-negative multiples of 16 bytes (8 bf16 / 4 fp32 elements), in each of the three positions."""
+  L = lib.lib()
+  for dtype, unit in ((lib.MMT_F32, 4), (lib.MMT_BF16, 8)):
+    message = b'strides must be non-negative multiples of %d elements' % unit
+    d = _stride_desc(lib, dtype)
+    good = getattr(d, which)[pos]
+    for bad in (-unit, -good, good + 1, good + unit // 2, good - 1, unit - 1):
+      getattr(d, which)[pos] = bad
+      _refused(lib, d, -1, message)
+    for fine in (good + unit, 0):                       # the unit itself and a broadcast (zero) stride pass
+      getattr(d, which)[pos] = fine
+      assert L.mmt_workspace_bytes(d) > 0, (fine, L.mmt_last_error())
+
+
 def test_no_cpu_fallback(lib):
   import torch
   import mmt_amd

@@ -31,7 +31,7 @@ for name in ('token-major (fused qkv buffer)', 'token-major (separate)', 'head-m
   else:
     q, k, v, dout = (torch.randn(B, N, S, 64, device='cuda', dtype=dt).permute(0, 2, 1, 3) for _ in range(4))
   out, lse = mmt_amd.relative_attention_forward(q, k, v, emb, bias, **kw)
-  go = (torch.empty_like(q), torch.empty_like(k), torch.empty_like(v))
+  go = tuple(torch.empty_strided(t.shape, t.stride(), dtype=dt, device='cuda') for t in (q, k, v))   # grads_out: the strides of q, k, v
   f = timeit(lambda: mmt_amd.relative_attention_forward(q, k, v, emb, bias, **kw))
   dout = dout if dout.stride() == out.stride() else dout.contiguous().as_strided(out.shape, out.stride())
   b = timeit(lambda: mmt_amd.relative_attention_backward(dout, q, k, v, emb, bias, out, lse, grads_out=go, **kw), 50)

@@ -62,6 +62,15 @@ enum {
                                         ignored like the rest of desc->mask); the general kernels; refused with an image grid (it
                                         names one image per row) and, as ever, with a listed global set.  Relative ids are
                                         untouched: they do not depend on the mask.  ids = 1 on [0, vl), 0 after, is valid_len = vl. */
+#define MMT_FLAG_EXAMPLE_STARTS 8u   /* packed MULTIMODAL examples, with MMT_FLAG_EXAMPLE_IDS only: mask.valid_len names int32 [B,2,S],
+                                        plane 0 the example ids, plane 1 start[b,x] = the first position of the example x belongs
+                                        to.  Every position-dependent term but the band then reads positions local to their example,
+                                        lq = q - start[b,q], lk = k - start[b,k] (clamped into [0, S): garbage starts give wrong
+                                        numbers, never a stray access): rel_id(lq, lk), grid(lq, lk) -- an example sees what it would
+                                        see alone at the start of a row.  Every run of equal ids is an example, a padding tail too;
+                                        an id must name ONE run of its row (two runs sharing an id are undefined with starts).
+                                        Takes an image grid; n_global > 0 is MMT_E_UNSUPPORTED (per-example global tokens: dense
+                                        operator).  The general kernels; without the flag every call is what it was. */
 
 /* Kernel-selection switches (mmt_attn_desc.tuning; ABI 4).  0 = the library's defaults.  They choose between kernels
  * that compute the same result (parity tests flip them to reach every kernel; they replace the MMT_* environment
@@ -83,6 +92,9 @@ enum {
  *   or, with MMT_FLAG_EXAMPLE_IDS in mmt_attn_desc.flags (packed examples): example_ids[b,q] == example_ids[b,k]
  * otherwise (build-defined):
  *   mask(q,k) = segmented(q,k) && (|q-k| <= local_radius || global(q) || global(k) || grid(q,k)),
+ *   with MMT_FLAG_EXAMPLE_STARTS (lq = q - start[b,q], lk = k - start[b,k]):
+ *   mask(q,k) = ids[b,q] == ids[b,k] && (|q-k| <= local_radius || global(lq) || global(lk) || grid(lq,lk)),
+ *   rel_id(q,k) = rel_id(lq,lk)   (the structured kernels take n_global = 0 only there),
  *   global(x) = global_start <= x < global_start + n_global, or -- with global_index --
  *   x is one of the n_global listed positions.  The structured kernels take the contiguous
  *   form only; a listed set is served by materialising the mask (mmt_side_inputs with
@@ -95,7 +107,8 @@ enum {
 typedef struct mmt_mask_desc {
   const int32_t* valid_len; /* [B] device ints (num_image_wordpieces + num_text_wordpieces),
                                NULL = every position valid.  With MMT_FLAG_EXAMPLE_IDS: the
-                               [B,S] device ints of example ids instead (must not be NULL) */
+                               [B,S] device ints of example ids instead (must not be NULL); with
+                               MMT_FLAG_EXAMPLE_STARTS as well: [B,2,S], ids and example starts */
   int32_t local_radius;     /* >= 0; values >= S mean "no band restriction"          */
   int32_t global_start;
   int32_t n_global;         /* contiguous range of global tokens; 0 = none           */

@@ -240,6 +240,27 @@ int mmt_embed_bwd(const mmt_embed_desc* desc, const void* dout, const int32_t* s
                   const float* rstd, float* dword_table, float* dgamma, float* dbeta, void* dpatch,
                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* Packed multimodal rows (mmt_attn.h, MMT_FLAG_EXAMPLE_STARTS): the same two calls with two per-position inputs,
+ *   example_starts int32 [B,S]  first position of the example the position belongs to (must not be NULL),
+ *   patch_slots    int32 [B,S]  entry of the position's example in patch_proj / dpatch, now [n_examples, n_patch, H]
+ *                               (one entry per imaged example of the batch); -1 = no image (NULL only with n_patch = 0).
+ * With ls = s - start (clamped into [0, S)): the position row is pos_table[min(ls, pos_rows - 1)], and the patch row of
+ * position s is patch_proj[slot][ls - patch_start] when 0 <= ls - patch_start < n_patch and 0 <= slot < n_examples.
+ * The backward's compact copy scatters by the same rule, dpatch[slot][ls - patch_start] = dout[b, s]; rows of dpatch no
+ * position maps to are not written (zero-fill it).  desc->patch_start + n_patch <= S is still asked.  Everything else,
+ * and mmt_embed_fwd / mmt_embed_bwd themselves, as above. */
+int mmt_embed_fwd_packed(const mmt_embed_desc* desc, const int32_t* word_ids, const int32_t* seg_ids,
+                         const float* word_table, const float* seg_table, const float* pos_table /* nullable */,
+                         int32_t pos_rows, const float* gamma, const float* beta, const void* patch_proj /* nullable */,
+                         const float* patch_bias /* nullable */, const int32_t* example_starts,
+                         const int32_t* patch_slots, int32_t n_examples, void* out, float* mean, float* rstd,
+                         void* stream);
+int mmt_embed_bwd_packed(const mmt_embed_desc* desc, const void* dout, const int32_t* sorted_ids,
+                         const int32_t* order, const float* word_table, const float* gamma, const float* mean,
+                         const float* rstd, float* dword_table, float* dgamma, float* dbeta, void* dpatch,
+                         const int32_t* example_starts, const int32_t* patch_slots, int32_t n_examples,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Per-row softmax cross-entropy of wide logits (the tied 30522-way MLM head):
  *   loss[row] = logsumexp(logits[row, :]) - logits[row, labels[row]]       (natural log; lse saved)

@@ -28,14 +28,14 @@ void inside(const void* p, size_t bytes, const char* what) {
 }  // namespace
 
 namespace mmt {
-hipError_t launch_attn_fwd(const FwdParams& p, int, bool, bool pack, hipStream_t) {
+hipError_t launch_attn_fwd(const FwdParams& p, int, bool, int pack, hipStream_t) {
   ++g_launches; g_last_kind = 1; g_last_epoch = p.epoch; g_last_pack = pack;
   const size_t slots = (size_t)p.B * p.N * p.n_rowblk * p.n_chunks;
   inside(p.part_o, slots * 32 * p.D * 4, "part_o");
   inside(p.part_ml, slots * 64 * 4, "part_ml");
   return hipSuccess;
 }
-hipError_t launch_attn_fwd_band_bf16(const FwdParams& p, hipStream_t st) { hipError_t e = launch_attn_fwd(p, 0, true, false, st); g_last_kind = 2; return e; }
+hipError_t launch_attn_fwd_band_bf16(const FwdParams& p, hipStream_t st) { hipError_t e = launch_attn_fwd(p, 0, true, 0, st); g_last_kind = 2; return e; }
 hipError_t launch_attn_fwd_win_bf16(const FwdParams& p, hipStream_t) {
   ++g_launches; g_last_kind = 3; g_last_epoch = p.epoch;
   if (p.rows_parts < 1 || p.rows_parts > 4) { std::fprintf(stderr, "asan driver: rows_parts %d\n", p.rows_parts); std::abort(); }
@@ -87,7 +87,7 @@ int fwd_walk_plan(FwdParams& p, int target_wgs) {
 size_t fwd_walk_workspace_bytes(int B, int N, int S) { return (size_t)B * N * (((S + 31) / 32 + 1) / 2) * 8 * 66 * sizeof(float); }
 int fwd_win_lds_bytes(int ng, int tstride) { return 65536 + (ng ? (2 * ((ng + 7) / 8) + 1) * 1024 : 0) + 512 * tstride; }
 hipError_t launch_rows_combine(const FwdParams&, bool, hipStream_t) { ++g_launches; g_last_kind = 4; return hipSuccess; }
-hipError_t launch_attn_bwd(const BwdParams& p, int, bool, bool pack, hipStream_t) {
+hipError_t launch_attn_bwd(const BwdParams& p, int, bool, int pack, hipStream_t) {
   ++g_launches; g_last_kind = 5; g_last_handover = p.ho != nullptr; g_last_epoch = p.epoch; g_last_pack = pack;
   if (pack && (p.peel_gkeys || p.lean2d)) { std::fprintf(stderr, "asan driver: example ids with a peeled step or the lean 2-D width\n"); std::abort(); }
   const size_t bn = (size_t)p.B * p.N, slots = bn * p.n_gblk * p.n_chunks;

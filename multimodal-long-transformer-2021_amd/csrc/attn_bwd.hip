@@ -59,9 +59,11 @@ __device__ __forceinline__ TileWalk band_walk(const PatternDev& pat, int x0, int
 
 // Mask bit and relative-table column of one (q,k) pair (col < 0: no relative term).
 // PACK (packed examples, kBand without a grid): the segmented term is `seg_ids`, the caller's compare of the two example ids.
-template <int MODE, bool GEN, bool GRID, bool PACK = false, typename P>
+// ORG (per-example origin, PACK only): lq, lk = the two positions local to their example -- what rel_id and the grid term
+// read; the band and the 1-D column keep k - q (an allowed pair shares its start).  No global term (refused on the host).
+template <int MODE, bool GEN, bool GRID, bool PACK = false, bool ORG = false, typename P>
 __device__ __forceinline__ void pair_mask_col(const P& p, int b, int valid_len, int q, int k,
-                                              bool& keep, int& col, bool seg_ids = false) {
+                                              bool& keep, int& col, bool seg_ids = false, int lq = 0, int lk = 0) {
   int id = -1;
   col = -1;
   if (MODE == kDense) {
@@ -70,16 +72,18 @@ __device__ __forceinline__ void pair_mask_col(const P& p, int b, int valid_len, 
     if (p.rel_ids) id = p.rel_ids[off];
     if ((unsigned)id < (unsigned)p.R) col = id;
   } else if (GEN) {
-    if constexpr (PACK) keep = pattern_mask_packed(p.pat, seg_ids, q, k);
+    if constexpr (ORG) keep = pattern_mask_origin<GRID>(p.pat, p.grid, seg_ids, q, k, lq, lk);
+    else if constexpr (PACK) keep = pattern_mask_packed(p.pat, seg_ids, q, k);
     else keep = pattern_mask<GRID>(p.pat, p.grid, valid_len, q, k);
-    if (p.pat.id_mode) id = rel_id(p.pat, q, k);
+    if (p.pat.id_mode) id = ORG ? rel_id(p.pat, lq, lk) : rel_id(p.pat, q, k);
     if ((unsigned)id < (unsigned)p.R) col = id;
   } else {
     const int d = k - q;
     const unsigned W = (unsigned)p.pat.radius;
     const bool near = (unsigned)(d + (int)W) <= 2u * W;
     const bool seg = PACK ? seg_ids : (k < valid_len) == (q < valid_len);
-    keep = (int)seg & ((int)near | (int)is_global(p.pat, k) | (int)is_global(p.pat, q) | (int)(GRID && in_grid(p.pat, p.grid, q, k)));
+    if constexpr (ORG) keep = (int)seg & ((int)near | (int)(GRID && in_grid(p.pat, p.grid, lq, lk)));
+    else keep = (int)seg & ((int)near | (int)is_global(p.pat, k) | (int)is_global(p.pat, q) | (int)(GRID && in_grid(p.pat, p.grid, q, k)));
     if (p.pat.id_mode == 1) col = min(max(d, -p.pat.m), p.pat.m) + p.pat.m;
   }
 }
@@ -148,7 +152,9 @@ __device__ __forceinline__ void build_table(const P& p, int n, const Frag<T, DH>
 // spills to scratch); XT = the K / Q / E tile, whole or in halves (BwdLds::kDqHalf).
 // PACK: as attn_fwd_kernel -- p.valid_len names the [B,S] example ids, PackWalk leaves out the key tiles with no id in the
 // row block's range.  A chunk of the global rows with no tile left writes zero partials, which the combine sums.
-template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH, bool PACK = false>
+// ORG: as attn_fwd_kernel -- p.valid_len names [B,2,S] ids and starts, ids and grid term on local positions (so the table
+// gradients are bucketed by the local id), the same two walks with a grid; attn_bwd_origin.hip.
+template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH, bool PACK = false, bool ORG = false>
 __global__ __launch_bounds__(256, (sizeof(T) == 2 && DH == 64 ? 2 : 1)) void attn_bwd_dq_kernel(const BwdParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x & 63;
@@ -187,6 +193,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && DH == 64 ? 2 : 1)) void att
   const unsigned qc = (unsigned)min(q, p.S - 1);
   const int valid_len = PACK ? 0 : (p.valid_len ? p.valid_len[b] : p.S);
   constexpr bool CUR = GRID || PACK;      // the walk is a cursor (t_cur, t_nxt), not a count
+  constexpr bool OG = ORG && GRID;        // origin + grid: GridWalk (one example in the rows) or PackWalk over the row
   const T* Q = reinterpret_cast<const T*>(p.q) + (long)b * p.qs[0] + (long)n * p.qs[2];
   const T* K = reinterpret_cast<const T*>(p.k) + (long)b * p.ks[0] + (long)n * p.ks[2];
   const T* V = reinterpret_cast<const T*>(p.v) + (long)b * p.vs[0] + (long)n * p.vs[2];
@@ -197,23 +204,50 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && DH == 64 ? 2 : 1)) void att
   TileWalk w{0, 0, 0, n_tiles, 0, 0};
   if (MODE == kBand) {
     if (split_item) { w.b0 = chunk * p.chunk_tiles; w.lenB = min(n_tiles, w.b0 + p.chunk_tiles) - w.b0; }
-    else w = band_walk(p.pat, q0, p.S);
+    else if (!OG) w = band_walk(p.pat, q0, p.S);      // (OG: every tile of the row is a candidate)
   }
   GridWalk gw;                    // GRID: cursor over the union (t_cur, t_nxt); w.count() unused
   int t_cur = 0, t_nxt = 0;
-  if constexpr (GRID) {
+  if constexpr (GRID && !ORG) {
     if (split_item) gw.init_chunk(w.b0, w.b0 + w.lenB - 1);
     else gw.init_band(p.pat, p.grid, q0, p.S);
     t_cur = gw.next(0);
   }
   PackWalk pw;                    // PACK: own id, cursor over the tiles that can hold an allowed pair, id r of the current / next tile
+  bool one_ex = false;            // OG: the block lies in one example
+  auto og_next = [&]() {          // OG: next candidate the id-range test lets through (one_ex: of GridWalk's union)
+    int t = pw.next([&](int c) { return w.at(c); }, lane);
+    while (one_ex && t != PackWalk::kEnd && !gw.has(t)) t = pw.next([&](int c) { return w.at(c); }, lane);
+    return t;
+  };
   int qid = 0, kid = 0, kid_nxt = 0;
+  int qst = 0, lq = 0, kst = 0, kst_nxt = 0;   // ORG: the row's example start and local position, start r of the current / next tile
   if constexpr (PACK) {
-    const int32_t* ids = p.valid_len + (long)b * p.S;
+    const int32_t* ids = p.valid_len + (long)b * (ORG ? 2 : 1) * p.S;
     qid = ids[qc];
     pw.init(ids, qid, p.S, w.count(), true);
-    t_cur = pw.next([&](int c) { return w.at(c); }, lane);
-    if (t_cur != PackWalk::kEnd) kid = pw.id_at(t_cur * 32 + r);
+    if constexpr (ORG) {
+      qst = pw.start_at(q);
+      lq = local_pos(q, qst, p.S);
+    }
+    if constexpr (OG) {
+      const int st0 = __builtin_amdgcn_readfirstlane(qst);
+      one_ex = pw.lo == pw.hi && __all(qst == st0);
+      if (one_ex) {
+        int t_hi;
+        gw.init_origin(p.pat, p.grid, q0, p.S, st0);
+        gw.span(w.b0, t_hi);
+        w.lenB = t_hi - w.b0 + 1;
+        pw.n_it = w.lenB;
+      }
+      t_cur = og_next();
+    } else {
+      t_cur = pw.next([&](int c) { return w.at(c); }, lane);
+    }
+    if (t_cur != PackWalk::kEnd) {
+      kid = pw.id_at(t_cur * 32 + r);
+      if constexpr (ORG) kst = pw.start_at(t_cur * 32 + r);
+    }
   }
 
   Frag<T, DH> qf, dof;
@@ -262,7 +296,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && DH == 64 ? 2 : 1)) void att
     vf.load_row(V + (unsigned)min(k0 + r, p.S - 1) * vs1, h);
     kt.load(K, ks1, k0, p.S, lane, 0);
   }
-  for (int it = 0; CUR ? t_cur != GridWalk::kEnd : it < n_it; ++it, t_cur = t_nxt, kid = kid_nxt) {
+  for (int it = 0; CUR ? t_cur != GridWalk::kEnd : it < n_it; ++it, t_cur = t_nxt, kid = kid_nxt, kst = kst_nxt) {
     const int k0 = (CUR ? t_cur : w.at(it)) * 32;
     kt.to_lds(xlds, lane);
     XT kcur;                     // (a HalfTile is staged by the product at the end: it keeps the tile across the prefetch)
@@ -270,14 +304,16 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && DH == 64 ? 2 : 1)) void att
     f32x16 c = {0}, dp = {0};
     c = mma_rows(kf, qf, c);     // S^T  [key x q]
     dp = mma_rows(vf, dof, dp);  // dP^T [key x q]
-    if constexpr (GRID) t_nxt = gw.next(t_cur + 1);
-    if constexpr (PACK) t_nxt = pw.next([&](int c) { return w.at(c); }, lane);
+    if constexpr (OG) t_nxt = og_next();
+    else if constexpr (GRID) t_nxt = gw.next(t_cur + 1);
+    else if constexpr (PACK) t_nxt = pw.next([&](int c) { return w.at(c); }, lane);
     if (CUR ? t_nxt != GridWalk::kEnd : it + 1 < n_it) {         // next tile's operands arrive under this tile's math
       const int k1 = (CUR ? t_nxt : w.at(it + 1)) * 32;
       kf.load_row(K + (unsigned)min(k1 + r, p.S - 1) * ks1, h);
       vf.load_row(V + (unsigned)min(k1 + r, p.S - 1) * vs1, h);
       kt.load(K, ks1, k1, p.S, lane, 0);
       if constexpr (PACK) kid_nxt = pw.id_at(k1 + r);
+      if constexpr (ORG) kst_nxt = pw.start_at(k1 + r);
     }
     // phase 1: mask bits, table columns and the gathered relative scores (reads only)
     int cols[16];
@@ -287,7 +323,9 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && DH == 64 ? 2 : 1)) void att
     for (int i = 0; i < 16; ++i) {
       const int kk = k0 + kap(i, h);
       bool keep;
-      if constexpr (PACK) pair_mask_col<MODE, GEN, GRID, true>(p, b, valid_len, q, kk, keep, cols[i], __shfl(kid, kap(i, h), 64) == qid);
+      if constexpr (ORG) pair_mask_col<MODE, GEN, GRID, true, true>(p, b, valid_len, q, kk, keep, cols[i], __shfl(kid, kap(i, h), 64) == qid,
+                                                                    lq, local_pos(kk, __shfl(kst, kap(i, h), 64), p.S));
+      else if constexpr (PACK) pair_mask_col<MODE, GEN, GRID, true>(p, b, valid_len, q, kk, keep, cols[i], __shfl(kid, kap(i, h), 64) == qid);
       else pair_mask_col<MODE, GEN, GRID>(p, b, valid_len, q, kk, keep, cols[i]);
       keepm |= (unsigned)keep << i;
       existm |= (unsigned)(kk < p.S && q_ok) << i;
@@ -463,7 +501,8 @@ __global__ __launch_bounds__(DH) void attn_bwd_dq_combine_kernel(const BwdParams
 // GRID instantiations are built for one workgroup per CU: at two the bf16 form spills to scratch (as the GRID = false
 // ones do, whose figures are kept as they were).  So are the DH = 128 ones (dk2, dk3, dv2, dv3: head dims 64 .. 127).
 // PACK: the same walk over query tiles against the key block's id range (the pattern is symmetric); built like the GRID ones.
-template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH, bool PACK = false>
+// ORG: likewise -- the key's start and local position on the lane, start r of the current / next query tile by shuffle.
+template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH, bool PACK = false, bool ORG = false>
 __global__ __launch_bounds__(256, ((sizeof(T) == 2 && !GRID && !PACK && DH == 64) ? 2 : 1)) void attn_bwd_dkv_kernel(const BwdParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x & 63;
@@ -501,6 +540,7 @@ __global__ __launch_bounds__(256, ((sizeof(T) == 2 && !GRID && !PACK && DH == 64
   const unsigned kc = (unsigned)min(k, p.S - 1);
   const int valid_len = PACK ? 0 : (p.valid_len ? p.valid_len[b] : p.S);
   constexpr bool CUR = GRID || PACK;      // the walk is a cursor (t_cur, t_nxt), not a count
+  constexpr bool OG = ORG && GRID;        // origin + grid: GridWalk (one example in the keys) or PackWalk over the row
   const T* Q = reinterpret_cast<const T*>(p.q) + (long)b * p.qs[0] + (long)n * p.qs[2];
   const T* K = reinterpret_cast<const T*>(p.k) + (long)b * p.ks[0] + (long)n * p.ks[2];
   const T* V = reinterpret_cast<const T*>(p.v) + (long)b * p.vs[0] + (long)n * p.vs[2];
@@ -512,23 +552,50 @@ __global__ __launch_bounds__(256, ((sizeof(T) == 2 && !GRID && !PACK && DH == 64
   TileWalk w{0, 0, 0, n_tiles, 0, 0};
   if (MODE == kBand) {
     if (split_item) { w.b0 = chunk * p.chunk_tiles; w.lenB = min(n_tiles, w.b0 + p.chunk_tiles) - w.b0; }
-    else w = band_walk(p.pat, k0, p.S);
+    else if (!OG) w = band_walk(p.pat, k0, p.S);      // (OG: every tile of the row is a candidate)
   }
   GridWalk gw;                    // GRID: the same walk over query tiles (the pattern is symmetric)
   int t_cur = 0, t_nxt = 0;
-  if constexpr (GRID) {
+  if constexpr (GRID && !ORG) {
     if (split_item) gw.init_chunk(w.b0, w.b0 + w.lenB - 1);
     else gw.init_band(p.pat, p.grid, k0, p.S);
     t_cur = gw.next(0);
   }
   PackWalk pw;                    // PACK: the key's id, cursor over the query tiles, id r of the current / next query tile
+  bool one_ex = false;            // OG: the block lies in one example
+  auto og_next = [&]() {          // OG: next candidate the id-range test lets through (one_ex: of GridWalk's union)
+    int t = pw.next([&](int c) { return w.at(c); }, lane);
+    while (one_ex && t != PackWalk::kEnd && !gw.has(t)) t = pw.next([&](int c) { return w.at(c); }, lane);
+    return t;
+  };
   int kid = 0, qid = 0, qid_nxt = 0;
+  int kst = 0, lk = 0, qst = 0, qst_nxt = 0;   // ORG: the key's example start and local position, start r of the current / next query tile
   if constexpr (PACK) {
-    const int32_t* ids = p.valid_len + (long)b * p.S;
+    const int32_t* ids = p.valid_len + (long)b * (ORG ? 2 : 1) * p.S;
     kid = ids[kc];
     pw.init(ids, kid, p.S, w.count(), true);
-    t_cur = pw.next([&](int c) { return w.at(c); }, lane);
-    if (t_cur != PackWalk::kEnd) qid = pw.id_at(t_cur * 32 + r);
+    if constexpr (ORG) {
+      kst = pw.start_at(k);
+      lk = local_pos(k, kst, p.S);
+    }
+    if constexpr (OG) {
+      const int st0 = __builtin_amdgcn_readfirstlane(kst);
+      one_ex = pw.lo == pw.hi && __all(kst == st0);
+      if (one_ex) {
+        int t_hi;
+        gw.init_origin(p.pat, p.grid, k0, p.S, st0);
+        gw.span(w.b0, t_hi);
+        w.lenB = t_hi - w.b0 + 1;
+        pw.n_it = w.lenB;
+      }
+      t_cur = og_next();
+    } else {
+      t_cur = pw.next([&](int c) { return w.at(c); }, lane);
+    }
+    if (t_cur != PackWalk::kEnd) {
+      qid = pw.id_at(t_cur * 32 + r);
+      if constexpr (ORG) qst = pw.start_at(t_cur * 32 + r);
+    }
   }
 
   Frag<T, DH> kf, vf;
@@ -545,12 +612,16 @@ __global__ __launch_bounds__(256, ((sizeof(T) == 2 && !GRID && !PACK && DH == 64
     qt.load(Q, qs1, (PACK && t_cur == PackWalk::kEnd) ? 0 : (CUR ? t_cur : w.at(0)) * 32, p.S, lane, 0);    // (kEnd: no tile at all, nothing to prefetch)
     dot.load(DO, os1, (PACK && t_cur == PackWalk::kEnd) ? 0 : (CUR ? t_cur : w.at(0)) * 32, p.S, lane, 0);
   }
-  for (int it = 0; CUR ? t_cur != GridWalk::kEnd : it < n_it; ++it, t_cur = t_nxt, qid = qid_nxt) {
+  for (int it = 0; CUR ? t_cur != GridWalk::kEnd : it < n_it; ++it, t_cur = t_nxt, qid = qid_nxt, qst = qst_nxt) {
     const int q0 = (CUR ? t_cur : w.at(it)) * 32;
-    if constexpr (GRID) t_nxt = gw.next(t_cur + 1);
+    if constexpr (GRID && !ORG) t_nxt = gw.next(t_cur + 1);
     if constexpr (PACK) {
-      t_nxt = pw.next([&](int c) { return w.at(c); }, lane);
-      if (t_nxt != PackWalk::kEnd) qid_nxt = pw.id_at(t_nxt * 32 + r);
+      if constexpr (OG) t_nxt = og_next();
+      else t_nxt = pw.next([&](int c) { return w.at(c); }, lane);
+      if (t_nxt != PackWalk::kEnd) {
+        qid_nxt = pw.id_at(t_nxt * 32 + r);
+        if constexpr (ORG) qst_nxt = pw.start_at(t_nxt * 32 + r);
+      }
     }
     Frag<T, DH> qf, dof;
     if constexpr (sizeof(T) == 2) {
@@ -583,7 +654,9 @@ __global__ __launch_bounds__(256, ((sizeof(T) == 2 && !GRID && !PACK && DH == 64
     for (int i = 0; i < 16; ++i) {
       const int qq = q0 + kap(i, h);
       bool keep;
-      if constexpr (PACK) pair_mask_col<MODE, GEN, GRID, true>(p, b, valid_len, qq, k, keep, cols[i], __shfl(qid, kap(i, h), 64) == kid);
+      if constexpr (ORG) pair_mask_col<MODE, GEN, GRID, true, true>(p, b, valid_len, qq, k, keep, cols[i], __shfl(qid, kap(i, h), 64) == kid,
+                                                                    local_pos(qq, __shfl(qst, kap(i, h), 64), p.S), lk);
+      else if constexpr (PACK) pair_mask_col<MODE, GEN, GRID, true>(p, b, valid_len, qq, k, keep, cols[i], __shfl(qid, kap(i, h), 64) == kid);
       else pair_mask_col<MODE, GEN, GRID>(p, b, valid_len, qq, k, keep, cols[i]);
       keepm |= (unsigned)keep << i;
       existm |= (unsigned)(qq < p.S && k_ok) << i;
@@ -759,7 +832,7 @@ static void allow_lds(K kernel, int bytes) {
                                                    hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
-template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH, bool PACK>
+template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH, bool PACK, bool ORG>
 static hipError_t launch_bwd_one(const BwdParams& p_in, hipStream_t st) {
   BwdParams p = p_in;
   p.red_per_plane = ((p.S + 127) >> 7) * 4;               // one dE partial per wave (32 rows)
@@ -767,16 +840,16 @@ static hipError_t launch_bwd_one(const BwdParams& p_in, hipStream_t st) {
   const int per_bn = (p.n_chunks * p.n_gblk + 3) / 4;
   dim3 grid(p.n_band_blocks + (MODE == kBand ? per_bn * p.B * p.N : 0));
   const int lds_a = 4 * BwdLds<T, Rp, DH>::kDq, lds_b = 4 * BwdLds<T, Rp, DH>::kDkv;
-  allow_lds(attn_bwd_dq_kernel<T, MODE, Rp, GEN, GRID, DH, PACK>, lds_a);
-  allow_lds(attn_bwd_dkv_kernel<T, MODE, Rp, GEN, GRID, DH, PACK>, lds_b);
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<T, MODE, Rp, GEN, GRID, DH, PACK>), grid, dim3(256), lds_a, st, p);
+  allow_lds(attn_bwd_dq_kernel<T, MODE, Rp, GEN, GRID, DH, PACK, ORG>, lds_a);
+  allow_lds(attn_bwd_dkv_kernel<T, MODE, Rp, GEN, GRID, DH, PACK, ORG>, lds_b);
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<T, MODE, Rp, GEN, GRID, DH, PACK, ORG>), grid, dim3(256), lds_a, st, p);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (MODE == kBand && p.n_gblk > 0) {
     hipLaunchKernelGGL((attn_bwd_dq_combine_kernel<T, DH>), dim3(p.pat.ng, p.B * p.N), dim3(DH), 0, st, p);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
-  hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, MODE, Rp, GEN, GRID, DH, PACK>), grid, dim3(256), lds_b, st, p);
+  hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, MODE, Rp, GEN, GRID, DH, PACK, ORG>), grid, dim3(256), lds_b, st, p);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if (MODE == kBand && p.n_gblk > 0) {
     hipLaunchKernelGGL((attn_bwd_dkv_combine_kernel<T, DH>), dim3(p.pat.ng, p.B * p.N), dim3(DH), 0, st, p);
@@ -789,15 +862,31 @@ static hipError_t launch_bwd_one(const BwdParams& p_in, hipStream_t st) {
   return e;
 }
 
-template <typename T, int MODE, bool GEN, bool GRID, int DH, bool PACK = false>
+template <typename T, int MODE, bool GEN, bool GRID, int DH, bool PACK = false, bool ORG = false>
 static hipError_t launch_bwd_rp(const BwdParams& p, hipStream_t st) {
-  if (p.Rp == 32) return launch_bwd_one<T, MODE, 32, GEN, GRID, DH, PACK>(p, st);
-  if (p.Rp == 64) return launch_bwd_one<T, MODE, 64, GEN, GRID, DH, PACK>(p, st);
-  return launch_bwd_one<T, MODE, 128, GEN, GRID, DH, PACK>(p, st);
+  if (p.Rp == 32) return launch_bwd_one<T, MODE, 32, GEN, GRID, DH, PACK, ORG>(p, st);
+  if (p.Rp == 64) return launch_bwd_one<T, MODE, 64, GEN, GRID, DH, PACK, ORG>(p, st);
+  return launch_bwd_one<T, MODE, 128, GEN, GRID, DH, PACK, ORG>(p, st);
 }
 
+#ifdef MMT_ORIGIN_TU
+// The per-example-origin instantiations (this file compiled as attn_bwd_origin.hip), as launch_attn_fwd_origin's.
 template <typename T, int DH>
-static hipError_t launch_bwd_t(const BwdParams& p, int mode, bool pack, hipStream_t st) {
+static hipError_t launch_bwd_origin_t(const BwdParams& p, hipStream_t st) {
+  const bool gen = !(p.pat.id_mode == 0 || p.perm_1d);
+  if (p.grid.ga > 0)
+    return gen ? launch_bwd_rp<T, kBand, true, true, DH, true, true>(p, st) : launch_bwd_rp<T, kBand, false, true, DH, true, true>(p, st);
+  return gen ? launch_bwd_rp<T, kBand, true, false, DH, true, true>(p, st) : launch_bwd_rp<T, kBand, false, false, DH, true, true>(p, st);
+}
+
+hipError_t launch_attn_bwd_origin(const BwdParams& p, bool bf16, hipStream_t st) {
+  if (p.D == 128) return bf16 ? launch_bwd_origin_t<__bf16, 128>(p, st) : launch_bwd_origin_t<float, 128>(p, st);
+  return bf16 ? launch_bwd_origin_t<__bf16, 64>(p, st) : launch_bwd_origin_t<float, 64>(p, st);
+}
+#else
+
+template <typename T, int DH>
+static hipError_t launch_bwd_t(const BwdParams& p, int mode, int pack, hipStream_t st) {
   if (mode == kDense) return launch_bwd_rp<T, kDense, true, false, DH>(p, st);
   const bool gen = !(p.pat.id_mode == 0 || p.perm_1d);
   if (pack)                          // packed examples (never with a grid): their own instantiations too
@@ -828,13 +917,15 @@ hipError_t launch_drel_reduce(const BwdParams& p, bool bf16, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t launch_attn_bwd(const BwdParams& p, int mode, bool bf16, bool pack, hipStream_t st) {
+hipError_t launch_attn_bwd(const BwdParams& p, int mode, bool bf16, int pack, hipStream_t st) {
   // head size 128, the image grid and packed examples: the general kernels only (the lean kernels are built for head size
   // 64 and for valid_len as the segmented term)
-  pack = pack && mode == kBand;
+  pack = mode == kBand ? pack : kPackNone;
+  if (pack == kPackOrigin) return launch_attn_bwd_origin(p, bf16, st);   // per-example origin: attn_bwd_origin.hip
   if (p.D == 128) return bf16 ? launch_bwd_t<__bf16, 128>(p, mode, pack, st) : launch_bwd_t<float, 128>(p, mode, pack, st);
   if (mode == kBand && bf16 && !pack && p.grid.ga == 0 && (p.pat.id_mode == 0 || (p.perm_1d && p.Rp <= 64) || p.lean2d)) return launch_attn_bwd_band_bf16(p, st);
   return bf16 ? launch_bwd_t<__bf16, 64>(p, mode, pack, st) : launch_bwd_t<float, 64>(p, mode, pack, st);
 }
+#endif  // MMT_ORIGIN_TU
 
 }  // namespace mmt

@@ -29,8 +29,17 @@ namespace mmt {
 // PACK = true (kBand without a grid only): packed examples -- p.valid_len names the [B,S] example ids, the segmented term
 // is ids[q] == ids[k], and the walk is PackWalk's: key tiles with no id in the row block's id range are never fetched.
 // PACK = false instantiations are the kernels as before.
-template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH, bool PACK = false>
-__global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
+// ORG = true (PACK only; attn_fwd_origin.hip): per-example origin -- p.valid_len names [B,2,S], the ids and each position's
+// example start; rel_id and the grid term take the positions local to their example (lq = q - start[q], lk likewise), the
+// band and the dropout hash keep row positions.  With GRID the walk is PackWalk's in both cases -- candidates judged
+// eight at a time by the id-range test -- over the span of GridWalk's union around the example's image, keeping the
+// tiles of that union, for a block whose 32 rows lie in one example (so the walk is cut to the example: with ids that
+// name one run each, nothing outside it passes the test), and over every tile of the row for a block that straddles
+// examples.  No global tokens (refused on the host), hence no rows items.
+// The ORG bf16 head-size-64 forms are held to two workgroups per CU (256 VGPRs): left to itself the allocator takes 260 for
+// some of them and halves the occupancy (207 -> 363 us at 16 x 256, 2-D ids).
+template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH, bool PACK = false, bool ORG = false>
+__global__ __launch_bounds__(256, (ORG && sizeof(T) == 2 && DH == 64) ? 2 : 1) void attn_fwd_kernel(const FwdParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -64,6 +73,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
   const bool q_ok = q < p.S;
   const int valid_len = PACK ? 0 : (p.valid_len ? p.valid_len[b] : p.S);
   constexpr bool CUR = GRID || PACK;      // the walk is a cursor (t_cur, t_nxt), not a count
+  constexpr bool OG = ORG && GRID;        // origin + grid: GridWalk (one example in the rows) or PackWalk over the row
 
   const T* Q = reinterpret_cast<const T*>(p.q) + (long)b * p.qs[0] + (long)n * p.qs[2];
   const T* K = reinterpret_cast<const T*>(p.k) + (long)b * p.ks[0] + (long)n * p.ks[2];
@@ -77,6 +87,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
     if (rows_item) {
       b0 = chunk * p.chunk_tiles;
       lenB = min(n_tiles, b0 + p.chunk_tiles) - b0;
+    } else if (OG) {
+      // every tile of the row is a candidate (b0 = 0, lenB = n_tiles)
     } else {
       const int lo = max(q0 - p.pat.radius, 0), hi = min(q0 + 31 + p.pat.radius, p.S - 1);
       b0 = lo >> 5;
@@ -96,7 +108,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
   // GRID: the walk is a cursor over GridWalk's union (t_cur, and t_nxt found under the tile's math); n_it unused
   GridWalk gw;
   int t_cur = 0, t_nxt = 0;
-  if constexpr (GRID) {
+  if constexpr (GRID && !ORG) {
     if (rows_item) gw.init_chunk(b0, b0 + lenB - 1);
     else gw.init_band(p.pat, p.grid, q0, p.S);
     t_cur = gw.next(0);
@@ -105,13 +117,40 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
   // A chunk of the global rows may have no such tile: its partial is then the empty one (max = -inf, sum = 0, O = 0),
   // which the combine takes as long as all chunks are reduced in one pass (<= 64 of them); beyond, nothing is left out.
   PackWalk pw;
+  bool one_ex = false;                         // OG: the block's rows lie in one example
+  auto og_next = [&]() {                       // OG: next candidate the id-range test lets through (one_ex: of GridWalk's union)
+    int t = pw.next(tile_at, lane);
+    while (one_ex && t != PackWalk::kEnd && !gw.has(t)) t = pw.next(tile_at, lane);
+    return t;
+  };
   int qid = 0, kid = 0, kid_nxt = 0;
+  int qst = 0, lq = 0, kst = 0, kst_nxt = 0;   // ORG: the row's example start and local position, start r of the current / next tile
   if constexpr (PACK) {
-    const int32_t* ids = p.valid_len + (long)b * p.S;
+    const int32_t* ids = p.valid_len + (long)b * (ORG ? 2 : 1) * p.S;
     qid = ids[min(q, p.S - 1)];
     pw.init(ids, qid, p.S, n_it, !rows_item || p.n_chunks <= 64);
-    t_cur = pw.next(tile_at, lane);
-    if (t_cur != PackWalk::kEnd) kid = pw.id_at(t_cur * 32 + r);
+    if constexpr (ORG) {
+      qst = pw.start_at(q);
+      lq = local_pos(q, qst, p.S);
+    }
+    if constexpr (OG) {
+      const int st0 = __builtin_amdgcn_readfirstlane(qst);
+      one_ex = pw.lo == pw.hi && __all(qst == st0);
+      if (one_ex) {
+        int t_hi;
+        gw.init_origin(p.pat, p.grid, q0, p.S, st0);
+        gw.span(b0, t_hi);
+        lenB = t_hi - b0 + 1;
+        pw.n_it = lenB;
+      }
+      t_cur = og_next();
+    } else {
+      t_cur = pw.next(tile_at, lane);
+    }
+    if (t_cur != PackWalk::kEnd) {
+      kid = pw.id_at(t_cur * 32 + r);
+      if constexpr (ORG) kst = pw.start_at(t_cur * 32 + r);
+    }
   }
 
   Frag<T, DH> qf;
@@ -158,7 +197,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
   const bool qblk_valid = q0 + 31 < valid_len, qblk_pad = q0 >= valid_len;
   const bool qblk_plain = q0 + 31 < p.S && !(p.pat.ng > 0 && q0 + 31 >= p.pat.g0 && q0 < p.pat.g0 + p.pat.ng);
 
-  for (int it = 0; CUR ? t_cur != GridWalk::kEnd : it < n_it; ++it, t_cur = t_nxt, kid = kid_nxt) {
+  for (int it = 0; CUR ? t_cur != GridWalk::kEnd : it < n_it; ++it, t_cur = t_nxt, kid = kid_nxt, kst = kst_nxt) {
     const int k0 = (CUR ? t_cur : tile_at(it)) * 32;
     vt.to_lds(vlds, lane);
 
@@ -167,13 +206,15 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
 
     VTile<T, DH> vcur;
     if constexpr (sizeof(T) == 4) vcur = vt;
-    if constexpr (GRID) t_nxt = gw.next(t_cur + 1);
-    if constexpr (PACK) t_nxt = pw.next(tile_at, lane);
+    if constexpr (OG) t_nxt = og_next();
+    else if constexpr (GRID) t_nxt = gw.next(t_cur + 1);
+    else if constexpr (PACK) t_nxt = pw.next(tile_at, lane);
     if (CUR ? t_nxt != GridWalk::kEnd : it + 1 < n_it) {   // prefetch the next tile (registers) under this tile's math
       const int k1 = (CUR ? t_nxt : tile_at(it + 1)) * 32;
       kf.load_row(K + (unsigned)min(k1 + r, p.S - 1) * ks1, h);
       vt.load(V, vs1, k1, p.S, lane, 0);
       if constexpr (PACK) kid_nxt = pw.id_at(k1 + r);
+      if constexpr (ORG) kst_nxt = pw.start_at(k1 + r);
     }
 
     // ---- scores in the log2 domain --------------------------------------------------------
@@ -215,7 +256,9 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
         const bool near = (unsigned)(d + (int)W) <= 2u * W;
         const bool gk = (unsigned)(kk - p.pat.g0) < (unsigned)p.pat.ng;
         const bool seg = PACK ? __shfl(kid, 4 * h + ci, 64) == qid : (kk < valid_len) == qv;
-        const bool keep = (int)seg & ((int)near | (int)gk | (int)gq | (int)(GRID && in_grid(p.pat, p.grid, q, kk)));
+        bool keep;
+        if constexpr (ORG) keep = (int)seg & ((int)near | (int)(GRID && in_grid(p.pat, p.grid, lq, local_pos(kk, __shfl(kst, 4 * h + ci, 64), p.S))));
+        else keep = (int)seg & ((int)near | (int)gk | (int)gq | (int)(GRID && in_grid(p.pat, p.grid, q, kk)));
         float rel = 0.f;
         if (id_mode == 1) rel = trow[min(max(d, -mdist), mdist) + mdist];
         float s = fmaf(c[i], p.sscale, rel);
@@ -235,9 +278,12 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const FwdParams p) {
           keep = p.att_mask ? p.att_mask[off] != 0 : true;
           if (p.rel_ids) id = p.rel_ids[off];
         } else {
-          if constexpr (PACK) keep = pattern_mask_packed(p.pat, __shfl(kid, kap(i, h), 64) == qid, q, kk);
+          int lk = kk;
+          if constexpr (ORG) lk = local_pos(kk, __shfl(kst, kap(i, h), 64), p.S);
+          if constexpr (ORG) keep = pattern_mask_origin<GRID>(p.pat, p.grid, __shfl(kid, kap(i, h), 64) == qid, q, kk, lq, lk);
+          else if constexpr (PACK) keep = pattern_mask_packed(p.pat, __shfl(kid, kap(i, h), 64) == qid, q, kk);
           else keep = pattern_mask<GRID>(p.pat, p.grid, valid_len, q, kk);
-          if (id_mode) id = rel_id(p.pat, q, kk);
+          if (id_mode) id = ORG ? rel_id(p.pat, lq, lk) : rel_id(p.pat, q, kk);
         }
         float rel = 0.f;
         if ((unsigned)id < (unsigned)p.R) rel = trow[id];
@@ -393,24 +439,42 @@ __global__ __launch_bounds__(DH) void attn_rows_combine_kernel(const FwdParams p
 }
 
 // ------------------------------------ launchers -----------------------------------------
-template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH, bool PACK>
+template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH, bool PACK, bool ORG>
 static hipError_t launch_one(const FwdParams& p, dim3 grid, hipStream_t st) {
   const int lds = 4 * WaveLds<T, Rp, DH>::kBytes;
   if (lds > 64 * 1024)               // (the 128-wide table: relative vocabularies of 65..128 ids; DH = 128 from Rp = 64)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<T, MODE, Rp, GEN, GRID, DH, PACK>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  hipLaunchKernelGGL((attn_fwd_kernel<T, MODE, Rp, GEN, GRID, DH, PACK>), grid, dim3(256), lds, st, p);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<T, MODE, Rp, GEN, GRID, DH, PACK, ORG>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  hipLaunchKernelGGL((attn_fwd_kernel<T, MODE, Rp, GEN, GRID, DH, PACK, ORG>), grid, dim3(256), lds, st, p);
   return hipGetLastError();
 }
 
-template <typename T, int MODE, bool GEN, bool GRID, int DH, bool PACK = false>
+template <typename T, int MODE, bool GEN, bool GRID, int DH, bool PACK = false, bool ORG = false>
 static hipError_t launch_rp(const FwdParams& p, dim3 grid, hipStream_t st) {
-  if (p.R <= 32) return launch_one<T, MODE, 32, GEN, GRID, DH, PACK>(p, grid, st);
-  if (p.R <= 64) return launch_one<T, MODE, 64, GEN, GRID, DH, PACK>(p, grid, st);
-  return launch_one<T, MODE, 128, GEN, GRID, DH, PACK>(p, grid, st);
+  if (p.R <= 32) return launch_one<T, MODE, 32, GEN, GRID, DH, PACK, ORG>(p, grid, st);
+  if (p.R <= 64) return launch_one<T, MODE, 64, GEN, GRID, DH, PACK, ORG>(p, grid, st);
+  return launch_one<T, MODE, 128, GEN, GRID, DH, PACK, ORG>(p, grid, st);
 }
 
+#ifdef MMT_ORIGIN_TU
+// The per-example-origin instantiations (this file compiled as attn_fwd_origin.hip).  1-D / no ids without a grid read no
+// start, but they too need kernels of their own: the ids of row b lie at [b][0][S] of [B,2,S] here.
 template <typename T, int DH>
-static hipError_t launch_t(const FwdParams& p, int mode, bool pack, dim3 grid, hipStream_t st) {
+static hipError_t launch_origin_t(const FwdParams& p, dim3 grid, hipStream_t st) {
+  const bool gen = !(p.pat.id_mode == 0 || p.perm_1d);
+  if (p.grid.ga > 0)
+    return gen ? launch_rp<T, kBand, true, true, DH, true, true>(p, grid, st) : launch_rp<T, kBand, false, true, DH, true, true>(p, grid, st);
+  return gen ? launch_rp<T, kBand, true, false, DH, true, true>(p, grid, st) : launch_rp<T, kBand, false, false, DH, true, true>(p, grid, st);
+}
+
+hipError_t launch_attn_fwd_origin(const FwdParams& p, bool bf16, hipStream_t st) {
+  dim3 grid(p.n_band_blocks);
+  if (p.D == 128) return bf16 ? launch_origin_t<__bf16, 128>(p, grid, st) : launch_origin_t<float, 128>(p, grid, st);
+  return bf16 ? launch_origin_t<__bf16, 64>(p, grid, st) : launch_origin_t<float, 64>(p, grid, st);
+}
+#else
+
+template <typename T, int DH>
+static hipError_t launch_t(const FwdParams& p, int mode, int pack, dim3 grid, hipStream_t st) {
   if (mode == kDense) return launch_rp<T, kDense, true, false, DH>(p, grid, st);
   const bool gen = !(p.pat.id_mode == 0 || p.perm_1d);
   if (pack)                          // packed examples (never with a grid: refused on the host): their own instantiations too
@@ -420,7 +484,8 @@ static hipError_t launch_t(const FwdParams& p, int mode, bool pack, dim3 grid, h
   return gen ? launch_rp<T, kBand, true, false, DH>(p, grid, st) : launch_rp<T, kBand, false, false, DH>(p, grid, st);
 }
 
-hipError_t launch_attn_fwd(const FwdParams& p, int mode, bool bf16, bool pack, hipStream_t st) {
+hipError_t launch_attn_fwd(const FwdParams& p, int mode, bool bf16, int pack, hipStream_t st) {
+  if (mode == kBand && pack == kPackOrigin) return launch_attn_fwd_origin(p, bf16, st);   // per-example origin: attn_fwd_origin.hip
   // band items first, then (kBand only) the global-row items of the same launch
   const int per_bn = (p.n_chunks * p.n_rowblk + 3) / 4;
   dim3 grid(p.n_band_blocks + (mode == kBand ? per_bn * p.B * p.N : 0));
@@ -439,5 +504,6 @@ static hipError_t launch_rows_combine_dh(const FwdParams& p, bool bf16, hipStrea
 hipError_t launch_rows_combine(const FwdParams& p, bool bf16, hipStream_t st) {
   return p.D == 128 ? launch_rows_combine_dh<128>(p, bf16, st) : launch_rows_combine_dh<64>(p, bf16, st);
 }
+#endif  // MMT_ORIGIN_TU
 
 }  // namespace mmt

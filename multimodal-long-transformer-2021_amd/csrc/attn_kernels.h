@@ -12,7 +12,7 @@ struct FwdParams {
   void* out;
   float* lse;
   const int32_t *att_mask, *rel_ids;  // dense mode
-  const int32_t* valid_len;           // [B] lengths; in the PACK instantiations (MMT_FLAG_EXAMPLE_IDS) the [B,S] example ids
+  const int32_t* valid_len;           // [B] lengths; in the PACK instantiations (MMT_FLAG_EXAMPLE_IDS) the [B,S] example ids; in the ORG ones [B,2,S] ids and starts
   int B, S, N, R;
   long qs[3], ks[3], vs[3], os[3];    // element strides of (b, s, n)
   float sscale;    // scale * log2(e)                          (multiplies q.k)
@@ -50,9 +50,12 @@ struct FwdParams {
   int D;              // head size (64 | 128): the launchers' choice of instantiation; 128 runs the general kernels only
 };
 
-// pack (both general launchers): the PACK instantiations -- p.valid_len holds example ids.  A launcher argument, not a
-// field: the parameter blocks, hence every kernel's argument layout, are what they were.
-hipError_t launch_attn_fwd(const FwdParams& p, int mode, bool bf16, bool pack, hipStream_t st);
+// pack (both general launchers): the PACK instantiations -- p.valid_len holds example ids [B,S] (kPackIds), or ids and
+// example starts [B,2,S] (kPackOrigin, MMT_FLAG_EXAMPLE_STARTS: the ORG instantiations of attn_*_origin.hip).  A launcher
+// argument, not a field: the parameter blocks, hence every kernel's argument layout, are what they were.
+enum { kPackNone = 0, kPackIds = 1, kPackOrigin = 2 };
+hipError_t launch_attn_fwd(const FwdParams& p, int mode, bool bf16, int pack, hipStream_t st);
+hipError_t launch_attn_fwd_origin(const FwdParams& p, bool bf16, hipStream_t st);              // attn_fwd_origin.hip
 hipError_t launch_rows_combine(const FwdParams& p, bool bf16, hipStream_t st);
 hipError_t launch_attn_fwd_band_bf16(const FwdParams& p, hipStream_t st);   // attn_fwd_band.hip
 hipError_t launch_attn_fwd_win_bf16(const FwdParams& p, hipStream_t st);    // attn_fwd_win.hip
@@ -115,7 +118,8 @@ struct BwdParams {
   GridDev grid;      // image-grid term (general kernels only; last, so that no other field moves)
 };
 
-hipError_t launch_attn_bwd(const BwdParams& p, int mode, bool bf16, bool pack, hipStream_t st);
+hipError_t launch_attn_bwd(const BwdParams& p, int mode, bool bf16, int pack, hipStream_t st);
+hipError_t launch_attn_bwd_origin(const BwdParams& p, bool bf16, hipStream_t st);              // attn_bwd_origin.hip
 hipError_t launch_attn_bwd_band_bf16(const BwdParams& p, hipStream_t st);   // attn_bwd_band.hip
 hipError_t launch_bwd_dq_combine(const BwdParams& p, bool bf16, hipStream_t st);
 hipError_t launch_bwd_dkv_combine(const BwdParams& p, bool bf16, hipStream_t st);

@@ -31,6 +31,22 @@ struct GridWalk {
     ia = max(x0, img_lo); ib = min(x0 + 31, img_hi);
     a = grid.ga; P = pat.P;
   }
+  // Per-example origin: a block whose rows all lie in the example that starts at `start` -- its image is at
+  // [start + g, start + g + P^2), cut at the end of the row (a start the caller clamped into [0, S): every tile the
+  // walk names is a tile of the row).  The union is not cut at the example's end here: the caller walks PackWalk's
+  // candidates over span() -- the id-range test leaves out what lies outside the example -- and keeps those has() names.
+  __device__ __forceinline__ void init_origin(const PatternDev& pat, const GridDev& grid, int x0, int S, int start) {
+    init_band(pat, grid, x0, S);
+    img_lo = min(start + grid.gs, S - 1); img_hi = min(img_lo + grid.gI - 1, S - 1);
+    ia = max(x0, img_lo); ib = min(x0 + 31, img_hi);
+  }
+  // first and last tile of the union (the band is never empty: it holds the block's own tile)
+  __device__ __forceinline__ void span(int& t_lo, int& t_hi) const {
+    t_lo = next(0);
+    t_hi = max(band_hi, glob_hi);
+    if (ia <= ib) t_hi = max(t_hi, min(ib + a * P + a, img_hi) >> 5);
+  }
+  __device__ __forceinline__ bool has(int t) const { return next(t) == t; }
   __device__ __forceinline__ void init_chunk(int t0, int t1) {
     band_lo = t0; band_hi = t1; glob_lo = 1; glob_hi = 0; ia = 1; ib = 0; img_lo = img_hi = 0; a = 0; P = 1;
   }
@@ -68,6 +84,9 @@ struct PackWalk {
   unsigned hits;          // ... and these of them are still to visit
   // id of position x of the row (clamped to the sequence: callers mask x >= S themselves)
   __device__ __forceinline__ int id_at(int x) const { return ids[min(x, S - 1)]; }
+  // start of the example of position x (MMT_FLAG_EXAMPLE_STARTS only: `ids` is plane 0 of the row's [2,S], the starts
+  // are plane 1), clamped into [0, S)
+  __device__ __forceinline__ int start_at(int x) const { return min(max(ids[S + min(x, S - 1)], 0), S - 1); }
   // [lo, hi] over the 32 rows x0 .. x0 + 31 (own = id of row x0 + (lane & 31), the same in both halves)
   __device__ __forceinline__ void init(const int32_t* row_ids, int own, int S_, int n_it_, bool skip) {
     ids = row_ids; S = S_; n_it = n_it_; base = -8; hits = 0;

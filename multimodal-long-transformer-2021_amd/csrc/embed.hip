@@ -45,9 +45,27 @@ struct EmbedParams {
   float* pieces;     // [rows][H] piece sums of runs that cross a cut (only those slots are written)
   void* dpatch;
   int nblocks;
+  // packed multimodal rows (mmt_embed_*_packed; the PK instantiations): per-position example start and entry of the
+  // position's example in patch [n_ex, n_patch, H] (-1: no image); rows of pos_table
+  const int *starts, *slots;
+  int n_ex, pos_rows;
 };
 
-template <typename T, int NCH>
+// Packed rows: position s of row b as a position of its example (clamped into [0, S): garbage starts give wrong
+// numbers, never a stray access) and the patch entry it reads -- `pj` in [0, n_patch) of entry `e`, or none.
+struct PackedPos { int local, e, pj; bool has_patch; };
+__device__ __forceinline__ PackedPos packed_pos(const EmbedParams& p, long row, int s) {
+  PackedPos o;
+  const int st = min(max(p.starts[row], 0), p.S - 1);
+  o.local = min(max(s - st, 0), p.S - 1);
+  o.e = p.slots ? p.slots[row] : -1;
+  o.pj = o.local - p.patch_start;
+  o.has_patch = (unsigned)o.pj < (unsigned)p.n_patch && (unsigned)o.e < (unsigned)p.n_ex;
+  return o;
+}
+
+// PK: packed multimodal rows -- the position row is the one of the LOCAL position, the patch row that of the example's entry.
+template <typename T, int NCH, bool PK = false>
 __global__ __launch_bounds__(256) void embed_fwd_kernel(const EmbedParams p) {
   const SeedPair sd = effective_seed(p.seed_lo, p.seed_hi, p.epoch);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -57,8 +75,13 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const EmbedParams p) {
     const int id = p.word_ids[row], sg = p.seg_ids[row];
     const bool id_ok = (unsigned)id < (unsigned)p.vocab, sg_ok = (unsigned)sg < (unsigned)p.seg_vocab;
     const int b = (int)(row / p.S), s = (int)(row - (long)b * p.S);
-    const int pj = s - p.patch_start;
-    const bool has_patch = p.patch != nullptr && (unsigned)pj < (unsigned)p.n_patch;
+    int pj = s - p.patch_start, pe = b, ps = s;        // patch row, patch entry, position row
+    bool has_patch = p.patch != nullptr && (unsigned)pj < (unsigned)p.n_patch;
+    if constexpr (PK) {
+      const PackedPos pp = packed_pos(p, row, s);
+      pj = pp.pj; pe = pp.e; ps = min(pp.local, p.pos_rows - 1);
+      has_patch = p.patch != nullptr && pp.has_patch;
+    }
     float v[NCH][8];
     float sum = 0.f;
 #pragma unroll
@@ -99,12 +122,12 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const EmbedParams p) {
         for (int i = 0; i < 8; ++i) y[i] += t[i];
       }
       if (p.pos_table) {
-        load_param(p.pos_table + (long)s * p.H + c * 8, t);
+        load_param(p.pos_table + (long)ps * p.H + c * 8, t);
 #pragma unroll
         for (int i = 0; i < 8; ++i) y[i] += t[i];
       }
       if (has_patch) {
-        Chunk<T>::load(reinterpret_cast<const T*>(p.patch) + ((long)b * p.n_patch + pj) * p.H + c * 8, t);
+        Chunk<T>::load(reinterpret_cast<const T*>(p.patch) + ((long)pe * p.n_patch + pj) * p.H + c * 8, t);
 #pragma unroll
         for (int i = 0; i < 8; ++i) y[i] += t[i];
         if (p.patch_bias) {
@@ -120,7 +143,9 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const EmbedParams p) {
 
 // One wave per sorted position i.  Heads of pieces (first of a run, or i % kEmbedCut == 0) sum
 // their piece [i, end): end = first position with another id, or the next cut.
-template <typename T, int NCH>
+// PK: the compact dpatch copy scatters by the forward's rule (entries and rows no position maps to are left as they are:
+// the caller zero-fills dpatch).
+template <typename T, int NCH, bool PK = false>
 __global__ __launch_bounds__(256) void embed_bwd_kernel(const EmbedParams p) {
   const SeedPair sd = effective_seed(p.seed_lo, p.seed_hi, p.epoch);
   __shared__ float red[4][64 * NCH * 8];
@@ -188,8 +213,15 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(const EmbedParams p) {
       for (int u = 0; u < 4; ++u) {
         if (k0 + u >= n_rows) break;
         const int row = rows4[u];
-        const int b = row / p.S, s = row - b * p.S, pj = s - p.patch_start;
-        const bool to_patch = p.dpatch != nullptr && (unsigned)pj < (unsigned)p.n_patch;
+        int b = row / p.S;
+        const int s = row - b * p.S;
+        int pj = s - p.patch_start;
+        bool to_patch = p.dpatch != nullptr && (unsigned)pj < (unsigned)p.n_patch;
+        if constexpr (PK) {
+          const PackedPos pp = packed_pos(p, row, s);
+          pj = pp.pj; b = pp.e;
+          to_patch = p.dpatch != nullptr && pp.has_patch;
+        }
 #pragma unroll
         for (int j = 0; j < NCH; ++j) {
           const int c = lane + 64 * j;
@@ -343,10 +375,12 @@ int embed_blocks(const mmt_embed_desc* d) {
 
 extern "C" {
 
-int mmt_embed_fwd(const mmt_embed_desc* d, const int32_t* word_ids, const int32_t* seg_ids,
+// shared by mmt_embed_fwd (starts == NULL) and mmt_embed_fwd_packed
+static int embed_fwd_any(const mmt_embed_desc* d, const int32_t* word_ids, const int32_t* seg_ids,
                   const float* word_table, const float* seg_table, const float* pos_table,
                   const float* gamma, const float* beta, const void* patch_proj, const float* patch_bias,
-                  void* out, float* mean, float* rstd, void* stream) {
+                  void* out, float* mean, float* rstd, const int32_t* starts, const int32_t* slots, int n_ex, int pos_rows,
+                  void* stream) {
   if (int rc = check_embed(d)) return rc;
   if (!word_ids || !seg_ids || !word_table || !seg_table || !gamma || !beta || !out || !mean || !rstd)
     return mmt::fail(MMT_E_INVALID, "mmt_embed_fwd: NULL argument");
@@ -355,14 +389,37 @@ int mmt_embed_fwd(const mmt_embed_desc* d, const int32_t* word_ids, const int32_
   p.word_ids = word_ids; p.seg_ids = seg_ids; p.word_table = word_table; p.seg_table = seg_table;
   p.pos_table = pos_table; p.gamma = gamma; p.beta = beta; p.patch = d->n_patch > 0 ? patch_proj : nullptr;
   p.patch_bias = patch_bias; p.out = out; p.mean_out = mean; p.rstd_out = rstd;
+  p.starts = starts; p.slots = slots; p.n_ex = n_ex; p.pos_rows = pos_rows;
   const int blocks = embed_blocks(d), nchl = ((d->H >> 3) + 63) / 64;
   hipStream_t st = (hipStream_t)stream;
-#define MMT_EF(T, N) hipLaunchKernelGGL((mmt::embed_fwd_kernel<T, N>), dim3(blocks), dim3(256), 0, st, p)
-  if (d->dtype == MMT_BF16) { if (nchl <= 1) MMT_EF(__bf16, 1); else if (nchl <= 2) MMT_EF(__bf16, 2); else MMT_EF(__bf16, 4); }
-  else { if (nchl <= 1) MMT_EF(float, 1); else if (nchl <= 2) MMT_EF(float, 2); else MMT_EF(float, 4); }
+#define MMT_EF(T, N, PK) hipLaunchKernelGGL((mmt::embed_fwd_kernel<T, N, PK>), dim3(blocks), dim3(256), 0, st, p)
+#define MMT_EFN(T, PK) do { if (nchl <= 1) MMT_EF(T, 1, PK); else if (nchl <= 2) MMT_EF(T, 2, PK); else MMT_EF(T, 4, PK); } while (0)
+  if (starts) { if (d->dtype == MMT_BF16) MMT_EFN(__bf16, true); else MMT_EFN(float, true); }
+  else { if (d->dtype == MMT_BF16) MMT_EFN(__bf16, false); else MMT_EFN(float, false); }
+#undef MMT_EFN
 #undef MMT_EF
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? MMT_OK : mmt::fail(MMT_E_LAUNCH, "mmt_embed_fwd: %s", hipGetErrorString(e));
+}
+
+int mmt_embed_fwd(const mmt_embed_desc* d, const int32_t* word_ids, const int32_t* seg_ids,
+                  const float* word_table, const float* seg_table, const float* pos_table,
+                  const float* gamma, const float* beta, const void* patch_proj, const float* patch_bias,
+                  void* out, float* mean, float* rstd, void* stream) {
+  return embed_fwd_any(d, word_ids, seg_ids, word_table, seg_table, pos_table, gamma, beta, patch_proj, patch_bias, out, mean,
+                       rstd, nullptr, nullptr, 0, 0, stream);
+}
+
+int mmt_embed_fwd_packed(const mmt_embed_desc* d, const int32_t* word_ids, const int32_t* seg_ids,
+                         const float* word_table, const float* seg_table, const float* pos_table, int32_t pos_rows,
+                         const float* gamma, const float* beta, const void* patch_proj, const float* patch_bias,
+                         const int32_t* example_starts, const int32_t* patch_slots, int32_t n_examples,
+                         void* out, float* mean, float* rstd, void* stream) {
+  if (!example_starts) return mmt::fail(MMT_E_INVALID, "mmt_embed_fwd_packed: example_starts is NULL");
+  if (pos_table && pos_rows <= 0) return mmt::fail(MMT_E_INVALID, "mmt_embed_fwd_packed: pos_table with pos_rows <= 0");
+  if (d && d->n_patch > 0 && (!patch_slots || n_examples <= 0)) return mmt::fail(MMT_E_INVALID, "mmt_embed_fwd_packed: n_patch > 0 needs patch_slots and n_examples > 0");
+  return embed_fwd_any(d, word_ids, seg_ids, word_table, seg_table, pos_table, gamma, beta, patch_proj, patch_bias, out, mean,
+                       rstd, example_starts, patch_slots, n_examples, pos_rows, stream);
 }
 
 size_t mmt_embed_workspace_bytes(const mmt_embed_desc* d) {
@@ -370,10 +427,10 @@ size_t mmt_embed_workspace_bytes(const mmt_embed_desc* d) {
   return ((size_t)mmt::kEmbedBlocks * 2 * d->H + (size_t)d->rows * d->H) * sizeof(float);
 }
 
-int mmt_embed_bwd(const mmt_embed_desc* d, const void* dout, const int32_t* sorted_ids, const int32_t* order,
+static int embed_bwd_any(const mmt_embed_desc* d, const void* dout, const int32_t* sorted_ids, const int32_t* order,
                   const float* word_table, const float* gamma, const float* mean, const float* rstd,
                   float* dword_table, float* dgamma, float* dbeta, void* dpatch, void* ws, size_t ws_bytes,
-                  void* stream) {
+                  const int32_t* starts, const int32_t* slots, int n_ex, void* stream) {
   if (int rc = check_embed(d)) return rc;
   if (!dout || !sorted_ids || !order || !word_table || !gamma || !mean || !rstd || !dword_table || !dgamma || !dbeta)
     return mmt::fail(MMT_E_INVALID, "mmt_embed_bwd: NULL argument");
@@ -383,11 +440,14 @@ int mmt_embed_bwd(const mmt_embed_desc* d, const void* dout, const int32_t* sort
   p.mean = mean; p.rstd = rstd; p.dword_table = dword_table; p.dpatch = d->n_patch > 0 ? dpatch : nullptr;
   p.part = (float*)ws; p.pieces = p.part + (size_t)mmt::kEmbedBlocks * 2 * d->H;
   p.nblocks = embed_blocks(d);
+  p.starts = starts; p.slots = slots; p.n_ex = n_ex;
   const int nchl = ((d->H >> 3) + 63) / 64;
   hipStream_t st = (hipStream_t)stream;
-#define MMT_EB(T, N) hipLaunchKernelGGL((mmt::embed_bwd_kernel<T, N>), dim3(p.nblocks), dim3(256), 0, st, p)
-  if (d->dtype == MMT_BF16) { if (nchl <= 1) MMT_EB(__bf16, 1); else if (nchl <= 2) MMT_EB(__bf16, 2); else MMT_EB(__bf16, 4); }
-  else { if (nchl <= 1) MMT_EB(float, 1); else if (nchl <= 2) MMT_EB(float, 2); else MMT_EB(float, 4); }
+#define MMT_EB(T, N, PK) hipLaunchKernelGGL((mmt::embed_bwd_kernel<T, N, PK>), dim3(p.nblocks), dim3(256), 0, st, p)
+#define MMT_EBN(T, PK) do { if (nchl <= 1) MMT_EB(T, 1, PK); else if (nchl <= 2) MMT_EB(T, 2, PK); else MMT_EB(T, 4, PK); } while (0)
+  if (starts) { if (d->dtype == MMT_BF16) MMT_EBN(__bf16, true); else MMT_EBN(float, true); }
+  else { if (d->dtype == MMT_BF16) MMT_EBN(__bf16, false); else MMT_EBN(float, false); }
+#undef MMT_EBN
 #undef MMT_EB
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return mmt::fail(MMT_E_LAUNCH, "mmt_embed_bwd: %s", hipGetErrorString(e));
@@ -397,6 +457,25 @@ int mmt_embed_bwd(const mmt_embed_desc* d, const void* dout, const int32_t* sort
   if ((e = hipGetLastError()) != hipSuccess) return mmt::fail(MMT_E_LAUNCH, "mmt_embed_bwd runs: %s", hipGetErrorString(e));
   e = mmt::launch_colsum_reduce(p.part, p.nblocks, 2, d->H, dgamma, dbeta, nullptr, d->accumulate, st);
   return e == hipSuccess ? MMT_OK : mmt::fail(MMT_E_LAUNCH, "mmt_embed_bwd reduce: %s", hipGetErrorString(e));
+}
+
+int mmt_embed_bwd(const mmt_embed_desc* d, const void* dout, const int32_t* sorted_ids, const int32_t* order,
+                  const float* word_table, const float* gamma, const float* mean, const float* rstd,
+                  float* dword_table, float* dgamma, float* dbeta, void* dpatch, void* ws, size_t ws_bytes,
+                  void* stream) {
+  return embed_bwd_any(d, dout, sorted_ids, order, word_table, gamma, mean, rstd, dword_table, dgamma, dbeta, dpatch, ws,
+                       ws_bytes, nullptr, nullptr, 0, stream);
+}
+
+int mmt_embed_bwd_packed(const mmt_embed_desc* d, const void* dout, const int32_t* sorted_ids, const int32_t* order,
+                         const float* word_table, const float* gamma, const float* mean, const float* rstd,
+                         float* dword_table, float* dgamma, float* dbeta, void* dpatch,
+                         const int32_t* example_starts, const int32_t* patch_slots, int32_t n_examples,
+                         void* ws, size_t ws_bytes, void* stream) {
+  if (!example_starts) return mmt::fail(MMT_E_INVALID, "mmt_embed_bwd_packed: example_starts is NULL");
+  if (dpatch && (!patch_slots || n_examples <= 0)) return mmt::fail(MMT_E_INVALID, "mmt_embed_bwd_packed: dpatch needs patch_slots and n_examples > 0");
+  return embed_bwd_any(d, dout, sorted_ids, order, word_table, gamma, mean, rstd, dword_table, dgamma, dbeta, dpatch, ws,
+                       ws_bytes, example_starts, patch_slots, n_examples, stream);
 }
 
 }  // extern "C"

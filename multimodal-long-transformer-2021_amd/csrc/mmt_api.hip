@@ -49,7 +49,7 @@ struct Plan {
 // The global tokens, if any, must be the peeled kind (<= 8, contiguous); the band at most 8 tiles wide.
 int handover_slots(const mmt_attn_desc* d, bool dense) {
   if (dense || d->dtype != MMT_BF16 || (d->mask.image_grid & 0xFF) || d->D != 64) return 0;     // (an image grid, head size 128: the general kernels)
-  if (d->flags & MMT_FLAG_EXAMPLE_IDS) return 0;                                                 // (packed examples: likewise)
+  if (d->flags & (MMT_FLAG_EXAMPLE_IDS | MMT_FLAG_EXAMPLE_STARTS)) return 0;                     // (packed examples: likewise)
   if (d->mask.global_index || d->mask.n_global > 8) return 0;
   const int W = d->mask.local_radius > d->S ? d->S : d->mask.local_radius;
   const int slots = 2 * ((W + 31) / 32) + 1;
@@ -106,9 +106,21 @@ int check_desc(const mmt_attn_desc* d) {
 
 // MMT_FLAG_EXAMPLE_IDS (mask.valid_len names the [B,S] example ids): its argument errors.  Asked for structured calls and
 // by mmt_workspace_bytes only -- with a dense att_mask the flag is ignored like the rest of desc->mask.
+// MMT_FLAG_EXAMPLE_STARTS (valid_len names [B,2,S]: ids and example starts) goes with the ids flag only; it takes the image
+// grid -- every example has its image at its own origin -- and refuses global tokens: per example they are scattered row
+// groups, which the split-rows plan (one contiguous range per row) does not describe.
 int check_packed(const mmt_attn_desc* d) {
+  const bool starts = d->flags & MMT_FLAG_EXAMPLE_STARTS;
+  if (starts && !(d->flags & MMT_FLAG_EXAMPLE_IDS)) return fail(MMT_E_INVALID, "MMT_FLAG_EXAMPLE_STARTS needs MMT_FLAG_EXAMPLE_IDS: the starts are plane 1 of [B,2,S] behind the ids");
   if (!(d->flags & MMT_FLAG_EXAMPLE_IDS)) return MMT_OK;
-  if (!d->mask.valid_len) return fail(MMT_E_INVALID, "MMT_FLAG_EXAMPLE_IDS: mask.valid_len must name the [B,S] example ids, it is NULL");
+  if (!d->mask.valid_len)
+    return starts ? fail(MMT_E_INVALID, "MMT_FLAG_EXAMPLE_STARTS: mask.valid_len must name the [B,2,S] example ids and starts, it is NULL")
+                  : fail(MMT_E_INVALID, "MMT_FLAG_EXAMPLE_IDS: mask.valid_len must name the [B,S] example ids, it is NULL");
+  if (starts) {
+    if (d->mask.n_global > 0)
+      return fail(MMT_E_UNSUPPORTED, "example starts with global tokens: per-example global tokens are scattered row groups with no structured kernel (materialise att_mask / rel_ids and use the dense operator)");
+    return MMT_OK;
+  }
   if (grid_radius(d->mask) > 0)
     return fail(MMT_E_UNSUPPORTED, "example ids with an image grid: the grid names one image per row, packed rows have several (materialise att_mask and use the dense operator)");
   return MMT_OK;
@@ -244,8 +256,9 @@ int mmt_attn_fwd(const mmt_attn_desc* desc, const void* q, const void* k, const 
   const bool dense = att_mask != nullptr || rel_ids != nullptr;
   if (!dense && desc->mask.global_index && desc->mask.n_global > 0)
     return fail(MMT_E_UNSUPPORTED, "a listed global-token set has no structured kernel: materialise att_mask with mmt_side_inputs(materialize_pattern = 1) and pass it (dense operator)");
-  const bool pack = !dense && (desc->flags & MMT_FLAG_EXAMPLE_IDS);
-  if (pack) if (int rc = check_packed(desc)) return rc;
+  if (!dense) if (int rc = check_packed(desc)) return rc;
+  const int pack = (dense || !(desc->flags & MMT_FLAG_EXAMPLE_IDS)) ? mmt::kPackNone
+                   : ((desc->flags & MMT_FLAG_EXAMPLE_STARTS) ? mmt::kPackOrigin : mmt::kPackIds);
   const Plan pl = make_plan(desc, dense);
   if (pl.fwd_ws > 0 && (!workspace || workspace_bytes < pl.fwd_ws))
     return fail(MMT_E_WORKSPACE, "workspace too small: need %zu bytes, got %zu", pl.fwd_ws, workspace_bytes);
@@ -262,7 +275,7 @@ int mmt_attn_fwd(const mmt_attn_desc* desc, const void* q, const void* k, const 
 
   hipError_t e;
   if (dense) {
-    e = mmt::launch_attn_fwd(p, mmt::kDense, bf16, false, st);
+    e = mmt::launch_attn_fwd(p, mmt::kDense, bf16, mmt::kPackNone, st);
     if (e != hipSuccess) return fail(MMT_E_LAUNCH, "dense forward launch: %s", hipGetErrorString(e));
     return MMT_OK;
   }
@@ -383,8 +396,9 @@ int mmt_attn_bwd(const mmt_attn_desc* desc, const void* q, const void* k, const 
   const bool dense = att_mask != nullptr || rel_ids != nullptr;
   if (!dense && desc->mask.global_index && desc->mask.n_global > 0)
     return fail(MMT_E_UNSUPPORTED, "a listed global-token set has no structured kernel: materialise att_mask with mmt_side_inputs(materialize_pattern = 1) and pass it (dense operator)");
-  const bool pack = !dense && (desc->flags & MMT_FLAG_EXAMPLE_IDS);
-  if (pack) if (int rc = check_packed(desc)) return rc;
+  if (!dense) if (int rc = check_packed(desc)) return rc;
+  const int pack = (dense || !(desc->flags & MMT_FLAG_EXAMPLE_IDS)) ? mmt::kPackNone
+                   : ((desc->flags & MMT_FLAG_EXAMPLE_STARTS) ? mmt::kPackOrigin : mmt::kPackIds);
   const Plan pl = make_plan(desc, dense);
   if (!workspace || workspace_bytes < pl.bwd_ws)
     return fail(MMT_E_WORKSPACE, "workspace too small: need %zu bytes, got %zu", pl.bwd_ws, workspace_bytes);

@@ -115,6 +115,17 @@ __device__ __forceinline__ bool pattern_mask_packed(const PatternDev& p, bool se
   return seg && (abs(q - k) <= p.radius || is_global(p, q) || is_global(p, k));
 }
 
+// Per-example origin (MMT_FLAG_EXAMPLE_STARTS): position x of the row as a position of its own example, whose first
+// position is `start`.  Clamped into [0, S): whatever the starts hold, the value feeds the magicP multiply (exact for
+// x < S) and table indices only inside their ranges -- garbage starts give wrong numbers, never a stray access.
+__device__ __forceinline__ int local_pos(int x, int start, int S) { return min(max(x - start, 0), S - 1); }
+// ... and the mask under it: the band on row positions (an allowed pair shares its start: k - q is lk - lq), the grid on
+// local ones.  No global term: per-example global tokens are refused on the host (scattered row groups).
+template <bool GRID>
+__device__ __forceinline__ bool pattern_mask_origin(const PatternDev& p, const GridDev& g, bool seg, int q, int k, int lq, int lk) {
+  return seg && (abs(q - k) <= p.radius || (GRID && in_grid(p, g, lq, lk)));
+}
+
 // ---------------------------------------------------------------------------------------
 // Dropout keep decision shared by forward and backward (and restated on the CPU in the
 // tests): one 32-bit mix per (b, n, q, k).  keep iff hash >= threshold.

@@ -101,14 +101,23 @@ class MmtEncoder(nn.Module):
             and w.embedding_table.dtype == torch.float32 and sg.embedding_table.dtype == torch.float32
             and sg.embedding_table.shape[1] == H and self.use_fused_embedding)
 
-  def embed(self, word_ids, segment_ids=None, patch_embeddings=None, training=False):
+  def embed(self, word_ids, segment_ids=None, patch_embeddings=None, training=False, example_starts=None,
+            patch_slots=None):
     """Embedding assembly, `mmt_encoder.py:189-218`: LayerNorm + dropout on
     the WORD embeddings only; segment / position / projected patches are added afterwards.
     On the GPU this is one HIP kernel (`fused.embed_assemble`) writing the compute dtype; the
-    patch projection runs in the compute dtype like every other Dense layer of the stack."""
+    patch projection runs in the compute dtype like every other Dense layer of the stack.
+
+    Packed multimodal rows (`example_starts`, `patch_slots` int32 [B,S]; `input_utils.packed_example_layout`): position s
+    of an example that starts at `start` takes the absolute position row `s - start` and, when its `slot >= 0` and
+    `0 <= s - start - 2 < P^2`, the projected patch `patch_embeddings[slot][s - start - 2]` -- `patch_embeddings` is then
+    [E, P^2, F], one entry per imaged example of the batch.  Same kernel path on the GPU (`mmt_embed_fwd_packed`); the
+    torch branch (`_embed_packed`) states the same rule and is the CPU yardstick."""
     if segment_ids is None:
       segment_ids = torch.ones_like(word_ids)
     ln = self._embedding_norm_layer
+    if example_starts is not None and patch_embeddings is not None and patch_slots is None:
+      raise ValueError('packed rows with patch_embeddings need patch_slots')
     if self._fused_embed_ok(word_ids):
       cd = self.compute_dtype
       pe = None
@@ -120,7 +129,10 @@ class MmtEncoder(nn.Module):
       return fused.embed_assemble(word_ids, segment_ids, self._word_embedding_layer.embedding_table,
                                   self._segment_embedding_layer.embedding_table, ln.weight, ln.bias,
                                   pos_table=self._position_embeddings, patch_proj=pe, eps=ln.eps, p=p,
-                                  seed=fused.next_seed(0) if p else 0, patch_start=2, out_dtype=cd)
+                                  seed=fused.next_seed(0) if p else 0, patch_start=2, out_dtype=cd,
+                                  example_starts=example_starts, patch_slots=patch_slots)
+    if example_starts is not None:
+      return self._embed_packed(word_ids, segment_ids, patch_embeddings, training, example_starts, patch_slots)
     word = self._word_embedding_layer(word_ids)
     seg = self._segment_embedding_layer(segment_ids)
     word = F.layer_norm(word, ln.normalized_shape, ln.weight, ln.bias, ln.eps)
@@ -137,18 +149,43 @@ class MmtEncoder(nn.Module):
       emb = emb + F.pad(pe, (0, 0, 2, S - 2 - n_patch))
     return emb
 
+  def _embed_packed(self, word_ids, segment_ids, patch_embeddings, training, example_starts, patch_slots):
+    ln = self._embedding_norm_layer
+    word = self._word_embedding_layer(word_ids)
+    seg = self._segment_embedding_layer(segment_ids)
+    word = F.layer_norm(word, ln.normalized_shape, ln.weight, ln.bias, ln.eps)
+    word = F.dropout(word, self._hidden_dropout_prob, training)
+    emb = word + seg
+    B, S = word_ids.shape
+    local = torch.arange(S, device=word_ids.device)[None] - example_starts.long()
+    if self._position_embeddings is not None:
+      emb = emb + self._position_embeddings[local.clamp(0, self._position_embeddings.shape[0] - 1)]
+    if patch_embeddings is not None:
+      pe = F.linear(patch_embeddings.to(emb.dtype), self._patch_projection_weight, self._patch_projection_bias)
+      E, n_patch = pe.shape[0], pe.shape[1]
+      pj = local - 2                          # 2 is for CLS and [PATCH] (`:213-218`), now of every example
+      has = (patch_slots >= 0) & (patch_slots < E) & (pj >= 0) & (pj < n_patch)
+      rows = pe[patch_slots.long().clamp(0, max(E - 1, 0)), pj.clamp(0, n_patch - 1)]
+      emb = emb + torch.where(has[..., None], rows, torch.zeros_like(rows[:1, :1]))
+    return emb
+
   def forward(self, word_ids, segment_ids=None, att_mask=None, relative_att_ids=None,
               patch_embeddings=None, training: Optional[bool] = None,
-              attention_pattern: Optional[AttentionPattern] = None, valid_len=None, example_ids=None):
+              attention_pattern: Optional[AttentionPattern] = None, valid_len=None, example_ids=None,
+              example_starts=None, patch_slots=None, first_positions=None):
+    """`example_starts` / `patch_slots` (with `example_ids`): packed multimodal rows (`embed`, ops.py).  `first_positions`
+    int64 [E_all, 2] = (row, first position) of every example: `pooled_output` is then [E_all, H], gathered there."""
     training = bool(training)
-    emb = self.embed(word_ids, segment_ids, patch_embeddings, training).to(self.compute_dtype)
+    if example_starts is not None and example_ids is None:
+      raise ValueError('example_starts needs example_ids')
+    emb = self.embed(word_ids, segment_ids, patch_embeddings, training, example_starts, patch_slots).to(self.compute_dtype)
     out = self._transformer_layers(inputs=emb, att_mask=att_mask, relative_att_ids=relative_att_ids,
                                    training=training, pattern=attention_pattern, valid_len=valid_len,
-                                   example_ids=example_ids,
+                                   example_ids=example_ids, example_starts=example_starts,
                                    dropout_seed=(fused.next_seed(0) >> 24) if training else 0)
     outputs = {'sequence_output': out}
     if hasattr(self, '_pooler_weight'):
-      first = out[:, 0]
+      first = out[:, 0] if first_positions is None else out[first_positions[:, 0], first_positions[:, 1]]
       outputs['pooled_output'] = torch.tanh(layers._linear(first, self._pooler_weight, self._pooler_bias))
     return outputs
 

@@ -628,7 +628,7 @@ class _EmbedAssembleFn(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, word_ids, seg_ids, word_table, seg_table, pos_table, gamma, beta, patch_proj, cfg):
-    eps, p, seed, patch_start, out_dtype = cfg
+    eps, p, seed, patch_start, out_dtype, starts, slots = cfg
     _check(word_ids, seg_ids, word_table, seg_table, gamma, beta, patch_proj, pos_table)
     B, S = word_ids.shape
     V, H = word_table.shape
@@ -636,13 +636,21 @@ class _EmbedAssembleFn(torch.autograd.Function):
     seg = seg_ids.reshape(-1).to(torch.int32).contiguous()
     wt, st = _f32(word_table.detach()), _f32(seg_table.detach())
     pt = None if pos_table is None else _f32(pos_table.detach())
-    if pt is not None and pt.shape[0] < S:
+    if pt is not None and starts is None and pt.shape[0] < S:
       raise ValueError(f'position table has {pt.shape[0]} rows, sequence length is {S}')
+    if starts is not None:           # packed multimodal rows: per-position example start and patch entry
+      starts = starts.reshape(-1).to(torch.int32).contiguous()
+      if starts.numel() != B * S or (slots is not None and slots.numel() != B * S):
+        raise ValueError('example_starts / patch_slots must be [B,S]')
+      slots = None if slots is None else slots.reshape(-1).to(torch.int32).contiguous()
+      if patch_proj is not None and slots is None:
+        raise ValueError('packed rows with patch_proj need patch_slots')
     g32, b32 = _f32(gamma.detach()), _f32(beta.detach())
     n_patch = 0
     if patch_proj is not None:
-      if patch_proj.dim() != 3 or patch_proj.shape[0] != B or patch_proj.shape[2] != H or patch_proj.dtype != out_dtype:
-        raise ValueError('patch_proj must be [B, n_patch, H] in the output dtype')
+      if (patch_proj.dim() != 3 or (starts is None and patch_proj.shape[0] != B) or patch_proj.shape[2] != H
+          or patch_proj.dtype != out_dtype):
+        raise ValueError('patch_proj must be [B, n_patch, H] ([E, n_patch, H] for packed rows) in the output dtype')
       patch_proj = patch_proj.contiguous()
       n_patch = patch_proj.shape[1]
     d = _lib.EmbedDesc()
@@ -653,9 +661,16 @@ class _EmbedAssembleFn(torch.autograd.Function):
     out = torch.empty((B, S, H), dtype=out_dtype, device=word_table.device)
     mean = torch.empty(B * S, dtype=torch.float32, device=out.device)
     rstd = torch.empty_like(mean)
+    n_ex = 0 if patch_proj is None else patch_proj.shape[0]
     with torch.cuda.device(out.device):
-      _lib.check(_lib.lib().mmt_embed_fwd(d, _p(ids), _p(seg), _p(wt), _p(st), _p(pt), _p(g32), _p(b32),
-                                          _p(patch_proj), None, _p(out), _p(mean), _p(rstd), _stream(out)))
+      if starts is None:
+        _lib.check(_lib.lib().mmt_embed_fwd(d, _p(ids), _p(seg), _p(wt), _p(st), _p(pt), _p(g32), _p(b32),
+                                            _p(patch_proj), None, _p(out), _p(mean), _p(rstd), _stream(out)))
+      else:
+        _lib.check(_lib.lib().mmt_embed_fwd_packed(d, _p(ids), _p(seg), _p(wt), _p(st), _p(pt), 0 if pt is None else pt.shape[0],
+                                                   _p(g32), _p(b32), _p(patch_proj), None, _p(starts), _p(slots), n_ex,
+                                                   _p(out), _p(mean), _p(rstd), _stream(out)))
+    ctx.packed = (starts, slots, n_ex)
     ctx.save_for_backward(ids, seg, wt, g32, mean, rstd)
     ctx.desc, ctx.params = d, (word_table, seg_table, pos_table, gamma, beta)
     ctx.has_patch = patch_proj is not None
@@ -684,13 +699,22 @@ class _EmbedAssembleFn(torch.autograd.Function):
       dg, db = torch.empty_like(g32), torch.empty_like(g32)
     d.accumulate = int(direct)
     need_patch = ctx.has_patch and ctx.needs_input_grad[7]
-    dpatch = torch.empty((B, d.n_patch, H), dtype=dout.dtype, device=dout.device) if need_patch else None
+    starts, slots, n_ex = ctx.packed
+    if starts is None:
+      dpatch = torch.empty((B, d.n_patch, H), dtype=dout.dtype, device=dout.device) if need_patch else None
+    else:                             # (rows of an image that its example is too short to hold are never written)
+      dpatch = torch.zeros((n_ex, d.n_patch, H), dtype=dout.dtype, device=dout.device) if need_patch else None
     L = _lib.lib()
     n = L.mmt_embed_workspace_bytes(d)
     ws = torch.empty((max(n, 16),), dtype=torch.uint8, device=dout.device)
     with torch.cuda.device(dout.device):
-      _lib.check(L.mmt_embed_bwd(d, _p(dout2), _p(sorted_ids), _p(order), _p(wt), _p(g32), _p(mean), _p(rstd), _p(dword),
-                                 _p(dg), _p(db), _p(dpatch), _p(ws), ws.numel(), _stream(dout)))
+      if starts is None:
+        _lib.check(L.mmt_embed_bwd(d, _p(dout2), _p(sorted_ids), _p(order), _p(wt), _p(g32), _p(mean), _p(rstd), _p(dword),
+                                   _p(dg), _p(db), _p(dpatch), _p(ws), ws.numel(), _stream(dout)))
+      else:
+        _lib.check(L.mmt_embed_bwd_packed(d, _p(dout2), _p(sorted_ids), _p(order), _p(wt), _p(g32), _p(mean), _p(rstd),
+                                          _p(dword), _p(dg), _p(db), _p(dpatch), _p(starts), _p(slots), n_ex, _p(ws),
+                                          ws.numel(), _stream(dout)))
     dword_ret = None
     if dword is not getattr(word_table, 'grad', None) and ctx.needs_input_grad[2]:
       dword_ret = dword.to(word_table.dtype)
@@ -701,17 +725,25 @@ class _EmbedAssembleFn(torch.autograd.Function):
       dseg = _mm_f32(onehot.t(), dout2).to(seg_table.dtype)
     if pos_table is not None and ctx.needs_input_grad[4]:
       dpos = torch.zeros(pos_table.shape, dtype=torch.float32, device=dout.device)
-      dpos[:S] = dout.sum(0, dtype=torch.float32)
+      if starts is None:
+        dpos[:S] = dout.sum(0, dtype=torch.float32)
+      else:                           # packed rows: summed by the LOCAL position, as the kernel clamps it
+        st = starts.clamp(0, S - 1).long()
+        local = (_arange_i32(S, dout.device).long().repeat(B) - st).clamp_(0, S - 1).clamp_(max=pos_table.shape[0] - 1)
+        dpos.index_add_(0, local, dout2.float())
       dpos = dpos.to(pos_table.dtype)
     return (None, None, dword_ret, dseg, dpos, _finish(gamma, dg, direct), _finish(beta, db, direct), dpatch, None)
 
 
 def embed_assemble(word_ids, seg_ids, word_table, seg_table, gamma, beta, pos_table=None, patch_proj=None,
-                   eps=1e-12, p=0.0, seed=0, patch_start=2, out_dtype=torch.bfloat16):
+                   eps=1e-12, p=0.0, seed=0, patch_start=2, out_dtype=torch.bfloat16, example_starts=None,
+                   patch_slots=None):
   """[B,S] ids -> [B,S,H] embeddings in `out_dtype` (see `_EmbedAssembleFn`); `patch_proj`
-  [B, n_patch, H] (projection bias included) is added at positions [patch_start, patch_start+n_patch)."""
+  [B, n_patch, H] (projection bias included) is added at positions [patch_start, patch_start+n_patch).
+  Packed multimodal rows (`example_starts`, `patch_slots` int32 [B,S]; `mmt_embed_fwd_packed`): position s takes the
+  position row `s - start` and row `s - start - patch_start` of entry `slot` of `patch_proj` [E, n_patch, H]."""
   return _EmbedAssembleFn.apply(word_ids, seg_ids, word_table, seg_table, pos_table, gamma, beta, patch_proj,
-                                (eps, p, seed, patch_start, out_dtype))
+                                (eps, p, seed, patch_start, out_dtype, example_starts, patch_slots))
 
 
 # ---- softmax cross-entropy over wide rows (MLM / MPP heads) ---------------------------------------

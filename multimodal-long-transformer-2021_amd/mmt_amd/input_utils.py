@@ -79,6 +79,38 @@ def example_ids_from_lengths(lengths, S: int, device=None) -> torch.Tensor:
   return ids if device is None else ids.to(device)
 
 
+def packed_example_layout(lengths, has_image, S: int, device=None):
+  """Layout of rows packed with multimodal examples, from one list of example lengths per row and one list of "has an
+  image" flags per row.  Returns (example_ids, example_starts, patch_slots, first_positions):
+    example_ids    int32 [B,S]  as `example_ids_from_lengths` (falling to 1, the tail after the last example 0);
+    example_starts int32 [B,S]  first position of the run each position belongs to (the tail is a run too);
+    patch_slots    int32 [B,S]  index of the position's example among the IMAGED examples of the batch, in (row, run)
+                                order -- its row of `patch_embeddings` [E, P^2, F]; -1 for examples without an image
+                                and for the tail;
+    first_positions int64 [E_all, 2]  (row, first position) of every example in (row, run) order, tails not counted."""
+  ids = example_ids_from_lengths(lengths, S)
+  if len(has_image) != len(lengths) or any(len(f) != len(row) for f, row in zip(has_image, lengths)):
+    raise ValueError('has_image must hold one flag per example')
+  starts = torch.zeros_like(ids)
+  slots = torch.full_like(ids, -1)
+  firsts, slot = [], 0
+  for b, (row, flags) in enumerate(zip(lengths, has_image)):
+    at = 0
+    for n, img in zip(row, flags):
+      n = int(n)
+      starts[b, at:at + n] = at
+      firsts.append((b, at))
+      if img:
+        slots[b, at:at + n] = slot
+        slot += 1
+      at += n
+    starts[b, at:] = at
+  first = torch.tensor(firsts, dtype=torch.int64).reshape(-1, 2)
+  if device is not None:
+    ids, starts, slots, first = (t.to(device) for t in (ids, starts, slots, first))
+  return ids, starts, slots, first
+
+
 def synthetic_batch(data_cfg, batch_size: int, device, generator: Optional[torch.Generator] = None,
                     vocab_size: int = 30522, dense_side_inputs: bool = False,
                     ragged: bool = False, task: str = 'pretrain'):

@@ -323,7 +323,7 @@ class RelativeAttention(nn.Module):
       self.relative_emb_table = self.relative_bias_table = None
 
   def forward(self, x, att_mask=None, relative_att_ids=None, pattern=None, valid_len=None,
-              training=False, dropout_seed=0, add_output_bias=True, example_ids=None):
+              training=False, dropout_seed=0, add_output_bias=True, example_ids=None, example_starts=None):
     B, S, H = x.shape
     qkv = _linear(x, self.qkv_weight, self.qkv_bias).view(B, S, 3, self.num_heads, self.head_size)
     emb_p, bias_p = self.relative_emb_table, self.relative_bias_table
@@ -342,7 +342,7 @@ class RelativeAttention(nn.Module):
     p_drop = self.att_dropout_prob if training else 0.0
     out = ops.relative_attention_qkv(
         qkv, emb, bias, rel_grad_sinks=sinks, att_mask=att_mask, relative_att_ids=relative_att_ids,
-        pattern=pattern, valid_len=valid_len, example_ids=example_ids, dropout_p=p_drop,
+        pattern=pattern, valid_len=valid_len, example_ids=example_ids, example_starts=example_starts, dropout_p=p_drop,
         dropout_seed=int(dropout_seed) if p_drop > 0 else 0)
     return _linear(out.reshape(B, S, H), self.output_weight, self.output_bias if add_output_bias else None)
 
@@ -392,7 +392,8 @@ class RelativeTransformerLayers(nn.Module):
   the call contract of `:220-224`: (inputs, att_mask, relative_att_ids, training).  The
   `pattern` / `valid_len` keywords select the structured fast path instead of dense side
   inputs (the build's extension; equal to the dense operator on the materialised mask);
-  `example_ids` (int32 [B,S]) instead of `valid_len` for packed rows."""
+  `example_ids` (int32 [B,S]) instead of `valid_len` for packed rows, with `example_starts` (int32 [B,S]) for packed
+  multimodal examples (ids and grid local to each example; ops.py)."""
 
   def __init__(self, hidden_size, num_hidden_layers, num_attention_heads, intermediate_size=None,
                hidden_act=None, hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1,
@@ -442,15 +443,17 @@ class RelativeTransformerLayers(nn.Module):
     return x
 
   def forward(self, inputs, att_mask=None, relative_att_ids=None, training=False, pattern=None,
-              valid_len=None, dropout_seed=0, example_ids=None):
+              valid_len=None, dropout_seed=0, example_ids=None, example_starts=None):
     x = inputs
     if self.use_fused_kernels and self._fused_ok(x):
       return self._forward_fused(x, training, dropout_seed,
                                  dict(att_mask=att_mask, relative_att_ids=relative_att_ids,
-                                      pattern=pattern, valid_len=valid_len, example_ids=example_ids))
+                                      pattern=pattern, valid_len=valid_len, example_ids=example_ids,
+                                      example_starts=example_starts))
     for i, layer in enumerate(self.layers):
       x = layer(x, training=training, att_mask=att_mask, relative_att_ids=relative_att_ids,
-                pattern=pattern, valid_len=valid_len, example_ids=example_ids, dropout_seed=dropout_seed * 131 + i)
+                pattern=pattern, valid_len=valid_len, example_ids=example_ids, example_starts=example_starts,
+                dropout_seed=dropout_seed * 131 + i)
     return x
 
 

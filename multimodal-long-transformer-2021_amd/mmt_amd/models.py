@@ -17,6 +17,23 @@ def _check_unique(heads):
     raise ValueError('Classification heads should have unique names.')
 
 
+def _packed_heads(model, outputs, seq, first_positions, training, mlm_positions=None, mpp_positions=None):
+  """Head outputs of packed multimodal rows: the row of every example a head reads is `first position + cls_token_idx`,
+  gathered into [E_all, 1, H] -- a batch of one-row sequences, which the heads read at index 0."""
+  if first_positions is None:
+    raise ValueError('packed multimodal rows need first_positions: the heads read one row per example')
+  if mlm_positions is not None:
+    outputs['mlm_logits'] = model.masked_lm(seq, masked_positions=mlm_positions)
+  if mpp_positions is not None:
+    outputs['mpp_logits'] = model.masked_pp(seq, masked_positions=mpp_positions)
+  S = seq.shape[1]
+  for head in model.classification_heads:
+    at = (first_positions[:, 1] + int(head.cls_token_idx)).clamp(max=S - 1)
+    rows = seq[first_positions[:, 0], at]
+    outputs[f'{head.name}_logits'] = head(seq, training=bool(training), gathered=rows)
+  return outputs
+
+
 class MmtPretrainingModel(nn.Module):
 
   def __init__(self, encoder: MmtEncoder, mpp_output_num_classes: Optional[int] = None,
@@ -38,13 +55,20 @@ class MmtPretrainingModel(nn.Module):
 
   def forward(self, word_ids, segment_ids=None, att_mask=None, relative_att_ids=None,
               patch_embeddings=None, mlm_positions=None, mpp_positions=None, training=None,
-              attention_pattern=None, valid_len=None, example_ids=None):
+              attention_pattern=None, valid_len=None, example_ids=None, example_starts=None, patch_slots=None,
+              first_positions=None):
+    """Packed multimodal rows (`example_starts`, `patch_slots`, `first_positions`; `input_utils.packed_example_layout`):
+    every classification head reads row `first position + cls_token_idx` of every example and returns
+    [E_all, classes] in (row, run) order; MLM / MPP positions stay row positions."""
     outputs = dict(self.encoder(word_ids=word_ids, segment_ids=segment_ids, att_mask=att_mask,
                                 relative_att_ids=relative_att_ids,
                                 patch_embeddings=patch_embeddings, training=training,
                                 attention_pattern=attention_pattern, valid_len=valid_len,
-                                example_ids=example_ids))
+                                example_ids=example_ids, example_starts=example_starts, patch_slots=patch_slots,
+                                first_positions=first_positions))
     seq = outputs['sequence_output']
+    if example_starts is not None:
+      return _packed_heads(self, outputs, seq, first_positions, training, mlm_positions, mpp_positions)
     # every head reads a few rows of the sequence output: pick them with one merged gather
     B = seq.shape[0]
     sets, names = [], []
@@ -84,12 +108,17 @@ class MmtClassificationModel(nn.Module):
     _check_unique(self.classification_heads)
 
   def forward(self, word_ids, segment_ids=None, att_mask=None, relative_att_ids=None,
-              patch_embeddings=None, training=None, attention_pattern=None, valid_len=None, example_ids=None):
+              patch_embeddings=None, training=None, attention_pattern=None, valid_len=None, example_ids=None,
+              example_starts=None, patch_slots=None, first_positions=None):
+    """Packed multimodal rows: as `MmtPretrainingModel.forward` -- head logits are [E_all, classes]."""
     outputs = dict(self.encoder(word_ids=word_ids, segment_ids=segment_ids, att_mask=att_mask,
                                 relative_att_ids=relative_att_ids,
                                 patch_embeddings=patch_embeddings, training=training,
                                 attention_pattern=attention_pattern, valid_len=valid_len,
-                                example_ids=example_ids))
+                                example_ids=example_ids, example_starts=example_starts, patch_slots=patch_slots,
+                                first_positions=first_positions))
+    if example_starts is not None:
+      return _packed_heads(self, outputs, outputs['sequence_output'], first_positions, training)
     for head in self.classification_heads:
       outputs[f'{head.name}_logits'] = head(outputs['sequence_output'], training=bool(training))
     return outputs

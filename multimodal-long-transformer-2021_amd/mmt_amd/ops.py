@@ -13,6 +13,12 @@ The segmented term of a pattern comes from `valid_len` (int32 [B]: one example a
 `example_ids` (int32 [B,S]: packed rows, positions attend each other only inside one example -- the reference's
 `make_segmented_att_mask` over `cumsum(long_breakpoints, reverse=True)`, src/data/data_utils.py:305-332; see
 `input_utils.example_ids_from_breakpoints`).  The two are mutually exclusive.
+
+Packed MULTIMODAL examples add `example_starts` (int32 [B,S], with `example_ids` only): the first position of the example
+each position belongs to.  Relative ids, the image grid and the global range are then read at positions local to the
+example (`x - start`), so that an example in a packed row sees what it would see alone at the start of a row
+(`input_utils.packed_example_layout` builds ids and starts).  The structured kernels take this with an image grid and
+without global tokens; with global tokens the dense operator is fed the composed mask and ids.
 """
 from __future__ import annotations
 
@@ -101,9 +107,38 @@ def _index_list(idx: tuple, device) -> torch.Tensor:
 
 
 _DENSE_CACHE = {}
+_ORIGIN_CACHE = {}       # what is derived from the last (example_ids, example_starts) pair: see _origin_cached
 
 
-def _materialized(pattern: 'AttentionPattern', valid_len, B: int, S: int, device, example_ids=None):
+def _origin_cached(slot, key, example_ids, example_starts, build):
+  """`build()` once per (key, ids tensor, starts tensor): the last result of each `slot` is kept, so that the layers
+  of one encoder pass, forward and backward, share it.  As `_DENSE_CACHE`, the entry is tied to the two tensor OBJECTS
+  (weak references + version counters) and dropped when either dies; `clear_pattern_cache` drops it too."""
+  hit = _ORIGIN_CACHE.get(slot)
+  vers = (example_ids._version, example_starts._version)
+  if hit is not None and hit[0] == key and hit[1]() is example_ids and hit[2]() is example_starts and hit[3] == vers:
+    return hit[4]
+  value = build()
+  drop = lambda _r, slot=slot: _ORIGIN_CACHE.pop(slot, None) if (_ORIGIN_CACHE.get(slot) or (None, None, None))[1:3].count(_r) else None
+  _ORIGIN_CACHE[slot] = (key, weakref.ref(example_ids, drop), weakref.ref(example_starts, drop), vers, value)
+  return value
+
+
+def compose_origin(pat_mask, pat_ids, example_ids, example_starts):
+  """Dense [B,S,S] mask and relative ids of packed examples with a per-example origin, from the single-example [S,S]
+  pattern mask / ids: both gathered at the local positions (lq, lk) = (q - start[q], k - start[k]), clamped into
+  [0, S), and ANDed with the equality of the example ids (ids outside an example are 0).  Plain torch, any device."""
+  S = example_ids.shape[1]
+  pos = torch.arange(S, device=example_ids.device)
+  loc = (pos[None] - example_starts.long()).clamp_(0, S - 1)
+  same = example_ids[:, :, None] == example_ids[:, None, :]
+  lq, lk = loc[:, :, None], loc[:, None, :]
+  mask = pat_mask[lq, lk].to(torch.int32) * same.to(torch.int32)
+  ids = None if pat_ids is None else torch.where(same, pat_ids[lq, lk], torch.zeros_like(pat_ids[:1, :1])).to(torch.int32)
+  return mask, ids
+
+
+def _materialized(pattern: 'AttentionPattern', valid_len, B: int, S: int, device, example_ids=None, example_starts=None):
   """(att_mask, relative_att_ids) int32 [B,S,S] of a pattern the structured kernels do not take (a listed global set;
   with example ids also an image grid), through `mmt_side_inputs`;
   the last result is kept, so that the layers of one encoder pass (same pattern, same valid_len tensor) share it.
@@ -111,8 +146,20 @@ def _materialized(pattern: 'AttentionPattern', valid_len, B: int, S: int, device
   a later batch's tensor that the caching allocator places at the same address is a different object and misses;
   when the tensor dies the entry (two B*S*S int32 tensors) is dropped with it.
   With `example_ids` the pattern mask is built without a length and `ids[:, :, None] == ids[:, None, :]` is ANDed into
-  it on the device; the entry is then tied to the ids tensor in the same way."""
+  it on the device; the entry is then tied to the ids tensor in the same way.  With `example_starts` as well the
+  single-example [S,S] pattern is built once and gathered at the local positions (`compose_origin`); the last result is
+  kept in the same manner, tied to both tensors (`_origin_cached`)."""
   packed = example_ids is not None
+  if example_starts is not None:
+    def build():
+      one = torch.full((1,), S, dtype=torch.int32, device=device)
+      pm = torch.empty((1, S, S), dtype=torch.int32, device=device)
+      pi = torch.empty((1, S, S), dtype=torch.int32, device=device) if pattern.id_mode != _lib.MMT_IDS_NONE else None
+      with torch.cuda.device(device):
+        _lib.check(_lib.lib().mmt_side_inputs(pattern.to_desc(None, device), 1, S, one.data_ptr(), torch.zeros_like(one).data_ptr(),
+                                              1, pm.data_ptr(), None if pi is None else pi.data_ptr(), None, _stream_ptr(device)))
+      return compose_origin(pm[0], None if pi is None else pi[0], example_ids, example_starts)
+    return _origin_cached('dense', (pattern, B, S, str(device)), example_ids, example_starts, build)
   if packed:
     valid_len = example_ids           # the tensor the entry is tied to
   key = (pattern, B, S, str(device), packed)
@@ -146,23 +193,29 @@ def _materialized(pattern: 'AttentionPattern', valid_len, B: int, S: int, device
 def clear_pattern_cache() -> None:
   """Drops the cached dense side inputs of listed global sets (and the device copies of their index lists)."""
   _DENSE_CACHE.clear()
+  _ORIGIN_CACHE.clear()
   _INDEX_LISTS.clear()
 
 
-def _resolve_pattern(pattern, att_mask, rel_ids, valid_len, q, example_ids=None):
+def _resolve_pattern(pattern, att_mask, rel_ids, valid_len, q, example_ids=None, example_starts=None):
   """Listed global sets: contiguous runs become the range form, anything else the dense operator's inputs.  So does,
-  with example ids, a pattern with an image grid (the structured kernels refuse that pair)."""
+  with example ids, a pattern with an image grid (the structured kernels refuse that pair) -- unless example starts are
+  given: they take the grid on the structured kernels, and send global tokens of any form to the dense operator."""
   if example_ids is not None and (att_mask is not None or rel_ids is not None):
     raise ValueError('example_ids go with a pattern: dense att_mask/relative_att_ids already hold the segmented mask')
   if pattern is None:
     return pattern, att_mask, rel_ids
   if pattern.global_index is not None:
     pattern = pattern.normalized()
-  if pattern.global_index is None and not (example_ids is not None and pattern.grid_radius > 0):
+  if example_starts is not None:
+    structured = pattern.global_index is None and pattern.n_global == 0
+  else:
+    structured = pattern.global_index is None and not (example_ids is not None and pattern.grid_radius > 0)
+  if structured:
     return pattern, att_mask, rel_ids
   if att_mask is not None or rel_ids is not None:
     raise ValueError('pass either dense att_mask/relative_att_ids or a pattern, not both')
-  mask, ids = _materialized(pattern, valid_len, q.shape[0], q.shape[1], q.device, example_ids)
+  mask, ids = _materialized(pattern, valid_len, q.shape[0], q.shape[1], q.device, example_ids, example_starts)
   return None, mask, ids
 
 
@@ -200,8 +253,14 @@ def _sync_words(device, stream_ptr: int, words: int) -> torch.Tensor:
   return t
 
 
+def _origin_planes(example_ids, example_starts) -> torch.Tensor:
+  """int32 [B,2,S] -- ids and starts as MMT_FLAG_EXAMPLE_STARTS wants them; the last pair's is kept (`_origin_cached`)."""
+  return _origin_cached('planes', None, example_ids, example_starts,
+                        lambda: torch.stack([example_ids, example_starts], 1).contiguous())
+
+
 def _make_desc(q, k, v, out, R, pattern, valid_len, scale, mask_value, scale_before_add,
-               dropout_p, dropout_seed, tuning=0, example_ids=None) -> _lib.AttnDesc:
+               dropout_p, dropout_seed, tuning=0, example_ids=None, example_starts=None) -> _lib.AttnDesc:
   B, S, N, D = q.shape
   d = _lib.AttnDesc()
   d.B, d.S, d.N, d.D, d.R = B, S, N, D, R
@@ -217,6 +276,9 @@ def _make_desc(q, k, v, out, R, pattern, valid_len, scale, mask_value, scale_bef
   if example_ids is not None:        # packed examples: the ids travel in the valid_len slot, named by the flag
     d.flags |= _lib.MMT_FLAG_EXAMPLE_IDS
     valid_len = example_ids
+    if example_starts is not None:   # ... and with starts, both planes of one [B,2,S] tensor (kept alive by the descriptor)
+      d.flags |= _lib.MMT_FLAG_EXAMPLE_STARTS
+      valid_len = d._origin_planes = _origin_planes(example_ids, example_starts)
   d.mask = (pattern or AttentionPattern(id_mode=_lib.MMT_IDS_NONE)).to_desc(valid_len, q.device)
   d.tuning = int(tuning)
   sync = _sync_words(q.device, _stream_ptr(q.device), B * N)
@@ -224,7 +286,7 @@ def _make_desc(q, k, v, out, R, pattern, valid_len, scale, mask_value, scale_bef
   return d
 
 
-def _check_inputs(q, k, v, rel_emb, rel_bias, att_mask, rel_ids, valid_len, example_ids=None):
+def _check_inputs(q, k, v, rel_emb, rel_bias, att_mask, rel_ids, valid_len, example_ids=None, example_starts=None):
   if not q.is_cuda:
     raise RuntimeError('relative_attention runs on the GPU only (no CPU fallback)')
   for t in (k, v):
@@ -253,6 +315,12 @@ def _check_inputs(q, k, v, rel_emb, rel_bias, att_mask, rel_ids, valid_len, exam
     if (not torch.is_tensor(example_ids) or example_ids.dtype != torch.int32 or example_ids.shape != (B, S)
         or not example_ids.is_contiguous() or example_ids.device != q.device):
       raise ValueError('example_ids must be a contiguous int32 [B,S] tensor on the device of q')
+  if example_starts is not None:
+    if example_ids is None:
+      raise ValueError('example_starts needs example_ids: a start says where the example of that id begins')
+    if (not torch.is_tensor(example_starts) or example_starts.dtype != torch.int32 or example_starts.shape != (B, S)
+        or not example_starts.is_contiguous() or example_starts.device != q.device):
+      raise ValueError('example_starts must be a contiguous int32 [B,S] tensor on the device of q')
   return R
 
 
@@ -260,12 +328,13 @@ def relative_attention_forward(q, k, v, rel_emb=None, rel_bias=None, *, att_mask
                                relative_att_ids=None, pattern: Optional[AttentionPattern] = None,
                                valid_len=None, scale=None, mask_value=-10000.0,
                                scale_before_add=False, dropout_p=0.0, dropout_seed=0,
-                               return_lse=True, tuning=0, example_ids=None):
+                               return_lse=True, tuning=0, example_ids=None, example_starts=None):
   """Forward only.  Returns (out [B,S,N,D] in q.dtype, lse fp32 [B,N,S]).  `tuning`: `_lib.MMT_TUNE_*` kernel-selection
   switches (0 = the library's defaults; the parity tests use them to reach every kernel).  `example_ids`: contiguous
-  int32 [B,S] on the device of q, instead of `valid_len` (packed rows; module docstring)."""
-  R = _check_inputs(q, k, v, rel_emb, rel_bias, att_mask, relative_att_ids, valid_len, example_ids)
-  pattern, att_mask, relative_att_ids = _resolve_pattern(pattern, att_mask, relative_att_ids, valid_len, q, example_ids)
+  int32 [B,S] on the device of q, instead of `valid_len` (packed rows; module docstring); `example_starts`: likewise, the
+  first position of each position's example (packed multimodal examples)."""
+  R = _check_inputs(q, k, v, rel_emb, rel_bias, att_mask, relative_att_ids, valid_len, example_ids, example_starts)
+  pattern, att_mask, relative_att_ids = _resolve_pattern(pattern, att_mask, relative_att_ids, valid_len, q, example_ids, example_starts)
   dense = att_mask is not None or relative_att_ids is not None
   if dense and pattern is not None:
     raise ValueError('pass either dense att_mask/relative_att_ids or a pattern, not both')
@@ -273,7 +342,7 @@ def relative_attention_forward(q, k, v, rel_emb=None, rel_bias=None, *, att_mask
   out = torch.empty((B, S, N, D), dtype=q.dtype, device=q.device)
   lse = torch.empty((B, N, S), dtype=torch.float32, device=q.device) if return_lse else None
   desc = _make_desc(q, k, v, out, R, pattern, valid_len, scale, mask_value, scale_before_add,
-                    dropout_p, dropout_seed, tuning, None if dense else example_ids)
+                    dropout_p, dropout_seed, tuning, None if dense else example_ids, None if dense else example_starts)
   L = _lib.lib()
   ws_bytes = 0 if dense else L.mmt_workspace_bytes(desc)
   ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=q.device)
@@ -315,7 +384,7 @@ def relative_attention_backward(dout, q, k, v, rel_emb, rel_bias, out, lse, *, a
                                 relative_att_ids=None, pattern: Optional[AttentionPattern] = None,
                                 valid_len=None, scale=None, mask_value=-10000.0,
                                 scale_before_add=False, dropout_p=0.0, dropout_seed=0, grads_out=None,
-                                rel_grads_accum=None, tuning=0, example_ids=None):
+                                rel_grads_accum=None, tuning=0, example_ids=None, example_starts=None):
   """Backward of `relative_attention_forward` (recomputes P from `lse`).
 
   Returns (dq, dk, dv, drel_emb, drel_bias); the table gradients are fp32.  `grads_out` may
@@ -324,10 +393,10 @@ def relative_attention_backward(dout, q, k, v, rel_emb, rel_bias, out, lse, *, a
   ValueError.  `rel_grads_accum` = (demb [R,N,D], dbias [R,N] | None), fp32
   and contiguous: the table gradients are ADDED to these buffers (the fp32 master gradients) and
   returned as such."""
-  R = _check_inputs(q, k, v, rel_emb, rel_bias, att_mask, relative_att_ids, valid_len, example_ids)
-  pattern, att_mask, relative_att_ids = _resolve_pattern(pattern, att_mask, relative_att_ids, valid_len, q, example_ids)
+  R = _check_inputs(q, k, v, rel_emb, rel_bias, att_mask, relative_att_ids, valid_len, example_ids, example_starts)
+  pattern, att_mask, relative_att_ids = _resolve_pattern(pattern, att_mask, relative_att_ids, valid_len, q, example_ids, example_starts)
   if att_mask is not None or relative_att_ids is not None:
-    example_ids = None              # the dense operator: the materialised mask holds the ids' term
+    example_ids = example_starts = None     # the dense operator: the materialised mask holds the ids' term
   B, S, N, D = q.shape
   dout = dout if dout.stride() == out.stride() else dout.contiguous()
   if out.stride() != dout.stride():
@@ -344,7 +413,7 @@ def relative_attention_backward(dout, q, k, v, rel_emb, rel_bias, out, lse, *, a
       q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
       dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
   desc = _make_desc(q, k, v, out, R, pattern, valid_len, scale, mask_value, scale_before_add,
-                    dropout_p, dropout_seed, tuning, example_ids)
+                    dropout_p, dropout_seed, tuning, example_ids, example_starts)
   if rel_grads_accum is not None and R:
     drel_emb, drel_bias = rel_grads_accum
     for t, shape in ((drel_emb, (R, N, D)), (drel_bias, (R, N))):
@@ -390,7 +459,7 @@ class _RelativeAttentionFn(torch.autograd.Function):
 
 def relative_attention(q, k, v, rel_emb=None, rel_bias=None, **kw):
   """Differentiable QkvRelativeAttention (see module docstring); kwargs as
-  `relative_attention_forward` (att_mask / relative_att_ids or pattern / valid_len or example_ids, scale,
+  `relative_attention_forward` (att_mask / relative_att_ids or pattern / valid_len or example_ids (+ example_starts), scale,
   mask_value, scale_before_add, dropout_p, dropout_seed)."""
   kw.pop('return_lse', None)
   return _RelativeAttentionFn.apply(q, k, v, rel_emb, rel_bias, kw)

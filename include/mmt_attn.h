@@ -48,8 +48,16 @@ enum {
   MMT_IDS_NONE = 0, /* no relative term                                                   */
   MMT_IDS_1D = 1,   /* etcmodel RelativePositionGenerator over the whole sequence
                        (data_utils.py:300-301): id = min(j-i,m) | m+min(i-j,m)           */
-  MMT_IDS_2D = 2    /* MmtRelativePositionGenerator (feature_utils.py:114-184): 2-D ids
+  MMT_IDS_2D = 2,   /* MmtRelativePositionGenerator (feature_utils.py:114-184): 2-D ids
                        for the first P*P positions, part ids across, 1-D ids for the rest */
+  MMT_IDS_2D_IMAGE = 3 /* MMT_IDS_2D with the image where the patches are: at [g, g + P*P), g = the first-
+                       image-position field of mask.image_grid (bits 8-30, the bits the grid term reads;
+                       read here with grid radius 0 as well: MMT_IMAGE_GRID(0, g)); g + P*P <= S.
+                       rel_id(q,k) = the MMT_IDS_2D id of (q-g, k-g) with img(x) = (unsigned)(x-g) < P*P:
+                       image x image the 2-D id of the patch pair, image row x other key text_part_id, other
+                       row x image key image_part_id, else the 1-D id of k-q -- [0, g) counts as text.
+                       g = 0 is MMT_IDS_2D bit for bit.  With MMT_FLAG_EXAMPLE_STARTS g is local to each
+                       example.  Not the reference's ids (it keeps the image at 0 behind [CLS][PATCH]).  */
 };
 
 /* flags */
@@ -102,7 +110,8 @@ enum {
  *   grid(q,k) = a > 0 && img(q) && img(k) && |row(q)-row(k)| <= a && |col(q)-col(k)| <= a  (ABI 4, image_grid):
  *   img(x) = g <= x < g + P*P, row(x) = (x-g) / P, col(x) = (x-g) % P, P = patches_per_row: the 2-D
  *   neighbourhood of the image patches (raster order, no wrap across rows).  Symmetric in (q,k).  */
-/* image_grid word of mmt_mask_desc: grid radius a (1..8) and first image position g */
+/* image_grid word of mmt_mask_desc: grid radius a (1..8) and first image position g; MMT_IMAGE_GRID(0, g) is
+ * meaningful with MMT_IDS_2D_IMAGE (no grid term, the image of the 2-D ids at g) and is no grid otherwise */
 #define MMT_IMAGE_GRID(a, g) ((int32_t)(((uint32_t)(a) & 0xFFu) | (((uint32_t)(g) & 0x7FFFFFu) << 8)))
 typedef struct mmt_mask_desc {
   const int32_t* valid_len; /* [B] device ints (num_image_wordpieces + num_text_wordpieces),
@@ -114,11 +123,12 @@ typedef struct mmt_mask_desc {
   int32_t n_global;         /* contiguous range of global tokens; 0 = none           */
   int32_t id_mode;          /* MMT_IDS_*                                             */
   int32_t max_dist;         /* relative_pos_max_distance m (encoders.py:60)          */
-  int32_t patches_per_row;  /* P  = image_size // patch_size        (MMT_IDS_2D)     */
-  int32_t core_layers;      /* r  = relative_att_num_core_layers    (MMT_IDS_2D)     */
+  int32_t patches_per_row;  /* P  = image_size // patch_size        (MMT_IDS_2D, MMT_IDS_2D_IMAGE) */
+  int32_t core_layers;      /* r  = relative_att_num_core_layers    (MMT_IDS_2D, MMT_IDS_2D_IMAGE) */
   int32_t image_grid;       /* ABI 4, in what was padding: 0 = no grid term; else grid radius a (bits 0-7) |
                                first image position g (bits 8-30); P = patches_per_row.  Callers must zero it.
-                               MMT_IMAGE_GRID(a, g) builds it; a is built up to 8.      */
+                               MMT_IMAGE_GRID(a, g) builds it; a is built up to 8.  a = 0 is no grid term; g is
+                               then read by MMT_IDS_2D_IMAGE only (the image origin of its ids).  */
   const int32_t* global_index; /* NULL: the contiguous range above; else n_global ascending,
                                distinct positions in [0, S) on the device (global_start
                                is ignored).  ABI 2.                                     */

@@ -20,6 +20,17 @@
 
 namespace mmt {
 
+// MMT_IMAGE_TU (this file compiled as attn_bwd_image.hip): as attn_fwd.hip's -- the id-generating instantiations with the
+// image origin of MMT_IDS_2D_IMAGE read by rel_id, under kernel names of their own.
+#ifdef MMT_IMAGE_TU
+#define attn_bwd_dq_kernel attn_bwd_dq_image_kernel
+#define attn_bwd_dkv_kernel attn_bwd_dkv_image_kernel
+#define pair_mask_col pair_mask_col_image
+constexpr bool kImageTU = true;
+#else
+constexpr bool kImageTU = false;
+#endif
+
 // LDS per wave: T table, dT table (K4a) / second tile (K4b), one or two 32 x 2 DH B tiles.
 template <typename T, int Rp, int DH = 64> struct BwdLds {
   static constexpr int kTab = (32 * kTStride(Rp) * 4 + 15) & ~15;
@@ -75,7 +86,7 @@ __device__ __forceinline__ void pair_mask_col(const P& p, int b, int valid_len, 
     if constexpr (ORG) keep = pattern_mask_origin<GRID>(p.pat, p.grid, seg_ids, q, k, lq, lk);
     else if constexpr (PACK) keep = pattern_mask_packed(p.pat, seg_ids, q, k);
     else keep = pattern_mask<GRID>(p.pat, p.grid, valid_len, q, k);
-    if (p.pat.id_mode) id = ORG ? rel_id(p.pat, lq, lk) : rel_id(p.pat, q, k);
+    if (p.pat.id_mode) id = ORG ? rel_id<kImageTU>(p.pat, lq, lk, p.ids_go) : rel_id<kImageTU>(p.pat, q, k, p.ids_go);
     if ((unsigned)id < (unsigned)p.R) col = id;
   } else {
     const int d = k - q;
@@ -869,7 +880,21 @@ static hipError_t launch_bwd_rp(const BwdParams& p, hipStream_t st) {
   return launch_bwd_one<T, MODE, 128, GEN, GRID, DH, PACK, ORG>(p, st);
 }
 
-#ifdef MMT_ORIGIN_TU
+#if defined(MMT_IMAGE_TU)
+// The MMT_IDS_2D_IMAGE instantiations (this file compiled as attn_bwd_image.hip), as launch_attn_fwd_image's.
+template <typename T, int DH>
+static hipError_t launch_bwd_image_t(const BwdParams& p, int pack, hipStream_t st) {
+  if (pack == kPackOrigin)
+    return p.grid.ga > 0 ? launch_bwd_rp<T, kBand, true, true, DH, true, true>(p, st) : launch_bwd_rp<T, kBand, true, false, DH, true, true>(p, st);
+  if (pack) return launch_bwd_rp<T, kBand, true, false, DH, true>(p, st);
+  return p.grid.ga > 0 ? launch_bwd_rp<T, kBand, true, true, DH>(p, st) : launch_bwd_rp<T, kBand, true, false, DH>(p, st);
+}
+
+hipError_t launch_attn_bwd_image(const BwdParams& p, bool bf16, int pack, hipStream_t st) {
+  if (p.D == 128) return bf16 ? launch_bwd_image_t<__bf16, 128>(p, pack, st) : launch_bwd_image_t<float, 128>(p, pack, st);
+  return bf16 ? launch_bwd_image_t<__bf16, 64>(p, pack, st) : launch_bwd_image_t<float, 64>(p, pack, st);
+}
+#elif defined(MMT_ORIGIN_TU)
 // The per-example-origin instantiations (this file compiled as attn_bwd_origin.hip), as launch_attn_fwd_origin's.
 template <typename T, int DH>
 static hipError_t launch_bwd_origin_t(const BwdParams& p, hipStream_t st) {
@@ -921,6 +946,9 @@ hipError_t launch_attn_bwd(const BwdParams& p, int mode, bool bf16, int pack, hi
   // head size 128, the image grid and packed examples: the general kernels only (the lean kernels are built for head size
   // 64 and for valid_len as the segmented term)
   pack = mode == kBand ? pack : kPackNone;
+  // MMT_IDS_2D_IMAGE on the general kernels (attn_bwd_image.hip): whatever the lean kernels below do not take
+  const bool lean_takes = mode == kBand && bf16 && !pack && p.D == 64 && p.grid.ga == 0 && p.lean2d;
+  if (mode == kBand && p.ids_go != 0 && p.pat.id_mode == 2 && !lean_takes) return launch_attn_bwd_image(p, bf16, pack, st);
   if (pack == kPackOrigin) return launch_attn_bwd_origin(p, bf16, st);   // per-example origin: attn_bwd_origin.hip
   if (p.D == 128) return bf16 ? launch_bwd_t<__bf16, 128>(p, mode, pack, st) : launch_bwd_t<float, 128>(p, mode, pack, st);
   if (mode == kBand && bf16 && !pack && p.grid.ga == 0 && (p.pat.id_mode == 0 || (p.perm_1d && p.Rp <= 64) || p.lean2d)) return launch_attn_bwd_band_bf16(p, st);

@@ -40,7 +40,7 @@ __device__ __forceinline__ void stage_e_image(unsigned char* elds, const void* e
 #pragma unroll
   for (int c0 = 0; c0 < Rp * 8; c0 += 256) {
     const int ci = c0 + tid, row = ci >> 3, ch = ci & 7, rt = row & 31;
-    const bf16x8 e = buf16(re, (unsigned)(REL == 2 ? row : icol(m, row)) * es1b + ch * 16, 0u);   // 2-D ids: columns in id order
+    const bf16x8 e = buf16(re, (unsigned)(REL >= 2 ? row : icol(m, row)) * es1b + ch * 16, 0u);   // 2-D ids: columns in id order
     *reinterpret_cast<bf16x8*>(elds + (row >> 5) * 4096 + rt * 128 + ((((ch >> 2) ^ ((rt >> 1) & 1))) << 6) + (ch & 3) * 16) = e;
   }
 }
@@ -87,11 +87,12 @@ __device__ __forceinline__ void buf_store16(__amdgpu_buffer_rsrc_t rs, unsigned 
 // =========================================================================================
 // dQ, delta, dRel (lane = query row).
 // =========================================================================================
-template <int Rp, int REL>         // REL: 0 none, 1 = 1-D ids (permuted table), 2 = 2-D ids (columns in id order, attn_lean.h)
+template <int Rp, int REL>         // REL: 0 none, 1 = 1-D ids (permuted table), 2 = 2-D ids (columns in id order, attn_lean.h), 3 = 2-D ids with the image at ids_go
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_band_bf16_kernel(const BwdParams p) {
   using T = __bf16;
   using L = LeanLds<Rp>;
   constexpr bool HAS_REL = REL != 0;
+  constexpr bool IMG = REL == 3;          // 2-D ids with the image at p.ids_go (MMT_IDS_2D_IMAGE)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -107,7 +108,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_band_bf16_kernel(const Bwd
   float* dtab = reinterpret_cast<float*>(wl + L::kTab);
   unsigned char* xlds = wl + L::kTab + 32 * dstride * 4;
   unsigned char* vlds = xlds + L::kTile;
-  int* lut = reinterpret_cast<int*>(smem + kEImg + 4 * kWave);        // REL == 2: one per workgroup
+  int* lut = reinterpret_cast<int*>(smem + kEImg + 4 * kWave);        // REL >= 2: one per workgroup
 
 #ifdef MMT_STAMP
   long long* dbg = (p.dbg && (p.dbg_mode & 1) == 0 && blockIdx.x == 900) ? p.dbg + wave * 32 : nullptr;
@@ -210,7 +211,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_band_bf16_kernel(const Bwd
     QSTAMP(1);
     if (HAS_REL) {           // every wave of the workgroup takes part (the plane, hence E, is the same for all four)
       stage_e_image<Rp, REL>(elds, p.emb, n, p.N, p.R, p.pat.m, threadIdx.x);
-      if (REL == 2) build_lut2d<Rp>(lut, p.pat, p.R, threadIdx.x, 256);
+      if (REL >= 2) build_lut2d<Rp>(lut, p.pat, p.R, threadIdx.x, 256);
       __syncthreads();
     }
     QSTAMP(2);
@@ -231,10 +232,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_band_bf16_kernel(const Bwd
   if (HAS_REL) {
     float* bias_ts = reinterpret_cast<float*>(xlds);
     if (lane < Rp) {
-      const int idc = REL == 2 ? lane : icol(m, lane);
+      const int idc = REL >= 2 ? lane : icol(m, lane);
       bias_ts[lane] = (p.bias && idc < p.R) ? (float)reinterpret_cast<const T*>(p.bias)[(long)idc * p.N + n] * p.tscale : 0.f;   // by column
     }
-    if (REL == 2) tab[r * kTStride(Rp) + kZeroCol(Rp)] = 0.f;
+    if (REL >= 2) tab[r * kTStride(Rp) + kZeroCol(Rp)] = 0.f;
     wave_lds_sync();
 #pragma unroll
     for (int rb = 0; rb < Rp / 32; ++rb) {
@@ -273,8 +274,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_band_bf16_kernel(const Bwd
   const int trow_addr = (int)(unsigned)(size_t)(__attribute__((address_space(3))) float*)(tab + r * kTStride(Rp));
   const SeedPair sd = effective_seed(p.seed_lo, p.seed_hi, p.epoch);
   const uint32_t drop_base = drop_row_base(sd.lo, sd.hi, (uint32_t)bn, (uint32_t)q);
-  // REL == 2: this lane's query on the patch grid, LDS addresses of the look-up table and of the lane's dRel row
-  const int xq2 = (int)__umulhi((unsigned)q, p.pat.magicP), yq2 = q - xq2 * p.pat.P;
+  // REL >= 2: this lane's query on the patch grid, LDS addresses of the look-up table and of the lane's dRel row
+  const int go = IMG ? p.ids_go : 0;
+  const int xq2 = (int)__umulhi((unsigned)(q - go), p.pat.magicP), yq2 = q - go - xq2 * p.pat.P;
   const int lut_addr = lds_addr(lut), dtrow_addr = lds_addr(dtrow);
   const int lim2 = p.pat.r + 1, nlim2 = -lim2;
 
@@ -329,8 +331,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_band_bf16_kernel(const Bwd
       const bool neg = kk < q;                             // beyond the radius on that side: clipped id (1-D)
       int col4_i = 0;                                      // 2-D ids: byte offset of the pair's table column
       float rel_i = HAS_REL ? (neg ? relfn : relfp) : 0.f;
-      if (REL == 2) {
-        col4_i = 4 * col2d<Rp>(p.pat, p.R, q, min(kk, p.S - 1));
+      if (REL >= 2) {
+        col4_i = 4 * col2d<Rp, IMG>(p.pat, go, p.R, q, min(kk, p.S - 1));
         rel_i = *(lds_cfp)(size_t)(unsigned)(trow_addr + col4_i);
       }
       float sc = fmaf(c[i], p.sscale, rel_i);
@@ -340,7 +342,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_band_bf16_kernel(const Bwd
       if (p.drop_thresh) f = drop_bits16(drop_base, (uint32_t)kk) >= p.drop_thresh ? p.inv_keep : 0.f;
       ds[i] = pr * (dp[i] * f - delta);
       pd4[i] = f != 0.f ? pr : -pr;
-      if (REL == 2) lds_add_f32(dtrow_addr + col4_i, ds[i] * p.rel_gscale);       // (0 when the pair is not present)
+      if (REL >= 2) lds_add_f32(dtrow_addr + col4_i, ds[i] * p.rel_gscale);       // (0 when the pair is not present)
       else if (HAS_REL) { far_neg_acc += neg ? ds[i] : 0.f; far_pos_acc += neg ? 0.f : ds[i]; }
     }
     if (p.ho) {              // the strip of this q block: rows x the 8 global keys (zeros where a band tile holds the pair)
@@ -405,20 +407,20 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_band_bf16_kernel(const Bwd
     }
     const bool no_gkey = p.pat.ng == 0 || k0 + 31 < p.pat.g0 || k0 >= p.pat.g0 + p.pat.ng;
     const TileClass tc = classify_tile(q0, k0, p.S, valid_len, W, m, ignore_band, no_gkey);
-    const bool one_id = REL != 2 && (!HAS_REL || tc.far_neg || tc.far_pos);
+    const bool one_id = REL < 2 && (!HAS_REL || tc.far_neg || tc.far_pos);
     const float relc = HAS_REL ? (tc.far_neg ? relfn : relfp) : 0.f;
     const int dbase = k0 - q + 4 * h;
 
     float pr[16];
-    int col4[16];                                               // REL == 2: byte offset of each element's table column
-    if (REL == 2) {
-      if (q0 + 31 < p.pat.I && k0 + 31 < p.pat.I && p.pat.P >= 32) {     // image x image: look-up table
-        const Ids2dTile t2 = ids2d_tile<1>(p.pat, lut_addr, k0 + 4 * h, xq2, yq2);
+    int col4[16];                                               // REL >= 2: byte offset of each element's table column
+    if (REL >= 2) {
+      if (tile_in_image<IMG>(p.pat, go, q0) && tile_in_image<IMG>(p.pat, go, k0) && p.pat.P >= 32) {     // image x image: look-up table
+        const Ids2dTile t2 = ids2d_tile<1>(p.pat, lut_addr, k0 - go + 4 * h, xq2, yq2);
 #pragma unroll
         for (int i = 0; i < 16; ++i) col4[i] = ids2d_col4<1>(t2, (i & 3) + 8 * (i >> 2), nlim2, lim2);
       } else {
 #pragma unroll
-        for (int i = 0; i < 16; ++i) col4[i] = 4 * col2d<Rp>(p.pat, p.R, q, k0 + 4 * h + (i & 3) + 8 * (i >> 2));
+        for (int i = 0; i < 16; ++i) col4[i] = 4 * col2d<Rp, IMG>(p.pat, go, p.R, q, k0 + 4 * h + (i & 3) + 8 * (i >> 2));
       }
       float sc[16];
 #pragma unroll
@@ -520,7 +522,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_band_bf16_kernel(const Bwd
       hold_so = split_item ? (unsigned)(k0 >> 5) * kHoStrip : (unsigned)((q0 >> 5) * p.ho_slots + it) * kHoTile;
     }
     // dRel (unscaled; rel_gscale applied at the flush / in the stores)
-    if (REL == 2) {                 // many keys of a row share an id: accumulate in the lane's dRel row
+    if (REL >= 2) {                 // many keys of a row share an id: accumulate in the lane's dRel row
       // LDS float atomics retire about one lane every three cycles on this chip (a tile's 16 x 64 updates cost more
       // than the rest of the tile), so equal neighbours are merged first: along a row the ids come in runs -- a
       // direction id for every key left of the core window, the 2r + 1 core ids, another direction id to the
@@ -583,7 +585,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_band_bf16_kernel(const Bwd
     float* pt = p.part_dtab + slot * (32 * Rp);
     for (int i = lane; i < 32 * Rp; i += 64) {
       const int rr = i / Rp, id = i - rr * Rp;
-      const int col = REL == 2 ? id : tcol(1, m, id);
+      const int col = REL >= 2 ? id : tcol(1, m, id);
       pt[i] = col < dstride ? dtab[rr * dstride + col] : 0.f;
     }
     return;
@@ -641,7 +643,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_band_bf16_kernel(const Bwd
 #pragma unroll
   for (int rb = 0; rb < Rp / 32; ++rb) {
     const int id = rb * 32 + r;
-    const int col = REL == 2 ? id : tcol(1, m, id);
+    const int col = REL >= 2 ? id : tcol(1, m, id);
     f32x16 e0 = {0}, e1 = {0};
     float bsum = 0.f;
     float vals[16];
@@ -708,6 +710,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_band_bf16_kernel(const Bw
   using T = __bf16;
   using L = LeanLds<Rp>;
   constexpr bool HAS_REL = REL != 0;
+  constexpr bool IMG = REL == 3;          // 2-D ids with the image at p.ids_go (MMT_IDS_2D_IMAGE)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -721,7 +724,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_band_bf16_kernel(const Bw
   float* bias_ts = reinterpret_cast<float*>(dolds + L::kTile);
   float* rowc = bias_ts + Rp;            // per row of the current q tile: [0,32) lse*log2e, [32,64) delta,
                                          // [64,96) rel(clipped, d<=-m) - lse2, [96,128) rel(clipped, d>=m) - lse2
-  int* lut = reinterpret_cast<int*>(smem + kEImg + 4 * L::kDkv);       // REL == 2: one per workgroup
+  int* lut = reinterpret_cast<int*>(smem + kEImg + 4 * L::kDkv);       // REL >= 2: one per workgroup
 
   if (p.comb_in_next) {          // trailing blocks: the dQ combine of the global rows (one row per wave)
     const int per_bn0 = (p.n_chunks * p.n_gblk + 3) >> 2;
@@ -785,9 +788,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_band_bf16_kernel(const Bw
   // The (<= 8) global query ROWS outside this wave's band q tiles: a PEELED step before the walk instead of a sixth
   // q tile (registers 0..3 only; one load instruction each for their Q and dO rows) -- the mirror of the dQ pass's
   // peeled global keys.
-  const bool peel = REL != 2 && (p.peel_gkeys & 2) && !split_item && live &&
+  const bool peel = REL < 2 && (p.peel_gkeys & 2) && !split_item && live &&
                     !(p.pat.g0 >= w.b0 * 32 && p.pat.g0 + p.pat.ng - 1 <= (w.b0 + w.lenB) * 32 - 1);
-  if (REL != 2 && (p.peel_gkeys & 2) && !split_item) { w.lenA = 0; w.lenC = 0; }
+  if (REL < 2 && (p.peel_gkeys & 2) && !split_item) { w.lenA = 0; w.lenC = 0; }
   const int n_it = live ? w.count() : 0;
 
   Frag<T> kf, vf;
@@ -820,20 +823,21 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_band_bf16_kernel(const Bw
   KSTAMP(1);
   if (HAS_REL) {           // E image after the item's loads are in flight (see the dQ kernel)
     stage_e_image<Rp, REL>(elds, p.emb, n, p.N, p.R, p.pat.m, threadIdx.x);
-    if (REL == 2) build_lut2d<Rp>(lut, p.pat, p.R, threadIdx.x, 256);
+    if (REL >= 2) build_lut2d<Rp>(lut, p.pat, p.R, threadIdx.x, 256);
     __syncthreads();
   }
   KSTAMP(2);
   if (!live) return;
   if (HAS_REL) {
     if (lane < Rp) {
-      const int idc = REL == 2 ? lane : icol(m, lane);
+      const int idc = REL >= 2 ? lane : icol(m, lane);
       bias_ts[lane] = (p.bias && idc < p.R) ? (float)reinterpret_cast<const T*>(p.bias)[(long)idc * p.N + n] * p.tscale : 0.f;   // by column
     }
   }
   wave_lds_sync();
-  // REL == 2: this lane's key on the patch grid
-  const int xk2 = (int)__umulhi((unsigned)k, p.pat.magicP), yk2 = k - xk2 * p.pat.P;
+  // REL >= 2: this lane's key on the patch grid
+  const int go = IMG ? p.ids_go : 0;
+  const int xk2 = (int)__umulhi((unsigned)(k - go), p.pat.magicP), yk2 = k - go - xk2 * p.pat.P;
   const int lut_addr = lds_addr(lut);
   const int lim2 = p.pat.r + 1, nlim2 = -lim2;
 
@@ -955,13 +959,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_band_bf16_kernel(const Bw
     }
     const bool no_gq = p.pat.ng == 0 || q0 + 31 < p.pat.g0 || q0 >= p.pat.g0 + p.pat.ng;
     const TileClass tc = classify_tile(q0, k0, p.S, valid_len, W, m, ignore_band, no_gq);
-    const bool one_id = REL != 2 && (!HAS_REL || tc.far_neg || tc.far_pos);
+    const bool one_id = REL < 2 && (!HAS_REL || tc.far_neg || tc.far_pos);
     wave_lds_sync();
     Frag<T> qf;
     frag_from_tile(qf, qlds, lane);
     if (HAS_REL && !one_id) {           // mixed ids: T rows = this q tile, with -lse2[row] folded in
       const float nl = -rowc[r];
-      if (REL == 2) tab[r * kTStride(Rp) + kZeroCol(Rp)] = nl;
+      if (REL >= 2) tab[r * kTStride(Rp) + kZeroCol(Rp)] = nl;
 #pragma unroll
       for (int rb = 0; rb < Rp / 32; ++rb) {
         Frag<T> ef;                     // E rows of the table columns, from the workgroup's LDS image
@@ -994,12 +998,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_band_bf16_kernel(const Bw
     const float* relrow = rowc + (tc.far_neg ? 64 : 96);   // clipped rel - lse2, per row
 
     float pr[16];
-    if (REL == 2) {
+    if (REL >= 2) {
       // table value (rel - lse2 of the row) of each element, then the mask by tile class
       float sc[16];
       const int rowbase = tab_addr + h4 * (kTStride(Rp) * 4);
-      if (q0 + 31 < p.pat.I && k0 + 31 < p.pat.I && p.pat.P >= 32) {     // image x image: look-up table
-        const Ids2dTile t2 = ids2d_tile<-1>(p.pat, lut_addr, q0 + h4, xk2, yk2);
+      if (tile_in_image<IMG>(p.pat, go, q0) && tile_in_image<IMG>(p.pat, go, k0) && p.pat.P >= 32) {     // image x image: look-up table
+        const Ids2dTile t2 = ids2d_tile<-1>(p.pat, lut_addr, q0 - go + h4, xk2, yk2);
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           const int ci = (i & 3) + 8 * (i >> 2);
@@ -1009,7 +1013,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_band_bf16_kernel(const Bw
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           const int ci = (i & 3) + 8 * (i >> 2);
-          sc[i] = fmaf(c[i], p.sscale, *(lds_cfp)(size_t)(unsigned)(rowbase + ci * (kTStride(Rp) * 4) + 4 * col2d<Rp>(p.pat, p.R, q0 + h4 + ci, k)));
+          sc[i] = fmaf(c[i], p.sscale, *(lds_cfp)(size_t)(unsigned)(rowbase + ci * (kTStride(Rp) * 4) + 4 * col2d<Rp, IMG>(p.pat, go, p.R, q0 + h4 + ci, k)));
         }
       }
       if (tc.plain) {
@@ -1497,8 +1501,8 @@ static hipError_t launch_lean(const BwdParams& p_in, hipStream_t st) {
   const int per_bn = (p.n_chunks * p.n_gblk + 3) / 4;
   dim3 grid(p.n_band_blocks + per_bn * p.B * p.N);
   const int e_img = HAS_REL ? Rp * 128 : 0;     // the workgroup's E image
-  p.dstride = (REL != 2 && Rp == 32 && 2 * p.pat.m + 1 <= 27) ? 28 : kTStride(Rp);     // 27 r: conflict-free diagonal stores
-  const int n2 = 2 * p.pat.r + 3, lut_bytes = REL == 2 ? 4 * ((n2 * n2 + 15) & ~15) : 0;   // (dx, dy) look-up table, one per workgroup
+  p.dstride = (REL < 2 && Rp == 32 && 2 * p.pat.m + 1 <= 27) ? 28 : kTStride(Rp);     // 27 r: conflict-free diagonal stores
+  const int n2 = 2 * p.pat.r + 3, lut_bytes = REL >= 2 ? 4 * ((n2 * n2 + 15) & ~15) : 0;   // (dx, dy) look-up table, one per workgroup
   const int lds_a = 4 * (LeanLds<Rp>::kTab + 32 * p.dstride * 4 + 2 * LeanLds<Rp>::kTile) + e_img + lut_bytes, lds_b = 4 * LeanLds<Rp>::kDkv + e_img + lut_bytes;
   if (lds_a > 64 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dq_band_bf16_kernel<Rp, REL>),
@@ -1531,6 +1535,7 @@ static hipError_t launch_lean(const BwdParams& p_in, hipStream_t st) {
 }
 
 hipError_t launch_attn_bwd_band_bf16(const BwdParams& p, hipStream_t st) {
+  if (p.lean2d && p.ids_go != 0) return p.Rp == 32 ? launch_lean<32, 3>(p, st) : launch_lean<64, 3>(p, st);
   if (p.lean2d) return p.Rp == 32 ? launch_lean<32, 2>(p, st) : launch_lean<64, 2>(p, st);
   const bool has_rel = p.pat.id_mode == 1 && p.R > 0;
   if (p.Rp == 32) return has_rel ? launch_lean<32, 1>(p, st) : launch_lean<32, 0>(p, st);

@@ -21,6 +21,16 @@
 
 namespace mmt {
 
+// MMT_IMAGE_TU (this file compiled as attn_fwd_image.hip): the id-generating instantiations a third time, with the image
+// origin of MMT_IDS_2D_IMAGE (ids_go) read by rel_id, under a kernel name of their own.  Every other instantiation never
+// reads the origin and is the kernel it was.
+#ifdef MMT_IMAGE_TU
+#define attn_fwd_kernel attn_fwd_image_kernel
+constexpr bool kImageTU = true;
+#else
+constexpr bool kImageTU = false;
+#endif
+
 // GEN = true: ids/mask through the generic per-element generators (2-D ids, or 1-D ids whose
 // vocabulary is smaller than 2m+1); GEN = false: no ids or 1-D ids with the permuted table.
 // GRID = true (kBand only): the pattern has the image-grid term -- the tile walk is GridWalk's union and the
@@ -283,7 +293,7 @@ __global__ __launch_bounds__(256, (ORG && sizeof(T) == 2 && DH == 64) ? 2 : 1) v
           if constexpr (ORG) keep = pattern_mask_origin<GRID>(p.pat, p.grid, __shfl(kid, kap(i, h), 64) == qid, q, kk, lq, lk);
           else if constexpr (PACK) keep = pattern_mask_packed(p.pat, __shfl(kid, kap(i, h), 64) == qid, q, kk);
           else keep = pattern_mask<GRID>(p.pat, p.grid, valid_len, q, kk);
-          if (id_mode) id = ORG ? rel_id(p.pat, lq, lk) : rel_id(p.pat, q, kk);
+          if (id_mode) id = ORG ? rel_id<kImageTU>(p.pat, lq, lk, p.ids_go) : rel_id<kImageTU>(p.pat, q, kk, p.ids_go);
         }
         float rel = 0.f;
         if ((unsigned)id < (unsigned)p.R) rel = trow[id];
@@ -455,7 +465,24 @@ static hipError_t launch_rp(const FwdParams& p, dim3 grid, hipStream_t st) {
   return launch_one<T, MODE, 128, GEN, GRID, DH, PACK, ORG>(p, grid, st);
 }
 
-#ifdef MMT_ORIGIN_TU
+#if defined(MMT_IMAGE_TU)
+// The MMT_IDS_2D_IMAGE instantiations (this file compiled as attn_fwd_image.hip): GEN only (the ids are generated), with and
+// without the grid, example ids and example starts.
+template <typename T, int DH>
+static hipError_t launch_image_t(const FwdParams& p, int pack, dim3 grid, hipStream_t st) {
+  if (pack == kPackOrigin)
+    return p.grid.ga > 0 ? launch_rp<T, kBand, true, true, DH, true, true>(p, grid, st) : launch_rp<T, kBand, true, false, DH, true, true>(p, grid, st);
+  if (pack) return launch_rp<T, kBand, true, false, DH, true>(p, grid, st);
+  return p.grid.ga > 0 ? launch_rp<T, kBand, true, true, DH>(p, grid, st) : launch_rp<T, kBand, true, false, DH>(p, grid, st);
+}
+
+hipError_t launch_attn_fwd_image(const FwdParams& p, bool bf16, int pack, hipStream_t st) {
+  const int per_bn = (p.n_chunks * p.n_rowblk + 3) / 4;                 // (no rows items with example starts: n_rowblk = 0)
+  dim3 grid(p.n_band_blocks + per_bn * p.B * p.N);
+  if (p.D == 128) return bf16 ? launch_image_t<__bf16, 128>(p, pack, grid, st) : launch_image_t<float, 128>(p, pack, grid, st);
+  return bf16 ? launch_image_t<__bf16, 64>(p, pack, grid, st) : launch_image_t<float, 64>(p, pack, grid, st);
+}
+#elif defined(MMT_ORIGIN_TU)
 // The per-example-origin instantiations (this file compiled as attn_fwd_origin.hip).  1-D / no ids without a grid read no
 // start, but they too need kernels of their own: the ids of row b lie at [b][0][S] of [B,2,S] here.
 template <typename T, int DH>
@@ -485,6 +512,7 @@ static hipError_t launch_t(const FwdParams& p, int mode, int pack, dim3 grid, hi
 }
 
 hipError_t launch_attn_fwd(const FwdParams& p, int mode, bool bf16, int pack, hipStream_t st) {
+  if (mode == kBand && p.ids_go != 0 && p.pat.id_mode == 2) return launch_attn_fwd_image(p, bf16, pack, st);   // MMT_IDS_2D_IMAGE: attn_fwd_image.hip
   if (mode == kBand && pack == kPackOrigin) return launch_attn_fwd_origin(p, bf16, st);   // per-example origin: attn_fwd_origin.hip
   // band items first, then (kBand only) the global-row items of the same launch
   const int per_bn = (p.n_chunks * p.n_rowblk + 3) / 4;

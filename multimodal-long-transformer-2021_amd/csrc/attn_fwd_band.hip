@@ -16,10 +16,11 @@
 
 namespace mmt {
 
-template <int Rp, int REL>        // REL: 0 no relative term, 1 = 1-D ids (permuted table), 2 = 2-D ids (columns in id order)
+template <int Rp, int REL>        // REL: 0 no relative term, 1 = 1-D ids (permuted table), 2 = 2-D ids (columns in id order), 3 = 2-D ids with the image at ids_go
 __global__ __launch_bounds__(256, 3) void attn_fwd_band_bf16_kernel(const FwdParams p) {
   using T = __bf16;
   constexpr bool HAS_REL = REL != 0;
+  constexpr bool IMG = REL == 3;          // 2-D ids with the image at p.ids_go (MMT_IDS_2D_IMAGE)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -29,7 +30,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_band_bf16_kernel(const FwdPar
   float* tab = reinterpret_cast<float*>(wl);                     // accesses in order, so the two never meet, and three
   unsigned char* vlds = wl + WaveLds<T, Rp>::kTBytesAligned;     // workgroups fit a compute unit at the 64-wide table too
   unsigned char* klds = vlds;
-  int* lut = reinterpret_cast<int*>(smem + 4 * kWaveBytes) + wave * ((lut2d_entries(p.pat) + 15) & ~15);   // REL == 2: wave-private
+  int* lut = reinterpret_cast<int*>(smem + 4 * kWaveBytes) + wave * ((lut2d_entries(p.pat) + 15) & ~15);   // REL >= 2: wave-private
 
   // ---- work item ------------------------------------------------------------------------
   const int n_tiles = (p.S + 31) >> 5, nqb = (p.S + 127) >> 7;
@@ -117,13 +118,13 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_band_bf16_kernel(const FwdPar
 #pragma unroll
     for (int rb = 0; rb < Rp / 32; ++rb)
 #pragma unroll
-      for (int s = 0; s < 4; ++s) ef[rb].v[s] = buf16(re, (unsigned)(REL == 2 ? rb * 32 + r : icol(m, rb * 32 + r)) * es1b + 64 * h + 16 * s, 0u);   // row r <- id of column rb*32 + r
+      for (int s = 0; s < 4; ++s) ef[rb].v[s] = buf16(re, (unsigned)(REL >= 2 ? rb * 32 + r : icol(m, rb * 32 + r)) * es1b + 64 * h + 16 * s, 0u);   // row r <- id of column rb*32 + r
     float* bias_ts = reinterpret_cast<float*>(vlds);
     if (lane < Rp) {
-      const int idc = REL == 2 ? lane : icol(m, lane);
+      const int idc = REL >= 2 ? lane : icol(m, lane);
       bias_ts[lane] = (p.bias && idc < p.R) ? (float)reinterpret_cast<const T*>(p.bias)[(long)idc * p.N + n] * p.tscale : 0.f;   // by column
     }
-    if (REL == 2) {
+    if (REL >= 2) {
       build_lut2d<Rp>(lut, p.pat, p.R, lane, 64);
       tab[r * kTStride(Rp) + kZeroCol(Rp)] = 0.f;
     }
@@ -161,8 +162,9 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_band_bf16_kernel(const FwdPar
   const bool qblk_valid = q0 + 31 < valid_len, qblk_pad = q0 >= valid_len, qblk_in = q0 + 31 < p.S;
   const SeedPair sd = effective_seed(p.seed_lo, p.seed_hi, p.epoch);
   const uint32_t drop_base = drop_row_base(sd.lo, sd.hi, (uint32_t)bn, (uint32_t)q);
-  // REL == 2: this lane's query on the patch grid, and the LDS address of the look-up table
-  const int xq2 = (int)__umulhi((unsigned)q, p.pat.magicP), yq2 = q - xq2 * p.pat.P;
+  // REL >= 2: this lane's query on the patch grid, and the LDS address of the look-up table
+  const int go = IMG ? p.ids_go : 0;
+  const int xq2 = (int)__umulhi((unsigned)(q - go), p.pat.magicP), yq2 = q - go - xq2 * p.pat.P;
   const int lut_addr = lds_addr(lut);
   const int lim2 = p.pat.r + 1, nlim2 = -lim2;
 
@@ -207,24 +209,24 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_band_bf16_kernel(const FwdPar
     const bool band_all = ignore_band || (dmin >= -W && dmax <= W);
     const bool plain = in_range && seg_all && band_all;
     const bool far_neg = dmax <= -m, far_pos = dmin >= m;
-    const bool one_id = REL != 2 && (!HAS_REL || far_neg || far_pos);
+    const bool one_id = REL < 2 && (!HAS_REL || far_neg || far_pos);
     const bool no_gkey = p.pat.ng == 0 || k0 + 31 < p.pat.g0 || k0 >= p.pat.g0 + p.pat.ng;
     const float relc = HAS_REL ? (far_neg ? relfn : relfp) : 0.f;
     const int dbase = k0 - q + 4 * h;
 
     float pr[16], s2[16];
-    if (REL == 2) {
+    if (REL >= 2) {
       // ---- 2-D ids: the relative term first (image x image tiles through the look-up table, anything else with
       //      the general id function), then the mask by tile class
       float rel[16];
-      if (q0 + 31 < p.pat.I && k0 + 31 < p.pat.I && p.pat.P >= 32) {
-        const Ids2dTile t2 = ids2d_tile<1>(p.pat, lut_addr, k0 + 4 * h, xq2, yq2);
+      if (tile_in_image<IMG>(p.pat, go, q0) && tile_in_image<IMG>(p.pat, go, k0) && p.pat.P >= 32) {
+        const Ids2dTile t2 = ids2d_tile<1>(p.pat, lut_addr, k0 - go + 4 * h, xq2, yq2);
 #pragma unroll
         for (int i = 0; i < 16; ++i)
           rel[i] = *(lds_cfp)(size_t)(unsigned)(trow_addr + ids2d_col4<1>(t2, (i & 3) + 8 * (i >> 2), nlim2, lim2));
       } else {
 #pragma unroll
-        for (int i = 0; i < 16; ++i) rel[i] = trow[col2d<Rp>(p.pat, p.R, q, k0 + 4 * h + (i & 3) + 8 * (i >> 2))];
+        for (int i = 0; i < 16; ++i) rel[i] = trow[col2d<Rp, IMG>(p.pat, go, p.R, q, k0 + 4 * h + (i & 3) + 8 * (i >> 2))];
       }
       if (plain) {
 #pragma unroll
@@ -406,13 +408,18 @@ hipError_t launch_attn_fwd_band_bf16(const FwdParams& p, hipStream_t st) {
   const int rel = p.R > 0 ? p.pat.id_mode : 0;
   if (rel == 2) {                    // 2-D ids: table width chosen by the host (lean_rp), one look-up table per wave
     const int n2 = 2 * p.pat.r + 3, lut_bytes = 4 * 4 * ((n2 * n2 + 15) & ~15);
+    const bool img = p.ids_go != 0;    // MMT_IDS_2D_IMAGE off the sequence start: the instantiations that read the origin
     if (p.lean_rp == 32) {
-      hipLaunchKernelGGL((attn_fwd_band_bf16_kernel<32, 2>), grid, dim3(256), 4 * (WaveLds<__bf16, 32>::kBytes) + lut_bytes, st, p);
+      const int lds = 4 * (WaveLds<__bf16, 32>::kBytes) + lut_bytes;
+      if (img) hipLaunchKernelGGL((attn_fwd_band_bf16_kernel<32, 3>), grid, dim3(256), lds, st, p);
+      else hipLaunchKernelGGL((attn_fwd_band_bf16_kernel<32, 2>), grid, dim3(256), lds, st, p);
     } else {
       const int lds = 4 * (WaveLds<__bf16, 64>::kBytes) + lut_bytes;
       if (lds > 64 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_band_bf16_kernel<64, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      hipLaunchKernelGGL((attn_fwd_band_bf16_kernel<64, 2>), grid, dim3(256), lds, st, p);
+        (void)hipFuncSetAttribute(img ? reinterpret_cast<const void*>(attn_fwd_band_bf16_kernel<64, 3>)
+                                      : reinterpret_cast<const void*>(attn_fwd_band_bf16_kernel<64, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+      if (img) hipLaunchKernelGGL((attn_fwd_band_bf16_kernel<64, 3>), grid, dim3(256), lds, st, p);
+      else hipLaunchKernelGGL((attn_fwd_band_bf16_kernel<64, 2>), grid, dim3(256), lds, st, p);
     }
     return hipGetLastError();
   }

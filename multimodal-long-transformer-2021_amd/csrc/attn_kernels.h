@@ -47,6 +47,8 @@ struct FwdParams {
   long long* dbg;     // -DMMT_STAMP diagnostic builds only: in-kernel s_memtime stamps (never set in the product)
   int dbg_mode, dbg_sleep;   // -DMMT_STAMP builds only: ablations (1 = no tile loop, 2 = no DMA), start delay of the second resident round
   GridDev grid;       // image-grid term (general kernels only; last, so that no other field moves)
+  int ids_go;         // MMT_IDS_2D_IMAGE: first image position of the 2-D ids, image = [ids_go, ids_go + pat.I); 0 otherwise.  Behind
+                      // everything else: no field of a kernel that does not read it moves (independent of grid.ga)
   int D;              // head size (64 | 128): the launchers' choice of instantiation; 128 runs the general kernels only
 };
 
@@ -56,6 +58,7 @@ struct FwdParams {
 enum { kPackNone = 0, kPackIds = 1, kPackOrigin = 2 };
 hipError_t launch_attn_fwd(const FwdParams& p, int mode, bool bf16, int pack, hipStream_t st);
 hipError_t launch_attn_fwd_origin(const FwdParams& p, bool bf16, hipStream_t st);              // attn_fwd_origin.hip
+hipError_t launch_attn_fwd_image(const FwdParams& p, bool bf16, int pack, hipStream_t st);     // attn_fwd_image.hip (MMT_IDS_2D_IMAGE)
 hipError_t launch_rows_combine(const FwdParams& p, bool bf16, hipStream_t st);
 hipError_t launch_attn_fwd_band_bf16(const FwdParams& p, hipStream_t st);   // attn_fwd_band.hip
 hipError_t launch_attn_fwd_win_bf16(const FwdParams& p, hipStream_t st);    // attn_fwd_win.hip
@@ -116,10 +119,13 @@ struct BwdParams {
   long long* dbg;    // -DMMT_STAMP diagnostic builds only (see FwdParams)
   int dbg_mode;
   GridDev grid;      // image-grid term (general kernels only; last, so that no other field moves)
+  int ids_go;         // MMT_IDS_2D_IMAGE: first image position of the 2-D ids, image = [ids_go, ids_go + pat.I); 0 otherwise.  Behind
+                      // everything else: no field of a kernel that does not read it moves (independent of grid.ga)
 };
 
 hipError_t launch_attn_bwd(const BwdParams& p, int mode, bool bf16, int pack, hipStream_t st);
 hipError_t launch_attn_bwd_origin(const BwdParams& p, bool bf16, hipStream_t st);              // attn_bwd_origin.hip
+hipError_t launch_attn_bwd_image(const BwdParams& p, bool bf16, int pack, hipStream_t st);     // attn_bwd_image.hip (MMT_IDS_2D_IMAGE)
 hipError_t launch_attn_bwd_band_bf16(const BwdParams& p, hipStream_t st);   // attn_bwd_band.hip
 hipError_t launch_bwd_dq_combine(const BwdParams& p, bool bf16, hipStream_t st);
 hipError_t launch_bwd_dkv_combine(const BwdParams& p, bool bf16, hipStream_t st);
@@ -133,6 +139,8 @@ struct SideParams {
   int materialize_pattern;
   int32_t *att_mask, *rel_ids, *segment_ids;
   GridDev grid;
+  int ids_go;         // MMT_IDS_2D_IMAGE: first image position of the 2-D ids, image = [ids_go, ids_go + pat.I); 0 otherwise.  Behind
+                      // everything else: no field of a kernel that does not read it moves (independent of grid.ga)
 };
 hipError_t launch_side_inputs(const SideParams& p, hipStream_t st);
 // mmt_write_step_scalars: one thread writes the step's epoch and {lr, bias corrections} (side_inputs.hip)

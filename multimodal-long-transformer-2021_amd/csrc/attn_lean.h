@@ -39,14 +39,26 @@ __device__ __forceinline__ void build_lut2d(int* lut, const PatternDev& pat, int
     lut[e] = 4 * ((id < Rp && id < R) ? id : kZeroCol(Rp));
   }
 }
-template <int Rp>
-__device__ __forceinline__ int col2d(const PatternDev& pat, int R, int q, int k) {    // general (any pair) column
-  const int id = rel_id(pat, q, k);
+template <int Rp, bool IMG>
+__device__ __forceinline__ int col2d(const PatternDev& pat, int go, int R, int q, int k) {    // general (any pair) column
+  const int id = rel_id<IMG>(pat, q, k, go);
   return ((unsigned)id < (unsigned)Rp && id < R) ? id : kZeroCol(Rp);
+}
+// The image starts at ids_go (MMT_IDS_2D_IMAGE; 0 otherwise), not on a tile boundary then: everything the look-up path
+// takes for a grid position -- the "all image" test of a tile, the lane's own (xfix, yfix), the first walked position
+// vb -- counts from ids_go.  Tiles that hold an end of the image fail the test and take col2d().  The kernels that serve
+// it are instantiations of their own (REL == 3, IMG here): the MMT_IDS_2D ones (REL == 2) never read ids_go and are what
+// they were.
+template <bool IMG>
+__device__ __forceinline__ bool tile_in_image(const PatternDev& pat, int go, int x0) {      // 32 positions from x0, all image
+  if (!IMG) return x0 + 31 < pat.I;
+  const int l0 = x0 - go;
+  return l0 >= 0 && l0 + 31 < pat.I;
 }
 struct Ids2dTile { int g0, g1, dy0, dy1, wth; };
 // SGN = +1: the registers walk keys vb + ci and the lane owns the query (xfix, yfix);  SGN = -1: the registers walk
-// query rows and the lane owns the key.  vb = first walked position of this half-wave.
+// query rows and the lane owns the key.  vb = first walked position of this half-wave, counted from ids_go like the
+// lane's own position behind (xfix, yfix).
 template <int SGN>
 __device__ __forceinline__ Ids2dTile ids2d_tile(const PatternDev& pat, int lut_addr, int vb, int xfix, int yfix) {
   const int xvb = (int)__umulhi((unsigned)vb, pat.magicP), yvb = vb - xvb * pat.P;

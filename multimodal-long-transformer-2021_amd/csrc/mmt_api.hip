@@ -60,11 +60,18 @@ int handover_slots(const mmt_attn_desc* d, bool dense) {
 int grid_radius(const mmt_mask_desc& m) { return m.image_grid & 0xFF; }
 int grid_start(const mmt_mask_desc& m) { return (m.image_grid >> 8) & 0x7FFFFF; }
 
-// argument errors of the image-grid term (shared by check_desc and mmt_side_inputs); 0 = fine or no grid
+bool ids_2d(const mmt_mask_desc& m) { return m.id_mode == MMT_IDS_2D || m.id_mode == MMT_IDS_2D_IMAGE; }
+
+// argument errors of the image-grid term (shared by check_desc and mmt_side_inputs); 0 = fine or no grid.
+// MMT_IDS_2D_IMAGE reads the first-image-position field of the word with or without a grid radius: the image of the
+// ids must lie inside the sequence too (P > 0 is the id mode's own check, made before this one).
 int check_grid(const mmt_mask_desc& m, int S) {
   if (m.image_grid == 0) return MMT_OK;
   if (m.image_grid < 0) return fail(MMT_E_INVALID, "image_grid: bit 31 must be zero");
   const int a = grid_radius(m);
+  if (m.id_mode == MMT_IDS_2D_IMAGE &&
+      (int64_t)grid_start(m) + (int64_t)m.patches_per_row * m.patches_per_row > S)
+    return fail(MMT_E_INVALID, "image of the 2-D ids outside the sequence (g + P*P > S)");
   if (a == 0) return MMT_OK;
   if (a > 8) return fail(MMT_E_UNSUPPORTED, "grid radius %d: built up to 8", a);
   if (m.patches_per_row <= 0) return fail(MMT_E_INVALID, "an image grid needs patches_per_row > 0");
@@ -95,9 +102,9 @@ int check_desc(const mmt_attn_desc* d) {
   const mmt_mask_desc& m = d->mask;
   if (m.local_radius < 0) return fail(MMT_E_INVALID, "local_radius must be >= 0");
   if (m.n_global < 0 || (!m.global_index && (m.global_start < 0 || m.global_start + m.n_global > d->S))) return fail(MMT_E_INVALID, "global range outside the sequence");
-  if (m.id_mode < MMT_IDS_NONE || m.id_mode > MMT_IDS_2D) return fail(MMT_E_INVALID, "bad id_mode");
+  if (m.id_mode < MMT_IDS_NONE || m.id_mode > MMT_IDS_2D_IMAGE) return fail(MMT_E_INVALID, "bad id_mode");
   if (m.id_mode != MMT_IDS_NONE && m.max_dist < 0) return fail(MMT_E_INVALID, "max_dist must be >= 0");
-  if (m.id_mode == MMT_IDS_2D) {
+  if (ids_2d(m)) {
     if (m.patches_per_row <= 0 || m.core_layers <= 0) return fail(MMT_E_INVALID, "2-D ids need patches_per_row > 0 and core_layers > 0");
     if ((int64_t)m.patches_per_row * m.patches_per_row > d->S) return fail(MMT_E_INVALID, "image part longer than the sequence");
   }
@@ -131,16 +138,20 @@ mmt::PatternDev make_pattern(const mmt_mask_desc& m, int S) {
   p.radius = m.local_radius > S ? S : m.local_radius;
   p.g0 = m.global_start;
   p.ng = m.n_global;
-  p.id_mode = m.id_mode;
+  p.id_mode = ids_2d(m) ? MMT_IDS_2D : m.id_mode;                  // the kernels know one 2-D generator, with an origin
   p.m = m.max_dist;
   p.P = m.patches_per_row > 0 ? m.patches_per_row : 1;
   p.magicP = (unsigned)((1ull << 32) / (unsigned)p.P) + 1u;      // exact for x * P < 2^32: x < S (checked: S * stride < 2^31, P <= S)
   p.r = m.core_layers;
-  p.I = m.id_mode == MMT_IDS_2D ? m.patches_per_row * m.patches_per_row : 0;
+  p.I = ids_2d(m) ? m.patches_per_row * m.patches_per_row : 0;
   p.image_part = m.patches_per_row * m.patches_per_row + 8 + 2 * m.max_dist + 1;
   p.text_part = p.image_part + 1;
   return p;
 }
+
+// image origin of the 2-D ids: the word's first-image-position field for MMT_IDS_2D_IMAGE (validated: go + P*P <= S, with or
+// without a grid radius), 0 for every other mode
+int ids_origin(const mmt_mask_desc& m) { return m.id_mode == MMT_IDS_2D_IMAGE ? grid_start(m) : 0; }
 
 mmt::GridDev make_grid(const mmt_mask_desc& m) {
   mmt::GridDev g;
@@ -212,6 +223,7 @@ void fill_common(mmt::FwdParams& p, const mmt_attn_desc* d) {
   p.mask_add = d->mask_value * mmt::kLog2e;
   p.pat = make_pattern(d->mask, d->S);
   p.grid = make_grid(d->mask);
+  p.ids_go = ids_origin(d->mask);
   p.valid_len = d->mask.valid_len;
   if (d->dropout_p > 0.f) {
     unsigned t = (unsigned)((double)d->dropout_p * 65536.0 + 0.5);
@@ -418,6 +430,7 @@ int mmt_attn_bwd(const mmt_attn_desc* desc, const void* q, const void* k, const 
   p.drel_accum = (desc->flags & MMT_FLAG_ACCUM_REL_GRADS) ? 1 : 0;
   p.pat = f.pat;
   p.grid = f.grid;
+  p.ids_go = f.ids_go;
   if (desc->R == 0) { p.pat.id_mode = 0; p.rel_ids = nullptr; }
   p.perm_1d = (!dense && p.pat.id_mode == MMT_IDS_1D && desc->R >= 2 * p.pat.m + 1) ? 1 : 0;
   p.drop_thresh = f.drop_thresh; p.seed_lo = f.seed_lo; p.seed_hi = f.seed_hi; p.inv_keep = f.inv_keep; p.epoch = f.epoch;
@@ -474,8 +487,8 @@ int mmt_side_inputs(const mmt_mask_desc* mask, int32_t B, int32_t S,
                     int32_t* segment_ids_out, void* stream) {
   if (!mask) return fail(MMT_E_INVALID, "mask desc is NULL");
   if (B <= 0 || S <= 0) return fail(MMT_E_INVALID, "B and S must be positive");
-  if (mask->id_mode < MMT_IDS_NONE || mask->id_mode > MMT_IDS_2D) return fail(MMT_E_INVALID, "bad id_mode");
-  if (mask->id_mode == MMT_IDS_2D) {
+  if (mask->id_mode < MMT_IDS_NONE || mask->id_mode > MMT_IDS_2D_IMAGE) return fail(MMT_E_INVALID, "bad id_mode");
+  if (ids_2d(*mask)) {
     // same argument errors as MmtRelativePositionGenerator.__init__ (feature_utils.py:60-65)
     if (mask->patches_per_row <= 0) return fail(MMT_E_INVALID, "`num_patch_per_row` must be positive.");
     if (mask->core_layers <= 0) return fail(MMT_E_INVALID, "`num_core_layers` must be positive.");
@@ -490,6 +503,7 @@ int mmt_side_inputs(const mmt_mask_desc* mask, int32_t B, int32_t S,
   mmt::SideParams p;
   p.pat = make_pattern(*mask, S);
   p.grid = make_grid(*mask);
+  p.ids_go = ids_origin(*mask);
   p.B = B; p.S = S;
   p.img_wp = num_image_wordpieces; p.txt_wp = num_text_wordpieces;
   p.materialize_pattern = materialize_pattern;

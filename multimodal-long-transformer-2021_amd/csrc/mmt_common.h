@@ -32,7 +32,7 @@ __device__ __forceinline__ int kap(int i, int h) { return (i & 3) + 8 * (i >> 2)
 struct PatternDev {
   int radius;      // local radius W (>= S: no band)
   int g0, ng;      // global tokens [g0, g0+ng)
-  int id_mode;     // 0 none, 1 = 1-D, 2 = 2-D
+  int id_mode;     // 0 none, 1 = 1-D, 2 = 2-D (MMT_IDS_2D_IMAGE too: it is 2-D with the parameter blocks' ids_go != 0)
   int m;           // relative_pos_max_distance
   int P, r;        // patches per row, core layers (2-D)
   int I;           // P*P image positions (2-D), 0 otherwise
@@ -73,10 +73,16 @@ __device__ __forceinline__ int id_2d(int dx, int dy, int r) {
   return d * d + (int)((lut >> (4 * (vert * 3 + horz))) & 0xF);
 }
 
-__device__ __forceinline__ int rel_id(const PatternDev& p, int q, int k) {
+// IMG = false: instantiations that are launched with go == 0 only (every kernel that served MMT_IDS_2D before the origin
+// came: their text is what it was) and do not read it.  IMG = true: the kernels of MMT_IDS_2D_IMAGE -- the lean REL = 3
+// ones, attn_fwd_image.hip / attn_bwd_image.hip -- and mmt_side_inputs.
+template <bool IMG>
+__device__ __forceinline__ int rel_id(const PatternDev& p, int q, int k, int go) {
   if (p.id_mode == 1) return id_1d(q, k, p.m);
-  // id_mode == 2  (feature_utils.py:172-184)
-  const bool qi = q < p.I, ki = k < p.I;
+  // id_mode == 2  (feature_utils.py:172-184), on positions counted from the image's first one: the image tests are
+  // unsigned (the prefix [0, go) is text-like), the 1-D id depends on k - q only.  go = 0: the reference's ids.
+  if (IMG) { q -= go; k -= go; }
+  const bool qi = IMG ? (unsigned)q < (unsigned)p.I : q < p.I, ki = IMG ? (unsigned)k < (unsigned)p.I : k < p.I;
   if (qi && ki) {
     const int xq = (int)__umulhi((unsigned)q, p.magicP), yq = q - xq * p.P;
     const int xk = (int)__umulhi((unsigned)k, p.magicP), yk = k - xk * p.P;

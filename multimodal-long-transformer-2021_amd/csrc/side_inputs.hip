@@ -39,7 +39,7 @@ __global__ __launch_bounds__(256) void side_inputs_kernel(const SideParams p) {
         else keep = pattern_mask<true>(p.pat, p.grid, valid, q, k);
       }
       mv[j] = keep ? 1 : 0;
-      iv[j] = p.pat.id_mode ? rel_id(p.pat, q, k) : 0;
+      iv[j] = p.pat.id_mode ? rel_id<true>(p.pat, q, k, p.ids_go) : 0;
     }
     const long off = rowid * S + k0;
     if ((S & 3) == 0) {

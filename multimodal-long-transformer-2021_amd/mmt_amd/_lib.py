@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(_HERE, 'libmmt_attn.so')
 MMT_ABI_VERSION = 4
 MMT_F32, MMT_BF16 = 0, 1
 MMT_IDS_NONE, MMT_IDS_1D, MMT_IDS_2D = 0, 1, 2
+MMT_IDS_2D_IMAGE = 3          # MMT_IDS_2D with the image at [g, g + P*P), g = the first-image-position field of image_grid
 MMT_FLAG_SCALE_BEFORE_ADD = 1
 MMT_FLAG_ACCUM_REL_GRADS = 2
 MMT_FLAG_EXAMPLE_IDS = 4      # mask.valid_len names int32 [B,S] example ids (packed rows) instead of [B] lengths

@@ -59,6 +59,7 @@ class MmtEncoderConfig(Config):     # encoders.py:32-101
   relative_pos_max_distance: int = 12
   relative_vocab_size: int = 32
   relative_att_num_core_layers: int = 0
+  relative_att_align_image: bool = False   # 2-D ids with the image at the patches' positions, behind [CLS][PATCH] (MMT_IDS_2D_IMAGE); not the reference's ids
   max_absolute_position_embeddings: Optional[int] = None
   intermediate_size: int = 3072
   hidden_activation: str = 'gelu'
@@ -128,6 +129,7 @@ class MmtDataConfig(Config):        # data/configs.py:20-55 (+ TFM DataConfig ba
   max_seq_len: int = 512
   relative_pos_max_distance: int = 12
   relative_att_num_core_layers: int = 0
+  relative_att_align_image: bool = False   # 2-D ids with the image at the patches' positions, behind [CLS][PATCH] (MMT_IDS_2D_IMAGE); not the reference's ids
   label_field: Optional[str] = None
   label_weights_field: Optional[str] = None
   logits_field: Optional[str] = None

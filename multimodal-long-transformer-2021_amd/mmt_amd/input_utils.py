@@ -46,10 +46,12 @@ def attention_pattern_from_config(data_cfg, encoder_cfg=None) -> AttentionPatter
   n_img = 2 + P * P
   g = int(getattr(data_cfg, 'num_global_tokens', 0))
   a = int(getattr(data_cfg, 'image_grid_radius', 0))
+  # relative_att_align_image: the 2-D ids read the image at grid_start like the grid term (no effect without 2-D ids)
+  ids_2d = _lib.MMT_IDS_2D_IMAGE if getattr(data_cfg, 'relative_att_align_image', False) else _lib.MMT_IDS_2D
   return AttentionPattern(
       local_radius=int(getattr(data_cfg, 'local_radius', 1 << 30)),
       global_start=n_img if g else 0, n_global=g,     # the [ATT] marker and the tokens after it
-      id_mode=_lib.MMT_IDS_NONE if m <= 0 else (_lib.MMT_IDS_2D if r > 0 else _lib.MMT_IDS_1D),
+      id_mode=_lib.MMT_IDS_NONE if m <= 0 else (ids_2d if r > 0 else _lib.MMT_IDS_1D),
       max_dist=m, patches_per_row=P if (r > 0 or a > 0) else 0, core_layers=r,
       grid_radius=a, grid_start=2)                    # the patches sit behind [CLS][PATCH]
 

@@ -39,7 +39,9 @@ class AttentionPattern:
   local_radius >= seq_len with n_global == 0 is the reference's segmented mask
   (src/data/data_utils.py:321-322); id_mode 1 is the etcmodel 1-D generator
   (data_utils.py:300-301), id_mode 2 `MmtRelativePositionGenerator`
-  (src/feature_utils.py:29).
+  (src/feature_utils.py:29), which takes positions [0, P^2) for the image.  id_mode 3 (`MMT_IDS_2D_IMAGE`, not the
+  reference's ids) is id_mode 2 with the image where the patches are, at [grid_start, grid_start + P^2): the
+  positions before it are text-like; with example starts `grid_start` is local to every example.
 
   Global tokens: the contiguous range [global_start, global_start + n_global), or `global_index`, any set of
   positions (a tuple of ints).  A listed set that is in fact a contiguous run takes the structured kernels like
@@ -49,6 +51,7 @@ class AttentionPattern:
   Image grid (`grid_radius` a > 0; SURVEY.md App. A.5 `grid_radius`): patches at most a image rows and a columns
   apart also attend each other -- the image at positions [grid_start, grid_start + P^2) in raster order,
   P = `patches_per_row` (which must then be set, whatever `id_mode`; with 1-D ids it changes no id).  0 = off.
+  `grid_start` is one field of the descriptor: the grid term and the ids of id_mode 3 cannot disagree about the image.
   """
   local_radius: int = 1 << 30
   global_start: int = 0
@@ -82,7 +85,9 @@ class AttentionPattern:
     m.global_start, m.n_global = int(self.global_start), int(self.n_global)
     m.id_mode, m.max_dist = int(self.id_mode), int(self.max_dist)
     m.patches_per_row, m.core_layers = int(self.patches_per_row), int(self.core_layers)
-    m.image_grid = _lib.image_grid(self.grid_radius, self.grid_start) if self.grid_radius > 0 else 0
+    # the word's first-image-position field is read with a grid radius, and by MMT_IDS_2D_IMAGE without one too
+    reads_start = self.grid_radius > 0 or int(self.id_mode) == _lib.MMT_IDS_2D_IMAGE
+    m.image_grid = _lib.image_grid(max(int(self.grid_radius), 0), self.grid_start) if reads_start else 0
     m.global_index = None
     if self.global_index is not None:
       if device is None:

@@ -12,6 +12,7 @@ extern const unsigned char* g_ws_hi;
 extern int g_launches, g_last_kind, g_last_handover;
 extern const void* g_last_epoch;
 extern int g_last_pack;
+extern int g_last_family, g_last_tu;   /* backward: 0 general, 1 lean kernels; general launchers: 0 plain, 1 origin, 2 image unit */
 
 #define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "asan driver: %s:%d: %s (last error: %s)\n", __FILE__, __LINE__, #cond, mmt_last_error()); return 1; } } while (0)
 
@@ -80,6 +81,8 @@ int main(void) {
     CHECK(mmt_attn_bwd(&d, dummy, dummy, dummy, s[3] ? dummy : NULL, NULL, NULL, NULL, dummy, dummy, (const float*)dummy, dummy, dummy, dummy,
                        s[3] ? (float*)dummy : NULL, NULL, ws, need, NULL) == MMT_OK);
     CHECK(g_launches > before);
+    CHECK(g_last_kind == 5 && g_last_family == (s[5] == MMT_BF16));   /* f32: the general kernels (plain unit); these bf16 shapes: the lean ones */
+    CHECK(s[5] == MMT_BF16 || g_last_tu == 0);
     free(ws);
   }
 
@@ -98,9 +101,11 @@ int main(void) {
       g_ws_lo = ws; g_ws_hi = ws + need;
       CHECK(mmt_attn_fwd(&d, dummy, dummy, dummy, dummy, NULL, NULL, NULL, dummy, (float*)dummy, ws, need, NULL) == MMT_OK);
       CHECK(g_last_kind == 1);      /* the general kernel: no lean, window, walk or sliding-window kernel */
+      CHECK(g_last_tu == 0);
       CHECK(mmt_attn_bwd(&d, dummy, dummy, dummy, dummy, NULL, NULL, NULL, dummy, dummy, (const float*)dummy, dummy, dummy, dummy,
                          (float*)dummy, NULL, ws, need, NULL) == MMT_OK);
       CHECK(g_last_kind == 5 && g_last_handover == 0);
+      CHECK(g_last_family == 0 && g_last_tu == 0);
       free(ws);
     }
   }
@@ -136,6 +141,7 @@ int main(void) {
         CHECK(mmt_attn_bwd(&d, dummy, dummy, dummy, s[3] ? dummy : NULL, NULL, NULL, NULL, dummy, dummy, (const float*)dummy, dummy, dummy, dummy,
                            s[3] ? (float*)dummy : NULL, NULL, ws, need, NULL) == MMT_OK);
         CHECK(g_last_kind == 5 && g_last_handover == 0);
+        CHECK(g_last_family == 0 && g_last_tu == 0);
         /* the dense operator (att_mask given) */
         CHECK(mmt_attn_fwd(&d, dummy, dummy, dummy, s[3] ? dummy : NULL, NULL, (const int32_t*)dummy, NULL, dummy, (float*)dummy, ws, need, NULL) == MMT_OK);
         CHECK(g_last_kind == 1);
@@ -186,6 +192,7 @@ int main(void) {
         CHECK(mmt_attn_bwd(&d, dummy, dummy, dummy, s[3] ? dummy : NULL, NULL, NULL, NULL, dummy, dummy, (const float*)dummy, dummy, dummy, dummy,
                            s[3] ? (float*)dummy : NULL, NULL, ws, need, NULL) == MMT_OK);
         CHECK(g_last_kind == 5 && g_last_handover == 0 && g_last_pack == 1);
+        CHECK(g_last_family == 0 && g_last_tu == 0);
         CHECK(mmt_attn_bwd(&d, dummy, dummy, dummy, s[3] ? dummy : NULL, NULL, NULL, NULL, dummy, dummy, (const float*)dummy, dummy, dummy, dummy,
                            s[3] ? (float*)dummy : NULL, NULL, ws, need - 1, NULL) == MMT_E_WORKSPACE);
         /* with a dense att_mask the flag is ignored like the rest of desc->mask */
@@ -219,6 +226,36 @@ int main(void) {
     CHECK(mmt_attn_fwd(&d, dummy, dummy, dummy, dummy, NULL, NULL, NULL, dummy, NULL, dummy, 64, NULL) == MMT_E_UNSUPPORTED);
     CHECK(strstr(mmt_last_error(), "listed global-token set") != NULL);
     CHECK(g_launches == before);
+  }
+
+  /* ---- the general kernels' translation units: example starts -> origin unit; MMT_IDS_2D_IMAGE away from origin 0 -> image
+   *      unit (whatever the packing), unless the lean kernels hold the ids (bf16, head size 64, no grid, no packing) ---- */
+  {
+    static const int cases[][6] = {   /* dtype, D, pack flags, 2-D image ids at origin 2, expected family, expected unit */
+        {MMT_BF16, 64, MMT_FLAG_EXAMPLE_IDS | MMT_FLAG_EXAMPLE_STARTS, 0, 0, 1}, {MMT_F32, 128, MMT_FLAG_EXAMPLE_IDS | MMT_FLAG_EXAMPLE_STARTS, 0, 0, 1},
+        {MMT_BF16, 64, MMT_FLAG_EXAMPLE_IDS | MMT_FLAG_EXAMPLE_STARTS, 1, 0, 2}, {MMT_BF16, 64, MMT_FLAG_EXAMPLE_IDS, 1, 0, 2},
+        {MMT_F32, 64, 0, 1, 0, 2}, {MMT_BF16, 128, 0, 1, 0, 2}, {MMT_BF16, 64, 0, 1, 1, 0}};
+    for (unsigned i = 0; i < sizeof(cases) / sizeof(cases[0]); ++i) {
+      const int* s = cases[i];
+      d = base_desc(2, 512, 2, 49, s[0]);
+      d.D = s[1];
+      const int64_t st[3] = {(int64_t)512 * 2 * s[1], (int64_t)2 * s[1], s[1]};
+      for (int j = 0; j < 3; ++j) d.q_stride[j] = d.k_stride[j] = d.v_stride[j] = d.o_stride[j] = st[j];
+      d.flags = (uint32_t)s[2];
+      if (s[2]) d.mask.valid_len = (const int32_t*)dummy;
+      if (s[3]) { d.mask.id_mode = MMT_IDS_2D_IMAGE; d.mask.patches_per_row = 4; d.mask.core_layers = 1; d.mask.max_dist = 3; d.mask.image_grid = MMT_IMAGE_GRID(0, 2); }
+      const size_t need = mmt_workspace_bytes(&d);
+      CHECK(need > 0);
+      unsigned char* ws = (unsigned char*)malloc(need);
+      CHECK(ws != NULL);
+      g_ws_lo = ws; g_ws_hi = ws + need;
+      CHECK(mmt_attn_fwd(&d, dummy, dummy, dummy, dummy, NULL, NULL, NULL, dummy, (float*)dummy, ws, need, NULL) == MMT_OK);
+      CHECK(s[4] ? g_last_kind == 2 : (g_last_kind == 1 && g_last_tu == s[5]));
+      CHECK(mmt_attn_bwd(&d, dummy, dummy, dummy, dummy, NULL, NULL, NULL, dummy, dummy, (const float*)dummy, dummy, dummy, dummy,
+                         (float*)dummy, NULL, ws, need, NULL) == MMT_OK);
+      CHECK(g_last_kind == 5 && g_last_family == s[4] && (s[4] || g_last_tu == s[5]));
+      free(ws);
+    }
   }
 
   /* ---- side inputs: the reference generator's argument errors (feature_utils.py:60-65) ---- */

@@ -880,47 +880,32 @@ static hipError_t launch_bwd_rp(const BwdParams& p, hipStream_t st) {
   return launch_bwd_one<T, MODE, 128, GEN, GRID, DH, PACK, ORG>(p, st);
 }
 
-#if defined(MMT_IMAGE_TU)
-// The MMT_IDS_2D_IMAGE instantiations (this file compiled as attn_bwd_image.hip), as launch_attn_fwd_image's.
-template <typename T, int DH>
-static hipError_t launch_bwd_image_t(const BwdParams& p, int pack, hipStream_t st) {
-  if (pack == kPackOrigin)
-    return p.grid.ga > 0 ? launch_bwd_rp<T, kBand, true, true, DH, true, true>(p, st) : launch_bwd_rp<T, kBand, true, false, DH, true, true>(p, st);
-  if (pack) return launch_bwd_rp<T, kBand, true, false, DH, true>(p, st);
-  return p.grid.ga > 0 ? launch_bwd_rp<T, kBand, true, true, DH>(p, st) : launch_bwd_rp<T, kBand, true, false, DH>(p, st);
+// GEN and GRID of one (PACK, ORG) pair, as far as this translation unit holds them: as attn_fwd.hip's launch_band
+template <typename T, int DH, bool PACK, bool ORG, bool GRIDS>
+static hipError_t launch_bwd_band(const BwdParams& p, hipStream_t st) {
+  const bool table = kTu.table_ids && (p.pat.id_mode == 0 || p.perm_1d), grd = GRIDS && p.grid.ga > 0;
+  if constexpr (kTu.table_ids && GRIDS) if (table && grd) return launch_bwd_rp<T, kBand, false, true, DH, PACK, ORG>(p, st);
+  if constexpr (kTu.table_ids) if (table) return launch_bwd_rp<T, kBand, false, false, DH, PACK, ORG>(p, st);
+  if constexpr (GRIDS) if (grd) return launch_bwd_rp<T, kBand, true, true, DH, PACK, ORG>(p, st);      // image grid: its own instantiations
+  return launch_bwd_rp<T, kBand, true, false, DH, PACK, ORG>(p, st);
 }
-
-hipError_t launch_attn_bwd_image(const BwdParams& p, bool bf16, int pack, hipStream_t st) {
-  if (p.D == 128) return bf16 ? launch_bwd_image_t<__bf16, 128>(p, pack, st) : launch_bwd_image_t<float, 128>(p, pack, st);
-  return bf16 ? launch_bwd_image_t<__bf16, 64>(p, pack, st) : launch_bwd_image_t<float, 64>(p, pack, st);
-}
-#elif defined(MMT_ORIGIN_TU)
-// The per-example-origin instantiations (this file compiled as attn_bwd_origin.hip), as launch_attn_fwd_origin's.
-template <typename T, int DH>
-static hipError_t launch_bwd_origin_t(const BwdParams& p, hipStream_t st) {
-  const bool gen = !(p.pat.id_mode == 0 || p.perm_1d);
-  if (p.grid.ga > 0)
-    return gen ? launch_bwd_rp<T, kBand, true, true, DH, true, true>(p, st) : launch_bwd_rp<T, kBand, false, true, DH, true, true>(p, st);
-  return gen ? launch_bwd_rp<T, kBand, true, false, DH, true, true>(p, st) : launch_bwd_rp<T, kBand, false, false, DH, true, true>(p, st);
-}
-
-hipError_t launch_attn_bwd_origin(const BwdParams& p, bool bf16, hipStream_t st) {
-  if (p.D == 128) return bf16 ? launch_bwd_origin_t<__bf16, 128>(p, st) : launch_bwd_origin_t<float, 128>(p, st);
-  return bf16 ? launch_bwd_origin_t<__bf16, 64>(p, st) : launch_bwd_origin_t<float, 64>(p, st);
-}
-#else
 
 template <typename T, int DH>
 static hipError_t launch_bwd_t(const BwdParams& p, int mode, int pack, hipStream_t st) {
-  if (mode == kDense) return launch_bwd_rp<T, kDense, true, false, DH>(p, st);
-  const bool gen = !(p.pat.id_mode == 0 || p.perm_1d);
-  if (pack)                          // packed examples (never with a grid): their own instantiations too
-    return gen ? launch_bwd_rp<T, kBand, true, false, DH, true>(p, st) : launch_bwd_rp<T, kBand, false, false, DH, true>(p, st);
-  if (p.grid.ga > 0)                 // image grid: its own instantiations
-    return gen ? launch_bwd_rp<T, kBand, true, true, DH>(p, st) : launch_bwd_rp<T, kBand, false, true, DH>(p, st);
-  return gen ? launch_bwd_rp<T, kBand, true, false, DH>(p, st) : launch_bwd_rp<T, kBand, false, false, DH>(p, st);
+  if constexpr (kTu.dense) if (mode == kDense) return launch_bwd_rp<T, kDense, true, false, DH>(p, st);
+  if constexpr (kTu.pack_origin) if (pack == kPackOrigin) return launch_bwd_band<T, DH, true, true, true>(p, st);
+  if constexpr (kTu.pack_ids) if (pack == kPackIds) return launch_bwd_band<T, DH, true, false, false>(p, st);
+  if constexpr (kTu.pack_none) if (pack == kPackNone) return launch_bwd_band<T, DH, false, false, true>(p, st);
+  return hipErrorInvalidValue;
 }
 
+// the general kernels; the lean ones (attn_bwd_band.hip) are the host's choice (mmt_api.hip: Route::family)
+hipError_t MMT_TU(launch_attn_bwd)(const BwdParams& p, int mode, bool bf16, int pack, hipStream_t st) {
+  if (p.D == 128) return bf16 ? launch_bwd_t<__bf16, 128>(p, mode, pack, st) : launch_bwd_t<float, 128>(p, mode, pack, st);
+  return bf16 ? launch_bwd_t<__bf16, 64>(p, mode, pack, st) : launch_bwd_t<float, 64>(p, mode, pack, st);
+}
+
+#if !defined(MMT_IMAGE_TU) && !defined(MMT_ORIGIN_TU)
 // the lean path's stand-alone combine / reduce launches (attn_bwd_band.hip): head size 64 only
 hipError_t launch_bwd_dq_combine(const BwdParams& p, bool bf16, hipStream_t st) {
   dim3 grid(p.pat.ng, p.B * p.N);
@@ -941,19 +926,6 @@ hipError_t launch_drel_reduce(const BwdParams& p, bool bf16, hipStream_t st) {
   else hipLaunchKernelGGL((drel_reduce_kernel<float, 64>), dim3(p.Rp + extra, p.N), dim3(1024), 0, st, p);
   return hipGetLastError();
 }
-
-hipError_t launch_attn_bwd(const BwdParams& p, int mode, bool bf16, int pack, hipStream_t st) {
-  // head size 128, the image grid and packed examples: the general kernels only (the lean kernels are built for head size
-  // 64 and for valid_len as the segmented term)
-  pack = mode == kBand ? pack : kPackNone;
-  // MMT_IDS_2D_IMAGE on the general kernels (attn_bwd_image.hip): whatever the lean kernels below do not take
-  const bool lean_takes = mode == kBand && bf16 && !pack && p.D == 64 && p.grid.ga == 0 && p.lean2d;
-  if (mode == kBand && p.ids_go != 0 && p.pat.id_mode == 2 && !lean_takes) return launch_attn_bwd_image(p, bf16, pack, st);
-  if (pack == kPackOrigin) return launch_attn_bwd_origin(p, bf16, st);   // per-example origin: attn_bwd_origin.hip
-  if (p.D == 128) return bf16 ? launch_bwd_t<__bf16, 128>(p, mode, pack, st) : launch_bwd_t<float, 128>(p, mode, pack, st);
-  if (mode == kBand && bf16 && !pack && p.grid.ga == 0 && (p.pat.id_mode == 0 || (p.perm_1d && p.Rp <= 64) || p.lean2d)) return launch_attn_bwd_band_bf16(p, st);
-  return bf16 ? launch_bwd_t<__bf16, 64>(p, mode, pack, st) : launch_bwd_t<float, 64>(p, mode, pack, st);
-}
-#endif  // MMT_ORIGIN_TU
+#endif
 
 }  // namespace mmt

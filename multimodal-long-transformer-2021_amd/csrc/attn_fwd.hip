@@ -465,62 +465,35 @@ static hipError_t launch_rp(const FwdParams& p, dim3 grid, hipStream_t st) {
   return launch_one<T, MODE, 128, GEN, GRID, DH, PACK, ORG>(p, grid, st);
 }
 
-#if defined(MMT_IMAGE_TU)
-// The MMT_IDS_2D_IMAGE instantiations (this file compiled as attn_fwd_image.hip): GEN only (the ids are generated), with and
-// without the grid, example ids and example starts.
-template <typename T, int DH>
-static hipError_t launch_image_t(const FwdParams& p, int pack, dim3 grid, hipStream_t st) {
-  if (pack == kPackOrigin)
-    return p.grid.ga > 0 ? launch_rp<T, kBand, true, true, DH, true, true>(p, grid, st) : launch_rp<T, kBand, true, false, DH, true, true>(p, grid, st);
-  if (pack) return launch_rp<T, kBand, true, false, DH, true>(p, grid, st);
-  return p.grid.ga > 0 ? launch_rp<T, kBand, true, true, DH>(p, grid, st) : launch_rp<T, kBand, true, false, DH>(p, grid, st);
+// GEN and GRID of one (PACK, ORG) pair, as far as this translation unit holds them (kTu, attn_kernels.h).  GRIDS = false:
+// the pair has no GRID instantiation (example ids never come with a grid: refused on the host).
+template <typename T, int DH, bool PACK, bool ORG, bool GRIDS>
+static hipError_t launch_band(const FwdParams& p, dim3 grid, hipStream_t st) {
+  const bool table = kTu.table_ids && (p.pat.id_mode == 0 || p.perm_1d), grd = GRIDS && p.grid.ga > 0;
+  if constexpr (kTu.table_ids && GRIDS) if (table && grd) return launch_rp<T, kBand, false, true, DH, PACK, ORG>(p, grid, st);
+  if constexpr (kTu.table_ids) if (table) return launch_rp<T, kBand, false, false, DH, PACK, ORG>(p, grid, st);
+  if constexpr (GRIDS) if (grd) return launch_rp<T, kBand, true, true, DH, PACK, ORG>(p, grid, st);      // image grid: its own instantiations
+  return launch_rp<T, kBand, true, false, DH, PACK, ORG>(p, grid, st);
 }
-
-hipError_t launch_attn_fwd_image(const FwdParams& p, bool bf16, int pack, hipStream_t st) {
-  const int per_bn = (p.n_chunks * p.n_rowblk + 3) / 4;                 // (no rows items with example starts: n_rowblk = 0)
-  dim3 grid(p.n_band_blocks + per_bn * p.B * p.N);
-  if (p.D == 128) return bf16 ? launch_image_t<__bf16, 128>(p, pack, grid, st) : launch_image_t<float, 128>(p, pack, grid, st);
-  return bf16 ? launch_image_t<__bf16, 64>(p, pack, grid, st) : launch_image_t<float, 64>(p, pack, grid, st);
-}
-#elif defined(MMT_ORIGIN_TU)
-// The per-example-origin instantiations (this file compiled as attn_fwd_origin.hip).  1-D / no ids without a grid read no
-// start, but they too need kernels of their own: the ids of row b lie at [b][0][S] of [B,2,S] here.
-template <typename T, int DH>
-static hipError_t launch_origin_t(const FwdParams& p, dim3 grid, hipStream_t st) {
-  const bool gen = !(p.pat.id_mode == 0 || p.perm_1d);
-  if (p.grid.ga > 0)
-    return gen ? launch_rp<T, kBand, true, true, DH, true, true>(p, grid, st) : launch_rp<T, kBand, false, true, DH, true, true>(p, grid, st);
-  return gen ? launch_rp<T, kBand, true, false, DH, true, true>(p, grid, st) : launch_rp<T, kBand, false, false, DH, true, true>(p, grid, st);
-}
-
-hipError_t launch_attn_fwd_origin(const FwdParams& p, bool bf16, hipStream_t st) {
-  dim3 grid(p.n_band_blocks);
-  if (p.D == 128) return bf16 ? launch_origin_t<__bf16, 128>(p, grid, st) : launch_origin_t<float, 128>(p, grid, st);
-  return bf16 ? launch_origin_t<__bf16, 64>(p, grid, st) : launch_origin_t<float, 64>(p, grid, st);
-}
-#else
 
 template <typename T, int DH>
 static hipError_t launch_t(const FwdParams& p, int mode, int pack, dim3 grid, hipStream_t st) {
-  if (mode == kDense) return launch_rp<T, kDense, true, false, DH>(p, grid, st);
-  const bool gen = !(p.pat.id_mode == 0 || p.perm_1d);
-  if (pack)                          // packed examples (never with a grid: refused on the host): their own instantiations too
-    return gen ? launch_rp<T, kBand, true, false, DH, true>(p, grid, st) : launch_rp<T, kBand, false, false, DH, true>(p, grid, st);
-  if (p.grid.ga > 0)                 // image grid: its own instantiations (the others carry no trace of it)
-    return gen ? launch_rp<T, kBand, true, true, DH>(p, grid, st) : launch_rp<T, kBand, false, true, DH>(p, grid, st);
-  return gen ? launch_rp<T, kBand, true, false, DH>(p, grid, st) : launch_rp<T, kBand, false, false, DH>(p, grid, st);
+  if constexpr (kTu.dense) if (mode == kDense) return launch_rp<T, kDense, true, false, DH>(p, grid, st);
+  if constexpr (kTu.pack_origin) if (pack == kPackOrigin) return launch_band<T, DH, true, true, true>(p, grid, st);
+  if constexpr (kTu.pack_ids) if (pack == kPackIds) return launch_band<T, DH, true, false, false>(p, grid, st);
+  if constexpr (kTu.pack_none) if (pack == kPackNone) return launch_band<T, DH, false, false, true>(p, grid, st);
+  return hipErrorInvalidValue;
 }
 
-hipError_t launch_attn_fwd(const FwdParams& p, int mode, bool bf16, int pack, hipStream_t st) {
-  if (mode == kBand && p.ids_go != 0 && p.pat.id_mode == 2) return launch_attn_fwd_image(p, bf16, pack, st);   // MMT_IDS_2D_IMAGE: attn_fwd_image.hip
-  if (mode == kBand && pack == kPackOrigin) return launch_attn_fwd_origin(p, bf16, st);   // per-example origin: attn_fwd_origin.hip
-  // band items first, then (kBand only) the global-row items of the same launch
+hipError_t MMT_TU(launch_attn_fwd)(const FwdParams& p, int mode, bool bf16, int pack, hipStream_t st) {
+  // band items first, then (kBand only) the global-row items of the same launch (none with example starts: n_rowblk = 0)
   const int per_bn = (p.n_chunks * p.n_rowblk + 3) / 4;
   dim3 grid(p.n_band_blocks + (mode == kBand ? per_bn * p.B * p.N : 0));
   if (p.D == 128) return bf16 ? launch_t<__bf16, 128>(p, mode, pack, grid, st) : launch_t<float, 128>(p, mode, pack, grid, st);
   return bf16 ? launch_t<__bf16, 64>(p, mode, pack, grid, st) : launch_t<float, 64>(p, mode, pack, grid, st);
 }
 
+#if !defined(MMT_IMAGE_TU) && !defined(MMT_ORIGIN_TU)
 template <int DH>
 static hipError_t launch_rows_combine_dh(const FwdParams& p, bool bf16, hipStream_t st) {
   dim3 grid(p.pat.ng, p.B * p.N);
@@ -532,6 +505,6 @@ static hipError_t launch_rows_combine_dh(const FwdParams& p, bool bf16, hipStrea
 hipError_t launch_rows_combine(const FwdParams& p, bool bf16, hipStream_t st) {
   return p.D == 128 ? launch_rows_combine_dh<128>(p, bf16, st) : launch_rows_combine_dh<64>(p, bf16, st);
 }
-#endif  // MMT_ORIGIN_TU
+#endif
 
 }  // namespace mmt

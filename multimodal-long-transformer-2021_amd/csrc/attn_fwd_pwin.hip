@@ -19,12 +19,11 @@
 //
 // LDS per workgroup as in attn_fwd_win.hip: 64 KiB ring + 4 tables + 3 KiB of global-key rows = 81,920 B (two per CU).
 #include "attn_lean.h"
+#include "attn_plan.h"
 
 namespace mmt {
 
 namespace {
-
-constexpr int kPwState = 512 + 256 + 16;      // floats of one rows stream: O^T of 8 rows (16 lanes x 32) | per-lane row sums | 8 maxima (+ pad)
 
 __device__ __forceinline__ unsigned pw_lds_u32(const void* p) {
   return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p;
@@ -697,24 +696,6 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_pwin_bf16_kernel(const FwdPar
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-// Blocks per walk so that all workgroups are resident at once (two per CU); fills pw_walk / walk_maxseg; returns the grid.
-int fwd_pwin_plan(FwdParams& p, int target_wgs) {
-  const int nqb = (p.S + 127) / 128, total = p.B * p.N * nqb;
-  int walk = (total + target_wgs - 1) / target_wgs;
-  if (walk < 1) walk = 1;
-  p.pw_walk = walk;
-  p.walk_maxseg = (nqb + walk - 1) / walk + 1;               // walks that can hold blocks of one plane
-  int grid = (total + walk - 1) / walk;
-  return grid;
-}
-size_t fwd_pwin_workspace_bytes(int B, int N, int S, int target_wgs) {
-  const int nqb = (S + 127) / 128, total = B * N * nqb;
-  const int walk = std::max(1, (total + target_wgs - 1) / target_wgs);
-  const size_t grid = (size_t)(total + walk - 1) / walk;
-  const size_t maxseg = (size_t)(nqb + walk - 1) / walk + 1;
-  return (grid * (8 * 34 + 4 * kPwState) + (size_t)B * N * maxseg * 4 * 8 * 66) * sizeof(float);
-}
-
 hipError_t launch_attn_fwd_pwin_bf16(const FwdParams& p, int grid_size, hipStream_t st) {
   const bool rel = p.R > 0 && p.pat.id_mode == 1;
   const bool drop = p.drop_thresh != 0;

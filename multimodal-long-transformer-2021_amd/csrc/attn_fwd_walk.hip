@@ -29,13 +29,11 @@
 // LDS per workgroup (1-D ids with 2m + 1 <= 25, 8 global tokens): 32 KiB ring + 8 tables of 3,328 B + E image 4 KiB +
 // global keys' rows 3 KiB + rows state 6.3 KiB + small = 75.8 KiB: two workgroups per CU, 16 waves, <= 128 VGPRs.
 #include "attn_lean.h"
+#include "attn_plan.h"
 
 namespace mmt {
 
 namespace {
-
-constexpr int kSlotBytes = 16384;        // K tile 2T | K tile 2T + 1 | V tile 2T | V tile 2T + 1
-constexpr int kRowsState = 2048 + 1024 + 64;      // O^T of 8 rows (16 lanes x 32 floats) | per-lane row sums | 8 maxima
 
 __device__ __forceinline__ unsigned walk_lds_u32(const void* p) {
   return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p;
@@ -56,27 +54,6 @@ __device__ __forceinline__ void step_barrier() {
 __device__ __forceinline__ void wave_fence() {
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
-}
-
-struct WalkLds {
-  int tab, eimg, btab, gk, gv, rst, pbuf, tabg, qimg, flag, total;
-};
-__host__ __device__ inline WalkLds walk_lds(int ng, int tstride, bool rel) {
-  const int ngrp = (ng + 7) / 8;
-  WalkLds L;
-  int o = 2 * kSlotBytes;
-  L.tab = o; o += rel ? 8 * 32 * tstride * 4 : 0;
-  L.eimg = o; o += rel ? 4096 : 0;
-  L.btab = o; o += rel ? 128 : 0;
-  L.gk = o; o += ngrp * 1024;
-  L.gv = o; o += ngrp ? (ngrp + 1) * 1024 : 0;
-  L.rst = o; o += ng ? 2 * kRowsState : 0;
-  L.pbuf = o; o += ng ? 2 * 512 : 0;
-  L.tabg = o; o += (ng && rel) ? 8 * tstride * 4 : 0;
-  L.qimg = o; o += ng ? 1024 : 0;
-  L.flag = o; o += 16 + 32;
-  L.total = o;
-  return L;
 }
 
 }  // namespace
@@ -710,27 +687,6 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_walk_bf16_kernel(const FwdPar
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-int fwd_walk_lds_bytes(int ng, int tstride, bool rel) { return walk_lds(ng, tstride, rel).total; }
-
-// Runs per plane: as many workgroups as fit the chip at once (2 per CU), shared out over the planes; a run is at least
-// one pair of row blocks.  Fills the walk_* fields of `p`; returns the grid size.
-int fwd_walk_plan(FwdParams& p, int target_wgs) {
-  const int BN = p.B * p.N, NT = (p.S + 31) / 32, U = (NT + 1) / 2;
-  const int ngroups = (BN % 8) == 0 ? 8 : 1, ppg = BN / ngroups;
-  int per_group = target_wgs / ngroups;
-  if (per_group > ppg * U) per_group = ppg * U;
-  if (per_group < ppg) per_group = ppg;
-  p.walk_groups = ngroups;
-  p.walk_nseg = per_group / ppg;
-  p.walk_nhi = per_group % ppg;
-  p.walk_maxseg = p.walk_nseg + (p.walk_nhi ? 1 : 0);
-  return ngroups * per_group;
-}
-size_t fwd_walk_workspace_bytes(int B, int N, int S) {      // upper bound over every plan: U runs per plane
-  const int NT = (S + 31) / 32, U = (NT + 1) / 2;
-  return (size_t)B * N * U * 8 * 66 * sizeof(float);
-}
-
 hipError_t launch_attn_fwd_walk_bf16(const FwdParams& p, int grid_size, hipStream_t st) {
   const bool rel = p.R > 0 && p.pat.id_mode == 1;
   const bool drop = p.drop_thresh != 0;

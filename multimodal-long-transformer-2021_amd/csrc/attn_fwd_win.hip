@@ -28,10 +28,9 @@
 // LDS per workgroup: 64 KiB window (re-used for the pair merge) + 4 relative-score tables (row stride 26 floats when 2m + 1 <= 25) + 3 KiB per
 // group of 8 global keys = 81,920 bytes = 64 granules of 1,280 B for the BASELINE pattern: two workgroups per CU.
 #include "attn_lean.h"
+#include "attn_plan.h"
 
 namespace mmt {
-
-constexpr int kWinTiles = 8;
 
 __device__ __forceinline__ unsigned lds_u32(const void* p) {
   return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p;
@@ -830,14 +829,6 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_win_bf16_kernel(const FwdPara
     *reinterpret_cast<bf16x4*>(O + 8 * g + 4 * h) = x;
   }
   if (p.lse && h == 0 && part == 0) p.lse[((long)b * p.N + n) * p.S + q] = (m_tot + log2f(l_tot)) * kLn2;
-}
-
-// LDS bytes of one workgroup (host side; `tstride` as chosen by the caller)
-int fwd_win_lds_bytes(int ng, int tstride) {
-  const int ngrp = (ng + 7) / 8;
-  const int band = 2 * kWinTiles * 4096 + (ngrp ? (2 * ngrp + 1) * 1024 : 0) + 4 * 32 * tstride * 4;
-  const int rows = 8 * (2 * 4096 + 512 + 64) + 8 * 34 * 4 + 4096;          // fwd_rows_body's carve (used when 0 < ng <= 16)
-  return (ng > 0 && ng <= 16 && rows > band) ? rows : band;
 }
 
 hipError_t launch_attn_fwd_win_bf16(const FwdParams& p, hipStream_t st) {

@@ -52,24 +52,30 @@ struct FwdParams {
   int D;              // head size (64 | 128): the launchers' choice of instantiation; 128 runs the general kernels only
 };
 
-// pack (both general launchers): the PACK instantiations -- p.valid_len holds example ids [B,S] (kPackIds), or ids and
-// example starts [B,2,S] (kPackOrigin, MMT_FLAG_EXAMPLE_STARTS: the ORG instantiations of attn_*_origin.hip).  A launcher
-// argument, not a field: the parameter blocks, hence every kernel's argument layout, are what they were.
+// pack (the general launchers): the PACK instantiations -- p.valid_len holds example ids [B,S] (kPackIds), or ids and example
+// starts [B,2,S] (kPackOrigin: the ORG instantiations).  A launcher argument, not a field: the parameter blocks stay what they were.
 enum { kPackNone = 0, kPackIds = 1, kPackOrigin = 2 };
+// The general kernels are three translation units per direction (attn_fwd.hip / attn_bwd.hip alone, and compiled again as
+// .._origin.hip and .._image.hip), each with the same launcher under its own name; the host's route (mmt_api.hip) names the unit.
+struct TuSet { bool dense, table_ids, pack_none, pack_ids, pack_origin; };   // table_ids: GEN = false (no ids, permuted 1-D table) beside GEN = true
+#if defined(MMT_IMAGE_TU)         // MMT_IDS_2D_IMAGE away from origin 0: the ids are generated, with every kind of packing
+constexpr TuSet kTu = {false, false, true, true, true};
+#define MMT_TU(launcher) launcher##_image
+#elif defined(MMT_ORIGIN_TU)      // example starts (the ORG instantiations)
+constexpr TuSet kTu = {false, true, false, false, true};
+#define MMT_TU(launcher) launcher##_origin
+#else
+constexpr TuSet kTu = {true, true, true, true, false};
+#define MMT_TU(launcher) launcher
+#endif
 hipError_t launch_attn_fwd(const FwdParams& p, int mode, bool bf16, int pack, hipStream_t st);
-hipError_t launch_attn_fwd_origin(const FwdParams& p, bool bf16, hipStream_t st);              // attn_fwd_origin.hip
-hipError_t launch_attn_fwd_image(const FwdParams& p, bool bf16, int pack, hipStream_t st);     // attn_fwd_image.hip (MMT_IDS_2D_IMAGE)
+hipError_t launch_attn_fwd_origin(const FwdParams& p, int mode, bool bf16, int pack, hipStream_t st);   // attn_fwd_origin.hip
+hipError_t launch_attn_fwd_image(const FwdParams& p, int mode, bool bf16, int pack, hipStream_t st);    // attn_fwd_image.hip
 hipError_t launch_rows_combine(const FwdParams& p, bool bf16, hipStream_t st);
 hipError_t launch_attn_fwd_band_bf16(const FwdParams& p, hipStream_t st);   // attn_fwd_band.hip
 hipError_t launch_attn_fwd_win_bf16(const FwdParams& p, hipStream_t st);    // attn_fwd_win.hip
-int fwd_win_lds_bytes(int ng, int tstride);
 hipError_t launch_attn_fwd_walk_bf16(const FwdParams& p, int grid_size, hipStream_t st);   // attn_fwd_walk.hip
-int fwd_walk_lds_bytes(int ng, int tstride, bool rel);
-int fwd_walk_plan(FwdParams& p, int target_wgs);
-size_t fwd_walk_workspace_bytes(int B, int N, int S);
 hipError_t launch_attn_fwd_pwin_bf16(const FwdParams& p, int grid_size, hipStream_t st);   // attn_fwd_pwin.hip
-int fwd_pwin_plan(FwdParams& p, int target_wgs);
-size_t fwd_pwin_workspace_bytes(int B, int N, int S, int target_wgs);
 
 struct BwdParams {
   const void *q, *k, *v, *emb, *bias, *out, *dout;
@@ -124,8 +130,8 @@ struct BwdParams {
 };
 
 hipError_t launch_attn_bwd(const BwdParams& p, int mode, bool bf16, int pack, hipStream_t st);
-hipError_t launch_attn_bwd_origin(const BwdParams& p, bool bf16, hipStream_t st);              // attn_bwd_origin.hip
-hipError_t launch_attn_bwd_image(const BwdParams& p, bool bf16, int pack, hipStream_t st);     // attn_bwd_image.hip (MMT_IDS_2D_IMAGE)
+hipError_t launch_attn_bwd_origin(const BwdParams& p, int mode, bool bf16, int pack, hipStream_t st);   // attn_bwd_origin.hip
+hipError_t launch_attn_bwd_image(const BwdParams& p, int mode, bool bf16, int pack, hipStream_t st);    // attn_bwd_image.hip
 hipError_t launch_attn_bwd_band_bf16(const BwdParams& p, hipStream_t st);   // attn_bwd_band.hip
 hipError_t launch_bwd_dq_combine(const BwdParams& p, bool bf16, hipStream_t st);
 hipError_t launch_bwd_dkv_combine(const BwdParams& p, bool bf16, hipStream_t st);

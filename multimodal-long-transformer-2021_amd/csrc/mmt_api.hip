@@ -5,13 +5,13 @@
 #include "../../include/mmt_attn.h"
 
 #include <algorithm>
-#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
-#include "attn_kernels.h"
+#include "attn_plan.h"
 #include "mmt_err.h"
 
 namespace {
@@ -32,29 +32,6 @@ namespace {
 using mmt::fail;
 
 constexpr int kChunkTiles = 8;  // kRows pass: 8 tiles = 256 keys per partial
-
-struct Plan {
-  bool dense;        // literal operator: att_mask / rel_ids from HBM
-  bool split_rows;   // structured pattern with global ROWS handled by the kRows pass
-  int n_rowblk, n_chunks;
-  size_t fwd_ws;     // bytes
-  size_t bwd_ws;
-  int n_split;
-  size_t off_delta, off_relfar, off_drel, off_pdq, off_pdtab, off_pdkv, off_red;  // float offsets
-  size_t off_ho;     // float offset of the P / dS hand-over region (attn_kernels.h), 0 bytes when the shape has none
-  int ho_slots;      // band key tiles per q block there (0 = no hand-over for this shape)
-};
-
-// P / dS hand-over between the two backward passes (lean bf16 kernels, 1-D or no relative ids): shapes it is built for.
-// The global tokens, if any, must be the peeled kind (<= 8, contiguous); the band at most 8 tiles wide.
-int handover_slots(const mmt_attn_desc* d, bool dense) {
-  if (dense || d->dtype != MMT_BF16 || (d->mask.image_grid & 0xFF) || d->D != 64) return 0;     // (an image grid, head size 128: the general kernels)
-  if (d->flags & (MMT_FLAG_EXAMPLE_IDS | MMT_FLAG_EXAMPLE_STARTS)) return 0;                     // (packed examples: likewise)
-  if (d->mask.global_index || d->mask.n_global > 8) return 0;
-  const int W = d->mask.local_radius > d->S ? d->S : d->mask.local_radius;
-  const int slots = 2 * ((W + 31) / 32) + 1;
-  return slots <= 8 ? slots : 0;
-}
 
 // image_grid word of mmt_mask_desc (MMT_IMAGE_GRID): radius a in bits 0-7, first image position g in bits 8-30
 int grid_radius(const mmt_mask_desc& m) { return m.image_grid & 0xFF; }
@@ -161,9 +138,85 @@ mmt::GridDev make_grid(const mmt_mask_desc& m) {
   return g;
 }
 
-Plan make_plan(const mmt_attn_desc* d, bool dense) {
+// Route: which kernel family and which translation unit serve a call.  Decided once, from the descriptor (make_route);
+// the plan, both entry points and the launchers read it and none of them asks the question again.
+enum { kGeneral = 0, kLean = 1 };                    // Route::family
+enum { kTuPlain = 0, kTuOrigin = 1, kTuImage = 2 };  // Route::tu: attn_{fwd,bwd}.hip, .._origin.hip, .._image.hip
+struct Route {
+  int pack;            // kPackNone / kPackIds / kPackOrigin (attn_kernels.h); none with a dense att_mask
+  int perm_1d;         // 1-D ids with R >= 2m+1: table columns permuted, fast path allowed
+  int Rp;              // padded table width of R
+  int lean_rp;         // 2-D ids: the table width (32 | 64) the lean kernels would run at, 0 = they cannot hold the ids
+  int tu, family;      // the general kernels' translation unit; kGeneral | kLean (lean band, window, walk kernels, hand-over)
+  bool extended;       // image grid, head size 128 or packed examples: general kernels, and no peeled global-key step
+  bool lean_features;  // dtype and features admit the lean kernels, whatever the ids (the plan sizes the hand-over by it)
+};
+
+int table_width(int R) { return R <= 32 ? 32 : (R <= 64 ? 64 : 128); }
+
+// 2-D ids on the lean (bf16, structured pattern) kernels: table width that holds every id that can contribute --
+// image ids < (2r+1)^2 + 8, text ids <= 2m, and the two cross-modal part ids P^2 + 8 + 2m + 1 (+ 1) WHEN they are
+// below R (small images: P = 4, m = 3 gives 31 / 32 against R = 49); never more than R (ids >= R contribute 0 under
+// the one-hot lookup).  0 = the lean tables cannot hold them.
+int lean2d_width(const mmt_mask_desc& m, int R) {
+  if (!ids_2d(m) || R <= 0) return 0;
+  const int d = 2 * m.core_layers + 1, n2 = d + 2;
+  if (n2 * n2 > 256) return 0;                       // look-up table of the clamped (dx, dy) grid
+  int need = std::max(d * d + 8, 2 * m.max_dist + 1);
+  const int image_part = m.patches_per_row * m.patches_per_row + 8 + 2 * m.max_dist + 1;
+  if (image_part < R) need = std::max(need, image_part + 2);       // the part ids (image_part, image_part + 1) index real table rows
+  need = std::min(R, need);
+  return need <= 32 ? 32 : (need <= 64 ? 64 : 0);
+}
+
+// "General kernels only": the ONE predicate that keeps a call away from every lean / window / walk / hand-over kernel.
+// A feature the lean kernels do not read (they would take example ids in valid_len for lengths: wrong numbers, no error)
+// is added to `extended` in make_route, nowhere else.
+bool general_only(const Route& r, int id_mode, int R) {
+  return !r.lean_features ||                                             // dense operator, f32, or an extended feature
+         !(id_mode == MMT_IDS_NONE || (r.perm_1d && R <= 64) || r.lean_rp);   // ids the lean tables (up to 64 wide) cannot hold
+}
+
+Route make_route(const mmt_attn_desc* d, bool dense) {
+  const mmt_mask_desc& m = d->mask;
+  const int id_mode = d->R == 0 ? MMT_IDS_NONE : (ids_2d(m) ? MMT_IDS_2D : m.id_mode);      // as the kernels see it (fill_common)
+  Route r;
+  r.pack = (dense || !(d->flags & MMT_FLAG_EXAMPLE_IDS)) ? mmt::kPackNone : ((d->flags & MMT_FLAG_EXAMPLE_STARTS) ? mmt::kPackOrigin : mmt::kPackIds);
+  r.perm_1d = (!dense && id_mode == MMT_IDS_1D && d->R >= 2 * m.max_dist + 1) ? 1 : 0;
+  r.Rp = table_width(d->R);
+  r.extended = r.pack || grid_radius(m) > 0 || d->D != 64;
+  r.lean_features = !dense && d->dtype == MMT_BF16 && !r.extended;
+  r.lean_rp = (dense || r.extended) ? 0 : lean2d_width(m, d->R);
+  r.family = general_only(r, id_mode, d->R) ? kGeneral : kLean;
+  // MMT_IDS_2D_IMAGE away from origin 0 and example starts have general kernels of their own
+  r.tu = dense ? kTuPlain : ((id_mode == MMT_IDS_2D && ids_origin(m) != 0) ? kTuImage : (r.pack == mmt::kPackOrigin ? kTuOrigin : kTuPlain));
+  return r;
+}
+
+constexpr decltype(&mmt::launch_attn_fwd) kGeneralFwd[] = {mmt::launch_attn_fwd, mmt::launch_attn_fwd_origin, mmt::launch_attn_fwd_image};
+constexpr decltype(&mmt::launch_attn_bwd) kGeneralBwd[] = {mmt::launch_attn_bwd, mmt::launch_attn_bwd_origin, mmt::launch_attn_bwd_image};
+
+struct Plan {
+  bool split_rows;   // structured pattern with global ROWS handled by the kRows pass
+  int n_rowblk, n_chunks, n_split;
+  size_t fwd_ws, bwd_ws;     // bytes
+  size_t off_delta, off_relfar, off_drel, off_pdq, off_pdtab, off_pdkv, off_red;  // float offsets
+  size_t off_ho;     // float offset of the P / dS hand-over region (attn_kernels.h), 0 bytes when the shape has none
+  int ho_slots;      // band key tiles per q block there (0 = no hand-over for this shape)
+};
+
+// P / dS hand-over between the two backward passes (lean bf16 kernels, 1-D or no relative ids): shapes it is built for.
+// The global tokens, if any, must be the peeled kind (<= 8, contiguous); the band at most 8 tiles wide.
+int handover_slots(const mmt_attn_desc* d, const Route& r) {
+  if (!r.lean_features || d->mask.global_index || d->mask.n_global > 8) return 0;
+  const int W = d->mask.local_radius > d->S ? d->S : d->mask.local_radius;
+  const int slots = 2 * ((W + 31) / 32) + 1;
+  return slots <= 8 ? slots : 0;
+}
+
+// The workspace is sized as a superset over the routes: whatever kernel the forward picks, whatever the ids.
+Plan make_plan(const mmt_attn_desc* d, bool dense, const Route& r) {
   Plan pl{};
-  pl.dense = dense;
   const int n_tiles = (d->S + 31) / 32;
   pl.split_rows = !dense && d->mask.n_global > 0 && d->mask.local_radius < d->S;
   pl.n_rowblk = pl.split_rows ? (d->mask.n_global + 31) / 32 : 0;
@@ -178,7 +231,7 @@ Plan make_plan(const mmt_attn_desc* d, bool dense) {
     pl.fwd_ws = std::max(pl.fwd_ws, mmt::fwd_pwin_workspace_bytes(d->B, d->N, d->S, 2 * 256));
   }
   // backward: delta, dRel, global-row / global-key partials, dE partials (floats)
-  const size_t bn = (size_t)d->B * d->N, Rp = d->R <= 32 ? 32 : (d->R <= 64 ? 64 : 128);
+  const size_t bn = (size_t)d->B * d->N, Rp = r.Rp;
   pl.n_split = (int)std::min<size_t>(256, ((size_t)d->B * d->S + 255) / 256);
   pl.off_delta = 0;
   pl.off_relfar = pl.off_delta + bn * d->S;
@@ -189,51 +242,152 @@ Plan make_plan(const mmt_attn_desc* d, bool dense) {
   pl.off_pdkv = pl.off_pdtab + bn * pl.n_rowblk * pl.n_chunks * (32 * Rp);
   pl.off_red = pl.off_pdkv + bn * pl.n_rowblk * (pl.n_chunks + (d64 ? 1 : 0)) * (2 * 32 * D);      // (+ 1: the hand-over's band slot)
   pl.off_ho = (pl.off_red + bn * ((d->S + 127) / 128) * 4 * (Rp * D + Rp) + 3) & ~(size_t)3;
-  pl.ho_slots = handover_slots(d, dense);
+  pl.ho_slots = handover_slots(d, r);
   const size_t ho_bytes = pl.ho_slots ? bn * n_tiles * ((size_t)pl.ho_slots * 2048 + 1024) : 0;
   pl.bwd_ws = pl.off_ho * sizeof(float) + ho_bytes;
   return pl;
 }
 
-// 2-D ids on the lean (bf16, structured pattern) kernels: table width that holds every id that can contribute --
-// image ids < (2r+1)^2 + 8, text ids <= 2m, and the two cross-modal part ids P^2 + 8 + 2m + 1 (+ 1) WHEN they are
-// below R (small images: P = 4, m = 3 gives 31 / 32 against R = 49); never more than R (ids >= R contribute 0 under
-// the one-hot lookup).  0 = not eligible (the general kernels of attn_fwd.hip / attn_bwd.hip take
-// the call).
-int lean2d_width(const mmt::PatternDev& pat, const mmt::GridDev& grid, int R, int D, bool dense, bool pack) {
-  if (dense || pack || pat.id_mode != MMT_IDS_2D || R <= 0 || grid.ga > 0 || D != 64) return 0;
-  const int d = 2 * pat.r + 1, n2 = d + 2;
-  if (n2 * n2 > 256) return 0;                       // look-up table of the clamped (dx, dy) grid
-  int need = std::max(d * d + 8, 2 * pat.m + 1);
-  if (pat.image_part < R) need = std::max(need, pat.text_part + 1);       // the part ids index real table rows
-  need = std::min(R, need);
-  return need <= 32 ? 32 : (need <= 64 ? 64 : 0);
+// What both entry points establish before they fill a parameter block: valid descriptor and operands, dense or structured,
+// route, plan.  `missing` / `no_table`: the caller's operand errors, reported after the descriptor's and before the mask's.
+struct Call { bool dense; Route route; Plan plan; };
+int prepare(const mmt_attn_desc* desc, const int32_t* att_mask, const int32_t* rel_ids, const char* missing, const char* no_table, Call& c) {
+  if (int rc = check_desc(desc)) return rc;
+  if (missing) return fail(MMT_E_INVALID, "%s", missing);
+  if (desc->R > 0 && no_table) return fail(MMT_E_INVALID, "%s", no_table);
+  c.dense = att_mask != nullptr || rel_ids != nullptr;
+  if (!c.dense && desc->mask.global_index && desc->mask.n_global > 0)
+    return fail(MMT_E_UNSUPPORTED, "a listed global-token set has no structured kernel: materialise att_mask with mmt_side_inputs(materialize_pattern = 1) and pass it (dense operator)");
+  if (!c.dense) if (int rc = check_packed(desc)) return rc;
+  c.route = make_route(desc, c.dense);
+  c.plan = make_plan(desc, c.dense, c.route);
+  return MMT_OK;
 }
 
-void fill_common(mmt::FwdParams& p, const mmt_attn_desc* d) {
+// the fields FwdParams and BwdParams share
+template <typename P>
+void fill_common(P& p, const mmt_attn_desc* d, const Route& r) {
   std::memset(&p, 0, sizeof(p));
-  p.rows_parts = 1;
   p.B = d->B; p.S = d->S; p.N = d->N; p.R = d->R; p.D = d->D;
-  for (int i = 0; i < 3; ++i) {
-    p.qs[i] = d->q_stride[i]; p.ks[i] = d->k_stride[i];
-    p.vs[i] = d->v_stride[i]; p.os[i] = d->o_stride[i];
-  }
+  for (int i = 0; i < 3; ++i) { p.qs[i] = d->q_stride[i]; p.ks[i] = d->k_stride[i]; p.vs[i] = d->v_stride[i]; p.os[i] = d->o_stride[i]; }
   p.sscale = d->scale * mmt::kLog2e;
   p.tscale = (d->flags & MMT_FLAG_SCALE_BEFORE_ADD) ? mmt::kLog2e : d->scale * mmt::kLog2e;
   p.mask_add = d->mask_value * mmt::kLog2e;
   p.pat = make_pattern(d->mask, d->S);
+  if (d->R == 0) p.pat.id_mode = 0;
   p.grid = make_grid(d->mask);
   p.ids_go = ids_origin(d->mask);
   p.valid_len = d->mask.valid_len;
+  p.perm_1d = r.perm_1d;
+  p.n_band_blocks = d->B * d->N * ((d->S + 127) / 128);
   if (d->dropout_p > 0.f) {
     unsigned t = (unsigned)((double)d->dropout_p * 65536.0 + 0.5);
     p.drop_thresh = t < 1 ? 1 : (t > 65535 ? 65535 : t);
     p.inv_keep = 65536.f / (65536.f - (float)p.drop_thresh);   // exact keep probability of the 16-bit test
-    p.seed_lo = (uint32_t)d->dropout_seed;
-    p.seed_hi = (uint32_t)(d->dropout_seed >> 32);
+    p.seed_lo = (uint32_t)d->dropout_seed; p.seed_hi = (uint32_t)(d->dropout_seed >> 32);
     p.epoch = reinterpret_cast<const unsigned long long*>(d->dropout_epoch);
   }
 }
+
+// -DMMT_STAMP diagnostic builds only: where the kernels stamp, and their ablations
+template <typename P>
+void read_stamp_env(P& p) {
+#ifdef MMT_STAMP
+  if (const char* v = std::getenv("MMT_DBG_PTR")) p.dbg = reinterpret_cast<long long*>(std::strtoull(v, nullptr, 0));
+  if (const char* v = std::getenv("MMT_DBG_MODE")) p.dbg_mode = std::atoi(v);
+  if constexpr (std::is_same_v<P, mmt::FwdParams>)
+    if (const char* v = std::getenv("MMT_DBG_SLEEP")) p.dbg_sleep = std::atoi(v);
+#endif
+}
+
+// Forward: which kernel runs.  choose_fwd decides (and fills the plan fields of the walk / sliding-window kernels, p.walk_* /
+// p.pw_walk); mmt_attn_fwd launches what it returns.  kFwdGeneral / kFwdLean: band kernel (+ rows combine); kFwdWin: the rows
+// of the global tokens, if any, in the window launch; kFwdWinRows: after it the lean band kernel's row items + combine.
+enum FwdKernel { kFwdDense, kFwdGeneral, kFwdLean, kFwdWin, kFwdWinRows, kFwdWalk, kFwdPwin };
+struct FwdChoice {
+  FwdKernel kernel;
+  int grid;                  // plane-walk / sliding-window kernels: workgroups
+  int n_rowblk, rows_parts;  // window kernel: its (plane, 8 rows) groups (0: the rows are not its business), workgroups per group
+  int rows_only;             // the band launch after the window kernel holds the global-row items only
+  bool counters;             // partials merged by the last arriver: desc->sync and the workspace (walk_part) go with the launch
+  float part_scale;
+};
+FwdChoice choose_fwd(const mmt_attn_desc* desc, const Call& c, mmt::FwdParams& p, const void* workspace, size_t workspace_bytes) {
+  const Plan& pl = c.plan;
+  if (c.dense) return {kFwdDense, 0, 0, 1, 0, false, 0.f};      // (no combine launch: no factor)
+  // every lean / window / walk kernel below needs `lean` (general_only): no tuning switch can route a call past it
+  const bool lean = c.route.family == kLean;       // attn_fwd_band.hip (tables up to 64 wide)
+  FwdChoice ch = {lean ? kFwdLean : kFwdGeneral, 0, p.n_rowblk, 1, 0, false, (lean && p.drop_thresh) ? p.inv_keep : 1.f};
+  if (!lean) return ch;
+  // window kernel (attn_fwd_win.hip): K / V staged once per workgroup, global keys as a peeled quarter-tile step,
+  // rows of up to 16 global tokens by flipped-orientation workgroups of the same launch (no workspace, no combine
+  // launch).  Shapes it does not cover, or whose LDS need leaves one workgroup per CU, stay with the per-wave staging
+  // kernel.  desc->tuning: MMT_TUNE_FWD_NO_WIN turns it off, MMT_TUNE_FWD_FORCE_WIN takes it whenever the shape is
+  // covered (the tests run both).
+  const int win_mode = (desc->tuning & MMT_TUNE_FWD_NO_WIN) ? 0 : ((desc->tuning & MMT_TUNE_FWD_FORCE_WIN) ? 2 : 1);
+  // plane-walk kernel (attn_fwd_walk.hip): persistent workgroups walking runs of row blocks down the band, K / V
+  // sliding through a two-slot LDS ring, the rows of <= 8 global tokens merged from the runs' partials by the last
+  // arriver of each plane (needs the caller's arrival counters, desc->sync).  OPT-IN (MMT_TUNE_FWD_WALK): measured
+  // slower than the window / per-wave kernels at every BASELINE shape (DESIGN.md section 4, round 4) -- at per-GPU
+  // batch 4 a plane walk has 12 row blocks per run, and filling / draining the diagonal costs 3 of its 9 super-steps.
+  const bool walk_shape = !p.lean_rp && desc->R <= 32 && p.pat.radius <= 64 && p.pat.ng <= 8 &&
+                          (p.pat.ng == 0 || pl.split_rows) && desc->S > 32;
+  const bool walk_sync = p.pat.ng == 0 || (desc->sync && desc->sync_words >= (uint32_t)(desc->B * desc->N));
+  if (walk_shape && walk_sync && (desc->tuning & MMT_TUNE_FWD_WALK) &&
+      mmt::fwd_walk_lds_bytes(p.pat.ng, p.tstride, p.pat.id_mode != 0) <= 81920) {
+    ch.kernel = kFwdWalk; ch.counters = true;
+    ch.grid = mmt::fwd_walk_plan(p, 2 * 256);      // two resident workgroups per compute unit of an MI355X
+    return ch;
+  }
+  // sliding-window kernel (attn_fwd_pwin.hip): the window kernel made persistent -- <= 512 resident workgroups walking
+  // consecutive 128-row blocks, four new K / V tiles per block by LDS-DMA, the next block's Q under the merge, the rows
+  // of <= 8 global tokens by the pairs' second waves beside the table build and merged by the plane's last arriver.
+  // OPT-IN (MMT_TUNE_FWD_PWIN): correct on every case of the forward tests, measured slower than the window kernel
+  // (config 3: 41.9 vs 37.9 us without global tokens, 96 vs 43 us with 8; stamps in profiles/r04_pwin_stamps_*.txt,
+  // DESIGN.md section 4, round 4).
+  const bool pwin_shape = !p.lean_rp && desc->R <= 32 && p.pat.radius <= 64 && p.pat.ng <= 8 && p.tstride <= 26 &&
+                          (p.pat.ng == 0 || (pl.split_rows && p.pat.radius > 32));
+  if (pwin_shape && walk_sync && (desc->tuning & MMT_TUNE_FWD_PWIN)) {
+    ch.grid = mmt::fwd_pwin_plan(p, 2 * 256);
+    if (p.pat.ng == 0 || p.walk_maxseg <= 51) {            // (the last arriver's merge keeps a (max, sum) pair per partial in LDS)
+      ch.kernel = kFwdPwin; ch.counters = true;
+      return ch;
+    }
+  }
+  const bool win_ok = !p.lean_rp && desc->R <= 32 && p.pat.radius <= 64 && p.pat.ng <= 128;
+  // The window kernel's flipped-rows workgroups walk the key tiles of their plane, 8 waves x S / 256 tiles each when one
+  // workgroup takes a (plane, 8 rows) group alone: under the band workgroups it shares its CU with it then lives about
+  // as long as the launch at S = 4096 and longer at S = 8192 (config 5, g = 8: window 52.7 us, per-wave 47.1 us per
+  // call).  With the caller's arrival counters (desc->sync) the group is split over the keys -- S / 2048 workgroups, at
+  // most four, merged by the plane's last arriver -- and the window kernel wins at both lengths (config 3: 41.6 against
+  // 44.0 us unsplit and 45.8 per-wave; config 5: 41.8 against 45.9).  Without counters it keeps S <= 4096 only.
+  // Without global tokens the window kernel has nothing to win -- what it made cheaper is the global tokens -- and the
+  // per-wave kernel, whose waves never meet at a barrier, is 5-7 % faster (config 3 shape, dropout 0.1: 34.8-35.4
+  // against 36.9-37.9 us, two boxes).
+  const bool can_split_rows = desc->sync && desc->sync_words >= (uint32_t)(desc->B * desc->N) && workspace &&
+                              !(desc->tuning & MMT_TUNE_FWD_ROWS_ONE_WG);
+  const bool win = win_ok && win_mode != 0 &&
+                   (win_mode == 2 || (mmt::fwd_win_lds_bytes(p.pat.ng, p.tstride) <= 81920 && p.pat.ng > 0 &&
+                                      (desc->S <= 4096 || (can_split_rows && p.pat.ng <= 16))));
+  if (!win) return ch;
+  // rows of the global tokens: at most 16 -> extra workgroups of the window launch (8 rows each, no workspace, no
+  // combine launch); more -> the 32-row items of the per-wave kernel + combine, as a launch of their own
+  const bool rows_in_win = pl.split_rows && p.pat.ng <= 16;
+  ch.kernel = (!pl.split_rows || rows_in_win) ? kFwdWin : kFwdWinRows;
+  ch.rows_only = ch.kernel == kFwdWinRows;
+  ch.n_rowblk = rows_in_win ? (p.pat.ng + 7) / 8 : 0;
+  // each (plane, 8 rows) group by up to four workgroups, a quarter of the keys each, merged by the plane's last arriver:
+  // needs the caller's arrival counters (desc->sync); without them one workgroup walks all keys, as until round 4
+  if (rows_in_win && can_split_rows) {
+    const int n_tiles = (desc->S + 31) / 32;
+    ch.rows_parts = std::max(1, std::min(4, n_tiles / 64));
+    if ((size_t)desc->B * desc->N * ch.n_rowblk * ch.rows_parts * 8 * 66 * sizeof(float) > workspace_bytes) ch.rows_parts = 1;
+    ch.counters = true;
+  }
+  return ch;
+}
+
+int launched(hipError_t e, const char* what) { return e == hipSuccess ? MMT_OK : fail(MMT_E_LAUNCH, "%s launch: %s", what, hipGetErrorString(e)); }
 
 }  // namespace
 
@@ -254,7 +408,7 @@ const char* mmt_last_error(void) { return g_err; }
 
 size_t mmt_workspace_bytes(const mmt_attn_desc* desc) {
   if (check_desc(desc) != MMT_OK || check_packed(desc) != MMT_OK) return 0;
-  Plan pl = make_plan(desc, false);   // the structured plan is a superset of the dense one
+  const Plan pl = make_plan(desc, false, make_route(desc, false));   // the structured plan is a superset of the dense one
   return pl.fwd_ws > pl.bwd_ws ? pl.fwd_ws : pl.bwd_ws;
 }
 
@@ -262,136 +416,52 @@ int mmt_attn_fwd(const mmt_attn_desc* desc, const void* q, const void* k, const 
                  const void* rel_emb, const void* rel_bias, const int32_t* att_mask,
                  const int32_t* rel_ids, void* out, float* lse, void* workspace,
                  size_t workspace_bytes, void* stream) {
-  if (int rc = check_desc(desc)) return rc;
-  if (!q || !k || !v || !out) return fail(MMT_E_INVALID, "q, k, v, out must not be NULL");
-  if (desc->R > 0 && !rel_emb) return fail(MMT_E_INVALID, "R > 0 but rel_emb is NULL");
-  const bool dense = att_mask != nullptr || rel_ids != nullptr;
-  if (!dense && desc->mask.global_index && desc->mask.n_global > 0)
-    return fail(MMT_E_UNSUPPORTED, "a listed global-token set has no structured kernel: materialise att_mask with mmt_side_inputs(materialize_pattern = 1) and pass it (dense operator)");
-  if (!dense) if (int rc = check_packed(desc)) return rc;
-  const int pack = (dense || !(desc->flags & MMT_FLAG_EXAMPLE_IDS)) ? mmt::kPackNone
-                   : ((desc->flags & MMT_FLAG_EXAMPLE_STARTS) ? mmt::kPackOrigin : mmt::kPackIds);
-  const Plan pl = make_plan(desc, dense);
+  Call c;
+  if (int rc = prepare(desc, att_mask, rel_ids, (!q || !k || !v || !out) ? "q, k, v, out must not be NULL" : nullptr,
+                       !rel_emb ? "R > 0 but rel_emb is NULL" : nullptr, c)) return rc;
+  const Plan& pl = c.plan;
   if (pl.fwd_ws > 0 && (!workspace || workspace_bytes < pl.fwd_ws))
     return fail(MMT_E_WORKSPACE, "workspace too small: need %zu bytes, got %zu", pl.fwd_ws, workspace_bytes);
 
   mmt::FwdParams p;
-  fill_common(p, desc);
+  fill_common(p, desc, c.route);
+  p.rows_parts = 1;
   p.q = q; p.k = k; p.v = v; p.emb = rel_emb; p.bias = rel_bias; p.out = out; p.lse = lse;
-  p.att_mask = att_mask; p.rel_ids = rel_ids;
-  if (desc->R == 0) { p.pat.id_mode = 0; p.rel_ids = nullptr; }
-  p.n_band_blocks = desc->B * desc->N * ((desc->S + 127) / 128);
-  p.perm_1d = (!dense && p.pat.id_mode == MMT_IDS_1D && desc->R >= 2 * p.pat.m + 1) ? 1 : 0;
+  p.att_mask = att_mask; p.rel_ids = desc->R == 0 ? nullptr : rel_ids;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const bool bf16 = desc->dtype == MMT_BF16;
-
-  hipError_t e;
-  if (dense) {
-    e = mmt::launch_attn_fwd(p, mmt::kDense, bf16, mmt::kPackNone, st);
-    if (e != hipSuccess) return fail(MMT_E_LAUNCH, "dense forward launch: %s", hipGetErrorString(e));
-    return MMT_OK;
-  }
-  p.skip_global_rows = pl.split_rows ? 1 : 0;
-  if (pl.split_rows) {
-    p.n_rowblk = pl.n_rowblk; p.n_chunks = pl.n_chunks; p.chunk_tiles = kChunkTiles;
-    p.part_o = reinterpret_cast<float*>(workspace);
-    p.part_ml = p.part_o + (size_t)desc->B * desc->N * pl.n_rowblk * pl.n_chunks * (32 * desc->D);
-  }
-  p.lean_rp = lean2d_width(p.pat, p.grid, desc->R, desc->D, dense, pack);
-  // an image grid (p.grid.ga > 0), head size 128 and packed examples (MMT_FLAG_EXAMPLE_IDS: valid_len holds ids there, which
-  // only the PACK instantiations read as such) are served by the general kernels only (attn_fwd.hip): every lean /
-  // window / walk kernel below needs `lean`, so no tuning switch can route them past it
-  const bool lean = bf16 && !pack && p.grid.ga == 0 && desc->D == 64 && (p.pat.id_mode == 0 || (p.perm_1d && desc->R <= 64) || p.lean_rp);   // attn_fwd_band.hip (tables up to 64 wide)
-  p.part_scale = (lean && p.drop_thresh) ? p.inv_keep : 1.f;
-  // window kernel (attn_fwd_win.hip): K / V staged once per workgroup, global keys as a peeled quarter-tile step,
-  // rows of up to 16 global tokens by flipped-orientation workgroups of the same launch (no workspace, no combine
-  // launch).  Shapes it does not cover, or whose LDS need leaves one workgroup per CU, stay with the per-wave staging
-  // kernel.  desc->tuning: MMT_TUNE_FWD_NO_WIN turns it off, MMT_TUNE_FWD_FORCE_WIN takes it whenever the shape is
-  // covered (the tests run both).
-  const int win_mode = (desc->tuning & MMT_TUNE_FWD_NO_WIN) ? 0 : ((desc->tuning & MMT_TUNE_FWD_FORCE_WIN) ? 2 : 1);
-  p.tstride = p.pat.id_mode == 0 ? 0 : (2 * p.pat.m + 1 <= 25 ? 26 : 34);
-#ifdef MMT_STAMP
-  if (const char* v = std::getenv("MMT_DBG_PTR")) p.dbg = reinterpret_cast<long long*>(std::strtoull(v, nullptr, 0));
-  if (const char* v = std::getenv("MMT_DBG_MODE")) p.dbg_mode = std::atoi(v);
-  if (const char* v = std::getenv("MMT_DBG_SLEEP")) p.dbg_sleep = std::atoi(v);
-#endif
-  // plane-walk kernel (attn_fwd_walk.hip): persistent workgroups walking runs of row blocks down the band, K / V
-  // sliding through a two-slot LDS ring, the rows of <= 8 global tokens merged from the runs' partials by the last
-  // arriver of each plane (needs the caller's arrival counters, desc->sync).  OPT-IN (MMT_TUNE_FWD_WALK): measured
-  // slower than the window / per-wave kernels at every BASELINE shape (DESIGN.md section 4, round 4) -- at per-GPU
-  // batch 4 a plane walk has 12 row blocks per run, and filling / draining the diagonal costs 3 of its 9 super-steps.
-  const bool walk_shape = lean && !p.lean_rp && desc->R <= 32 && p.pat.radius <= 64 && p.pat.ng <= 8 &&
-                          (p.pat.ng == 0 || pl.split_rows) && desc->S > 32;
-  const bool walk_sync = p.pat.ng == 0 || (desc->sync && desc->sync_words >= (uint32_t)(desc->B * desc->N));
-  if (walk_shape && walk_sync && (desc->tuning & MMT_TUNE_FWD_WALK) &&
-      mmt::fwd_walk_lds_bytes(p.pat.ng, p.tstride, p.pat.id_mode != 0) <= 81920) {
-    const int grid = mmt::fwd_walk_plan(p, 2 * 256);      // two resident workgroups per compute unit of an MI355X
-    p.walk_part = reinterpret_cast<float*>(workspace);
-    p.sync = desc->sync;
-    e = mmt::launch_attn_fwd_walk_bf16(p, grid, st);
-    if (e != hipSuccess) return fail(MMT_E_LAUNCH, "plane-walk forward launch: %s", hipGetErrorString(e));
-    return MMT_OK;
-  }
-  // sliding-window kernel (attn_fwd_pwin.hip): the window kernel made persistent -- <= 512 resident workgroups walking
-  // consecutive 128-row blocks, four new K / V tiles per block by LDS-DMA, the next block's Q under the merge, the rows
-  // of <= 8 global tokens by the pairs' second waves beside the table build and merged by the plane's last arriver.
-  // OPT-IN (MMT_TUNE_FWD_PWIN): correct on every case of the forward tests, measured slower than the window kernel
-  // (config 3: 41.9 vs 37.9 us without global tokens, 96 vs 43 us with 8; stamps in profiles/r04_pwin_stamps_*.txt,
-  // DESIGN.md section 4, round 4).
-  const bool pwin_shape = lean && !p.lean_rp && desc->R <= 32 && p.pat.radius <= 64 && p.pat.ng <= 8 && p.tstride <= 26 &&
-                          (p.pat.ng == 0 || (pl.split_rows && p.pat.radius > 32));
-  if (pwin_shape && walk_sync && (desc->tuning & MMT_TUNE_FWD_PWIN)) {
-    const int grid = mmt::fwd_pwin_plan(p, 2 * 256);
-    if (p.pat.ng == 0 || p.walk_maxseg <= 51) {            // (the last arriver's merge keeps a (max, sum) pair per partial in LDS)
-      p.walk_part = reinterpret_cast<float*>(workspace);
-      p.sync = desc->sync;
-      e = mmt::launch_attn_fwd_pwin_bf16(p, grid, st);
-      if (e != hipSuccess) return fail(MMT_E_LAUNCH, "sliding-window forward launch: %s", hipGetErrorString(e));
-      return MMT_OK;
+  if (!c.dense) {
+    p.skip_global_rows = pl.split_rows ? 1 : 0;
+    if (pl.split_rows) {
+      p.n_rowblk = pl.n_rowblk; p.n_chunks = pl.n_chunks; p.chunk_tiles = kChunkTiles;
+      p.part_o = reinterpret_cast<float*>(workspace);
+      p.part_ml = p.part_o + (size_t)desc->B * desc->N * pl.n_rowblk * pl.n_chunks * (32 * desc->D);
     }
+    p.lean_rp = c.route.lean_rp;
+    p.tstride = p.pat.id_mode == 0 ? 0 : (2 * p.pat.m + 1 <= 25 ? 26 : 34);
+    read_stamp_env(p);
   }
-  const bool win_ok = lean && !p.lean_rp && desc->R <= 32 && p.pat.radius <= 64 && p.pat.ng <= 128;
-  // The window kernel's flipped-rows workgroups walk the key tiles of their plane, 8 waves x S / 256 tiles each when one
-  // workgroup takes a (plane, 8 rows) group alone: under the band workgroups it shares its CU with it then lives about
-  // as long as the launch at S = 4096 and longer at S = 8192 (config 5, g = 8: window 52.7 us, per-wave 47.1 us per
-  // call).  With the caller's arrival counters (desc->sync) the group is split over the keys -- S / 2048 workgroups, at
-  // most four, merged by the plane's last arriver -- and the window kernel wins at both lengths (config 3: 41.6 against
-  // 44.0 us unsplit and 45.8 per-wave; config 5: 41.8 against 45.9).  Without counters it keeps S <= 4096 only.
-  // Without global tokens the window kernel has nothing to win -- what it made cheaper is the global tokens -- and the
-  // per-wave kernel, whose waves never meet at a barrier, is 5-7 % faster (config 3 shape, dropout 0.1: 34.8-35.4
-  // against 36.9-37.9 us, two boxes).
-  const bool can_split_rows = desc->sync && desc->sync_words >= (uint32_t)(desc->B * desc->N) && workspace &&
-                              !(desc->tuning & MMT_TUNE_FWD_ROWS_ONE_WG);
-  const bool win = win_ok && win_mode != 0 &&
-                   (win_mode == 2 || (mmt::fwd_win_lds_bytes(p.pat.ng, p.tstride) <= 81920 && p.pat.ng > 0 &&
-                                      (desc->S <= 4096 || (can_split_rows && p.pat.ng <= 16))));
-  if (win) {
-    // rows of the global tokens: at most 16 -> extra workgroups of the window launch (8 rows each, no workspace, no
-    // combine launch); more -> the 32-row items of the per-wave kernel + combine, as a launch of their own
-    const bool rows_in_win = pl.split_rows && p.pat.ng <= 16;
-    const int n_rowblk_items = p.n_rowblk;
-    p.n_rowblk = rows_in_win ? (p.pat.ng + 7) / 8 : 0;
-    // each (plane, 8 rows) group by up to four workgroups, a quarter of the keys each, merged by the plane's last arriver:
-    // needs the caller's arrival counters (desc->sync); without them one workgroup walks all keys, as until round 4
-    p.rows_parts = 1;
-    if (rows_in_win && can_split_rows) {
-      const int n_tiles = (desc->S + 31) / 32;
-      p.rows_parts = std::max(1, std::min(4, n_tiles / 64));
-      if ((size_t)desc->B * desc->N * p.n_rowblk * p.rows_parts * 8 * 66 * sizeof(float) > workspace_bytes) p.rows_parts = 1;
-      p.walk_part = reinterpret_cast<float*>(workspace);
-      p.sync = desc->sync;
+  const FwdChoice ch = choose_fwd(desc, c, p, workspace, workspace_bytes);
+  p.part_scale = ch.part_scale;
+  if (ch.counters) { p.walk_part = reinterpret_cast<float*>(workspace); p.sync = desc->sync; }
+  switch (ch.kernel) {
+    case kFwdDense: return launched(kGeneralFwd[c.route.tu](p, mmt::kDense, bf16, c.route.pack, st), "dense forward");
+    case kFwdWalk: return launched(mmt::launch_attn_fwd_walk_bf16(p, ch.grid, st), "plane-walk forward");
+    case kFwdPwin: return launched(mmt::launch_attn_fwd_pwin_bf16(p, ch.grid, st), "sliding-window forward");
+    case kFwdWin:
+    case kFwdWinRows:
+      p.n_rowblk = ch.n_rowblk; p.rows_parts = ch.rows_parts;
+      if (int rc = launched(mmt::launch_attn_fwd_win_bf16(p, st), "window forward")) return rc;
+      if (ch.kernel == kFwdWin) return MMT_OK;
+      p.n_rowblk = pl.n_rowblk; p.rows_only = ch.rows_only;      // the 32-row items of the lean band kernel
+      [[fallthrough]];
+    case kFwdLean:
+    case kFwdGeneral: {
+      const hipError_t e = ch.kernel == kFwdGeneral ? kGeneralFwd[c.route.tu](p, mmt::kBand, bf16, c.route.pack, st)
+                                                    : mmt::launch_attn_fwd_band_bf16(p, st);
+      if (int rc = launched(e, "band forward")) return rc;
+      return pl.split_rows ? launched(mmt::launch_rows_combine(p, bf16, st), "global-rows combine") : MMT_OK;
     }
-    e = mmt::launch_attn_fwd_win_bf16(p, st);
-    if (e != hipSuccess) return fail(MMT_E_LAUNCH, "window forward launch: %s", hipGetErrorString(e));
-    if (!pl.split_rows || rows_in_win) return MMT_OK;
-    p.n_rowblk = n_rowblk_items;
-    p.rows_only = 1;
-  }
-  e = lean ? mmt::launch_attn_fwd_band_bf16(p, st) : mmt::launch_attn_fwd(p, mmt::kBand, bf16, pack, st);
-  if (e != hipSuccess) return fail(MMT_E_LAUNCH, "band forward launch: %s", hipGetErrorString(e));
-  if (pl.split_rows) {
-    e = mmt::launch_rows_combine(p, bf16, st);
-    if (e != hipSuccess) return fail(MMT_E_LAUNCH, "global-rows combine launch: %s", hipGetErrorString(e));
   }
   return MMT_OK;
 }
@@ -401,49 +471,28 @@ int mmt_attn_bwd(const mmt_attn_desc* desc, const void* q, const void* k, const 
                  const int32_t* rel_ids, const void* out, const void* dout, const float* lse,
                  void* dq, void* dk, void* dv, float* drel_emb, float* drel_bias,
                  void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = check_desc(desc)) return rc;
-  if (!q || !k || !v || !out || !dout || !lse || !dq || !dk || !dv)
-    return fail(MMT_E_INVALID, "q, k, v, out, dout, lse, dq, dk, dv must not be NULL");
-  if (desc->R > 0 && (!rel_emb || !drel_emb)) return fail(MMT_E_INVALID, "R > 0 but rel_emb / drel_emb is NULL");
-  const bool dense = att_mask != nullptr || rel_ids != nullptr;
-  if (!dense && desc->mask.global_index && desc->mask.n_global > 0)
-    return fail(MMT_E_UNSUPPORTED, "a listed global-token set has no structured kernel: materialise att_mask with mmt_side_inputs(materialize_pattern = 1) and pass it (dense operator)");
-  if (!dense) if (int rc = check_packed(desc)) return rc;
-  const int pack = (dense || !(desc->flags & MMT_FLAG_EXAMPLE_IDS)) ? mmt::kPackNone
-                   : ((desc->flags & MMT_FLAG_EXAMPLE_STARTS) ? mmt::kPackOrigin : mmt::kPackIds);
-  const Plan pl = make_plan(desc, dense);
+  Call c;
+  if (int rc = prepare(desc, att_mask, rel_ids,
+                       (!q || !k || !v || !out || !dout || !lse || !dq || !dk || !dv) ? "q, k, v, out, dout, lse, dq, dk, dv must not be NULL" : nullptr,
+                       (!rel_emb || !drel_emb) ? "R > 0 but rel_emb / drel_emb is NULL" : nullptr, c)) return rc;
+  const Plan& pl = c.plan; const Route& r = c.route;
   if (!workspace || workspace_bytes < pl.bwd_ws)
     return fail(MMT_E_WORKSPACE, "workspace too small: need %zu bytes, got %zu", pl.bwd_ws, workspace_bytes);
 
-  mmt::FwdParams f;
-  fill_common(f, desc);
   mmt::BwdParams p;
-  std::memset(&p, 0, sizeof(p));
+  fill_common(p, desc, r);
   p.q = q; p.k = k; p.v = v; p.emb = rel_emb; p.bias = rel_bias; p.out = out; p.dout = dout; p.lse = lse;
-  p.att_mask = att_mask; p.rel_ids = rel_ids; p.valid_len = f.valid_len;
+  p.att_mask = att_mask; p.rel_ids = desc->R == 0 ? nullptr : rel_ids;
   p.dq = dq; p.dk = dk; p.dv = dv; p.drel_emb = drel_emb; p.drel_bias = rel_bias ? drel_bias : nullptr;
-  p.B = f.B; p.S = f.S; p.N = f.N; p.R = f.R; p.D = f.D; p.Rp = desc->R <= 32 ? 32 : (desc->R <= 64 ? 64 : 128);
-  for (int i = 0; i < 3; ++i) { p.qs[i] = f.qs[i]; p.ks[i] = f.ks[i]; p.vs[i] = f.vs[i]; p.os[i] = f.os[i]; }
-  p.sscale = f.sscale; p.tscale = f.tscale; p.mask_add = f.mask_add;
   p.gscale = desc->scale;
   p.rel_gscale = (desc->flags & MMT_FLAG_SCALE_BEFORE_ADD) ? 1.f : desc->scale;
   p.drel_accum = (desc->flags & MMT_FLAG_ACCUM_REL_GRADS) ? 1 : 0;
-  p.pat = f.pat;
-  p.grid = f.grid;
-  p.ids_go = f.ids_go;
-  if (desc->R == 0) { p.pat.id_mode = 0; p.rel_ids = nullptr; }
-  p.perm_1d = (!dense && p.pat.id_mode == MMT_IDS_1D && desc->R >= 2 * p.pat.m + 1) ? 1 : 0;
-  p.drop_thresh = f.drop_thresh; p.seed_lo = f.seed_lo; p.seed_hi = f.seed_hi; p.inv_keep = f.inv_keep; p.epoch = f.epoch;
-  if (desc->dtype == MMT_BF16) {
-    if (const int w2 = lean2d_width(p.pat, p.grid, desc->R, desc->D, dense, pack)) {      // lean 2-D path: the kernels run at the narrowed table width
-      p.lean2d = 1;
-      p.Rp = w2;
-    }
-  }
+  const bool lean = r.family == kLean;
+  p.lean2d = (lean && r.lean_rp) ? 1 : 0;            // lean 2-D path: the kernels run at the narrowed table width
+  p.Rp = p.lean2d ? r.lean_rp : r.Rp;
   float* ws = reinterpret_cast<float*>(workspace);
   p.delta = ws + pl.off_delta; p.relfar = ws + pl.off_relfar; p.drel = ws + pl.off_drel; p.part_dq = ws + pl.off_pdq;
   p.part_dtab = ws + pl.off_pdtab; p.part_dkv = ws + pl.off_pdkv; p.part_red = ws + pl.off_red;
-  p.n_band_blocks = desc->B * desc->N * ((desc->S + 127) / 128);
   p.n_split = pl.n_split;
   if (pl.split_rows) {
     p.skip_global = 1; p.n_gblk = pl.n_rowblk; p.n_chunks = pl.n_chunks; p.chunk_tiles = kChunkTiles;
@@ -456,29 +505,22 @@ int mmt_attn_bwd(const mmt_attn_desc* desc, const void* q, const void* k, const 
   }
   p.dq_plane_major = (desc->tuning & MMT_TUNE_BWD_DQ_PLANE_MAJOR) ? 1 : 0;
   p.ho_per_wave = (desc->tuning & MMT_TUNE_BWD_HO_PER_WAVE) ? 1 : 0;
-  // peeled global keys need clipped relative ids only: every peeled key lies beyond the radius, hence beyond max_dist
-  p.peel_gkeys = (!dense && pl.split_rows && p.pat.ng <= 8 && (p.pat.id_mode == 0 || (p.perm_1d && p.pat.radius >= p.pat.m))) ? 3 : 0;
-  if (!dense && pl.split_rows && p.pat.ng <= 8 && p.lean2d) p.peel_gkeys = 1;      // 2-D ids: the dQ pass's peeled step looks its columns up (the recomputing dK/dV pass keeps its tile visit)
-  if (p.grid.ga > 0 || p.D != 64 || pack) p.peel_gkeys = 0;             // an image grid, head size 128, packed examples: the general kernels, no peeled steps
+  // peeled global keys (<= 8, no extended feature) need clipped relative ids only: every peeled key lies beyond the radius, hence
+  // beyond max_dist.  Lean 2-D ids: the dQ pass's peeled step looks its columns up (the recomputing dK/dV pass keeps its tile visit)
+  if (!c.dense && pl.split_rows && p.pat.ng <= 8 && !r.extended)
+    p.peel_gkeys = p.lean2d ? 1 : ((p.pat.id_mode == 0 || (p.perm_1d && p.pat.radius >= p.pat.m)) ? 3 : 0);
   if (desc->tuning & MMT_TUNE_BWD_NO_PEEL_DQ) p.peel_gkeys &= ~1;       // bit 0: dQ pass, bit 1: dK/dV pass
   if (desc->tuning & MMT_TUNE_BWD_NO_PEEL_DKV) p.peel_gkeys &= ~2;
   p.dkv_slots = p.n_chunks;
-  {   // P / dS hand-over: the dK/dV pass reads what the dQ pass computed (needs the peeled kind of global tokens, if any)
-    const bool on = !(desc->tuning & MMT_TUNE_BWD_NO_HANDOVER);
-    const bool lean = desc->dtype == MMT_BF16 && !dense && !pack && p.grid.ga == 0 && p.D == 64 && (p.pat.id_mode == 0 || (p.perm_1d && p.Rp <= 64) || p.lean2d);
-    if (on && lean && pl.ho_slots > 0 && (p.pat.ng == 0 || !pl.split_rows || (p.peel_gkeys & 1))) {
-      p.ho = reinterpret_cast<unsigned char*>(ws + pl.off_ho);
-      p.ho_slots = pl.ho_slots;
-      if (pl.split_rows) p.dkv_slots = p.n_chunks + 1;
-    }
+  // P / dS hand-over: the dK/dV pass reads what the dQ pass computed (needs the peeled kind of global tokens, if any)
+  if (!(desc->tuning & MMT_TUNE_BWD_NO_HANDOVER) && lean && pl.ho_slots > 0 && (p.pat.ng == 0 || !pl.split_rows || (p.peel_gkeys & 1))) {
+    p.ho = reinterpret_cast<unsigned char*>(ws + pl.off_ho);
+    p.ho_slots = pl.ho_slots;
+    if (pl.split_rows) p.dkv_slots = p.n_chunks + 1;
   }
-#ifdef MMT_STAMP
-  if (const char* v = std::getenv("MMT_DBG_PTR")) p.dbg = reinterpret_cast<long long*>(std::strtoull(v, nullptr, 0));
-  if (const char* v = std::getenv("MMT_DBG_MODE")) p.dbg_mode = std::atoi(v);
-#endif
-  hipError_t e = mmt::launch_attn_bwd(p, dense ? mmt::kDense : mmt::kBand, desc->dtype == MMT_BF16, pack, st);
-  if (e != hipSuccess) return fail(MMT_E_LAUNCH, "backward launch: %s", hipGetErrorString(e));
-  return MMT_OK;
+  read_stamp_env(p);
+  return launched(lean ? mmt::launch_attn_bwd_band_bf16(p, st)
+                       : kGeneralBwd[r.tu](p, c.dense ? mmt::kDense : mmt::kBand, desc->dtype == MMT_BF16, r.pack, st), "backward");
 }
 
 int mmt_side_inputs(const mmt_mask_desc* mask, int32_t B, int32_t S,

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 import __graft_entry__  # noqa: F401
-from tests.test_gpu_encoder import tiny_experiment
+from tests._parity import tiny_experiment
 
 
 def _models():

@@ -1,66 +1,34 @@
 """Backward parity: HIP kernels (through the C ABI + autograd) vs the analytic CPU oracle.
 
-Tolerances: fp32 path 2e-3 absolute (gradients are O(1..10); observed ~1e-5); bf16 path is
-compared against the fp64 oracle run on bf16-rounded inputs, relative to each gradient's
-max magnitude (3e-2: bf16 outputs + bf16 P/dS operands)."""
+Tolerances: the gradient bars of tests/_cases.py (F32_GRAD_TOL, BF16_GRAD_TOL: fp32 2e-3 absolute; bf16 against the
+fp64 oracle run on bf16-rounded inputs, 3e-2 relative to each gradient's max magnitude), the output bars for `out`."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import attention as oa
-from tests._cases import attention_inputs, bf16_round, dense_side_inputs
+from tests._cases import (BF16_GRAD_TOL, DTYPES, F32_TOL, attention_inputs, bf16_round, dense_side_inputs, grad_error, grad_tol,
+                          out_tol, parity_inputs)
+from tests._parity import GRAD_NAMES, check_against, device_call, make_pattern, oracle_call, to_dev
 
 pytestmark = pytest.mark.gpu
 
 
 def run_bwd(B, S, N, R, dtype, *, dense, valid=None, radius=1 << 30, g0=0, ng=0, id_mode=1, m=3,
             P=0, r=0, seed=0, scale_before_add=False, use_bias=True, tuning=0):
-  import mmt_amd
-  q, k, v, emb, bias = attention_inputs(B, S, N, R, seed)
-  rng = np.random.default_rng(seed + 100)
-  dout = rng.standard_normal(q.shape).astype(np.float32)
-  if not use_bias:
-    bias = None
-  if dtype == torch.bfloat16:
-    q, k, v, dout = (bf16_round(x) for x in (q, k, v, dout))
-    emb = None if emb is None else bf16_round(emb)
-    bias = None if bias is None else bf16_round(bias)
+  """Autograd path against the oracle: output and every gradient; returns the worst gradient error."""
+  arrays = parity_inputs(B, S, N, R, dtype, seed, use_bias=use_bias)
   if R == 0:
     id_mode = 0
   mask, ids = dense_side_inputs(B, S, valid, radius, g0, ng, id_mode, m, P, r)
-  ref = oa.relative_attention_bwd(dout, q, k, v, emb, bias, mask, ids,
-                                  scale_after_add=not scale_before_add)
-  dev = lambda x, dt=dtype: None if x is None else torch.from_numpy(x).cuda().to(dt).contiguous()
-  tq, tk, tv, te, tb = (None if x is None else dev(x).requires_grad_(True) for x in (q, k, v, emb, bias))
-  kw = dict(scale_before_add=scale_before_add)
   if dense:
-    out = mmt_amd.relative_attention(tq, tk, tv, te, tb, att_mask=dev(mask, torch.int32),
-                                     relative_att_ids=dev(ids, torch.int32), **kw)
+    kw = dict(att_mask=to_dev(mask, torch.int32), relative_att_ids=to_dev(ids, torch.int32))
   else:
-    pat = mmt_amd.AttentionPattern(local_radius=radius, global_start=g0, n_global=ng, id_mode=id_mode,
-                                   max_dist=m, patches_per_row=P, core_layers=r)
     vl = None if valid is None else torch.tensor(valid, dtype=torch.int32, device='cuda:0')
-    out = mmt_amd.relative_attention(tq, tk, tv, te, tb, pattern=pat, valid_len=vl, tuning=tuning, **kw)
-  out.backward(dev(dout))
-  torch.cuda.synchronize()
-  worst = 0.0
-  for name, t in (('dq', tq), ('dk', tk), ('dv', tv), ('drel_emb', te), ('drel_bias', tb)):
-    if t is None:
-      continue
-    got = t.grad.float().cpu().numpy()
-    want = ref[name]
-    assert np.isfinite(got).all(), name
-    if dtype == torch.float32:
-      err = np.abs(got - want).max()
-      assert err < 2e-3, f'{name}: max abs err {err}'
-    else:
-      err = np.abs(got - want).max() / max(1.0, np.abs(want).max())
-      assert err < 3e-2, f'{name}: max err relative to max |grad| = {err}'
-    worst = max(worst, err)
-  return worst
-
-
-DTYPES = [torch.float32, torch.bfloat16]
+    kw = dict(pattern=make_pattern(radius=radius, g0=g0, ng=ng, id_mode=id_mode, m=m, P=P, r=r), valid_len=vl, tuning=tuning)
+  got = device_call(arrays, dtype, scale_before_add=scale_before_add, **kw)
+  errs = check_against(got, oracle_call(arrays, mask, ids, scale_before_add=scale_before_add), dtype)
+  return max(errs[n] for n in errs if n != 'out')
 
 
 @pytest.mark.parametrize('dtype', DTYPES, ids=['f32', 'bf16'])
@@ -162,7 +130,7 @@ def test_config3_shape_backward_against_oracle():
   of the lean backward -- band items, the global-row / global-key chunk partials and their combines riding in
   the next launches, the per-workgroup dE partials -- against the dense fp64 oracle."""
   worst = run_bwd(1, 4096, 1, 32, torch.bfloat16, dense=False, radius=64, g0=3971, ng=8, m=12, seed=5)
-  assert worst < 3e-2
+  assert worst < BF16_GRAD_TOL
 
 
 # ---- the three forms of the dK/dV pass on the lean bf16 path ----
@@ -207,7 +175,7 @@ def test_dkv_pass_forms_agree_under_dropout():
     res[form] = [g.float().cpu().numpy() for g in mmt_amd.relative_attention_backward(dout, q, k, v, emb, bias, out, lse, tuning=tuning, **kw)]
   for form in ('handover-wave', 'handover-window'):
     for a, b in zip(res['recompute'], res[form]):
-      assert np.abs(a - b).max() <= 3e-2 * max(1.0, np.abs(a).max()), form
+      assert np.abs(a - b).max() <= BF16_GRAD_TOL * max(1.0, np.abs(a).max()), form
   for a, b in zip(res['handover-wave'], res['handover-window']):      # same arithmetic, different staging
     assert np.abs(a - b).max() <= 1e-6 * max(1.0, np.abs(a).max())
 
@@ -240,12 +208,12 @@ def test_dropout_mask_matches_oracle_forward_and_backward(path):
     pat = mmt_amd.AttentionPattern(local_radius=radius, global_start=g0, n_global=ng, id_mode=1, max_dist=m)
     out = mmt_amd.relative_attention(tq, tk, tv, te, tb, pattern=pat, **kw)
   out.backward(dev(dout))
-  tol = 3e-2 if dtype == torch.bfloat16 else 2e-3
+  tol = grad_tol(dtype)
   err = np.abs(out.detach().float().cpu().numpy() - ref_o).max()
   assert err < tol, f'out: {err}'
-  for name, t in (('dq', tq), ('dk', tk), ('dv', tv), ('drel_emb', te), ('drel_bias', tb)):
+  for name, t in zip(GRAD_NAMES, (tq, tk, tv, te, tb)):
     got, want = t.grad.float().cpu().numpy(), ref[name]
-    err = np.abs(got - want).max() / (max(1.0, np.abs(want).max()) if dtype == torch.bfloat16 else 1.0)
+    err = grad_error(got, want, dtype)
     assert err < tol, f'{name}: {err}'
 
 
@@ -270,11 +238,11 @@ def test_2d_ids_long_sequence_forward_backward_against_oracle(dtype):
                                  patches_per_row=P, core_layers=r)
   out = mmt_amd.relative_attention(tq, tk, tv, te, tb, pattern=pat)
   out.backward(dev(dout))
-  tol_o, tol_g = (2e-2, 3e-2) if dtype == torch.bfloat16 else (1e-3, 2e-3)
+  tol_o, tol_g = out_tol(dtype), grad_tol(dtype)
   assert np.abs(out.detach().float().cpu().numpy() - ref_o).max() < tol_o
-  for name, t in (('dq', tq), ('dk', tk), ('dv', tv), ('drel_emb', te), ('drel_bias', tb)):
+  for name, t in zip(GRAD_NAMES, (tq, tk, tv, te, tb)):
     got, want = t.grad.float().cpu().numpy(), ref[name]
-    err = np.abs(got - want).max() / (max(1.0, np.abs(want).max()) if dtype == torch.bfloat16 else 1.0)
+    err = grad_error(got, want, dtype)
     assert err < tol_g, f'{name}: {err}'
 
 
@@ -306,11 +274,11 @@ def test_listed_global_tokens_forward_backward_and_materialised_mask(dtype):
   tq, tk, tv, te, tb = (dev(x).requires_grad_(True) for x in (q, k, v, emb, bias))
   out = mmt_amd.relative_attention(tq, tk, tv, te, tb, pattern=pat, valid_len=vl)
   out.backward(dev(dout))
-  tol_o, tol_g = (2e-2, 3e-2) if dtype == torch.bfloat16 else (1e-3, 2e-3)
+  tol_o, tol_g = out_tol(dtype), grad_tol(dtype)
   assert np.abs(out.detach().float().cpu().numpy() - ref_o).max() < tol_o
-  for name, t in (('dq', tq), ('dk', tk), ('dv', tv), ('drel_emb', te), ('drel_bias', tb)):
+  for name, t in zip(GRAD_NAMES, (tq, tk, tv, te, tb)):
     got_g, want = t.grad.float().cpu().numpy(), ref[name]
-    err = np.abs(got_g - want).max() / (max(1.0, np.abs(want).max()) if dtype == torch.bfloat16 else 1.0)
+    err = grad_error(got_g, want, dtype)
     assert err < tol_g, f'{name}: {err}'
   # a contiguous run, listed: the range form's kernels, bit for bit
   run = mmt_amd.AttentionPattern(local_radius=16, id_mode=1, max_dist=m, global_index=(152, 150, 151, 153))
@@ -348,7 +316,7 @@ def test_listed_global_mask_cache_is_not_keyed_on_the_address():
     o, _ = mmt_amd.relative_attention_forward(tq, tk, tv, te, tb, pattern=pat, valid_len=vl)
     mask, ids = dense_side_inputs(B, S, valid, 16, 0, 0, 1, m, gidx=gidx)
     ref, _ = oa.relative_attention_fwd(q, k, v, emb, bias, mask, ids)
-    assert np.abs(o.cpu().numpy() - ref).max() < 1e-3, valid
+    assert np.abs(o.cpu().numpy() - ref).max() < F32_TOL, valid
     del vl, o
     gc.collect()
     assert 'last' not in ops._DENSE_CACHE          # the entry went with its valid_len tensor

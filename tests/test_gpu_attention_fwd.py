@@ -1,64 +1,34 @@
 """Forward parity: HIP kernels (through the C ABI) vs the dense CPU oracle.
 
-Tolerances: fp32 path 1e-3 absolute on O(1) outputs (north_star; observed ~1e-5);
-bf16 path is compared against the oracle run on the bf16-rounded inputs with 2e-2
-(bf16 output rounding 2^-9 relative plus bf16 P in the PV product).
+Tolerances: the output bars of tests/_cases.py (F32_TOL, BF16_TOL: fp32 1e-3 absolute on O(1) outputs, bf16 2e-2
+against the oracle run on the bf16-rounded inputs), for the output and for lse.
 """
 import numpy as np
 import pytest
 import torch
 
 from oracle import attention as oa
-from tests._cases import attention_inputs, bf16_round, dense_side_inputs
+from tests._cases import BF16_TOL, DTYPES, F32_TOL, attention_inputs, bf16_round, dense_side_inputs, parity_inputs
+from tests._parity import check_against, device_call, make_pattern, oracle_call, to_dev
 
 pytestmark = pytest.mark.gpu
-
-F32_TOL = 1e-3
-BF16_TOL = 2e-2
-
-
-def _to_dev(x, dtype):
-  return None if x is None else torch.from_numpy(x).to('cuda:0').to(dtype).contiguous()
 
 
 def run_case(B, S, N, R, dtype, *, dense, valid=None, radius=1 << 30, g0=0, ng=0, id_mode=1, m=3,
              P=0, r=0, seed=0, scale_before_add=False, use_bias=True, tuning=0):
-  import mmt_amd
-  q, k, v, emb, bias = attention_inputs(B, S, N, R, seed)
-  if not use_bias:
-    bias = None
-  if dtype == torch.bfloat16:
-    q, k, v = bf16_round(q), bf16_round(k), bf16_round(v)
-    emb = None if emb is None else bf16_round(emb)
-    bias = None if bias is None else bf16_round(bias)
+  """Forward API against the oracle: output and lse."""
+  arrays = parity_inputs(B, S, N, R, dtype, seed, use_bias=use_bias)
   if R == 0:
     id_mode = 0
   mask, ids = dense_side_inputs(B, S, valid, radius, g0, ng, id_mode, m, P, r)
-  ref, ref_lse = oa.relative_attention_fwd(q, k, v, emb, bias, mask, ids,
-                                           scale_after_add=not scale_before_add)
-  tq, tk, tv, te, tb = (_to_dev(x, dtype) for x in (q, k, v, emb, bias))
-  kw = dict(scale_before_add=scale_before_add)
   if dense:
-    out, lse = mmt_amd.relative_attention_forward(
-        tq, tk, tv, te, tb, att_mask=_to_dev(mask, torch.int32),
-        relative_att_ids=_to_dev(ids, torch.int32), **kw)
+    kw = dict(att_mask=to_dev(mask, torch.int32), relative_att_ids=to_dev(ids, torch.int32))
   else:
-    pat = mmt_amd.AttentionPattern(local_radius=radius, global_start=g0, n_global=ng, id_mode=id_mode,
-                                   max_dist=m, patches_per_row=P, core_layers=r)
     vl = None if valid is None else torch.tensor(valid, dtype=torch.int32, device='cuda:0')
-    out, lse = mmt_amd.relative_attention_forward(tq, tk, tv, te, tb, pattern=pat, valid_len=vl, tuning=tuning, **kw)
-  torch.cuda.synchronize()
-  tol = F32_TOL if dtype == torch.float32 else BF16_TOL
-  got = out.float().cpu().numpy()
-  err = np.abs(got - ref).max()
-  lerr = np.abs(lse.cpu().numpy() - ref_lse).max()
-  assert np.isfinite(got).all()
-  assert err < tol, f'max |out - oracle| = {err}'
-  assert lerr < tol, f'max |lse - oracle| = {lerr}'
-  return err
-
-
-DTYPES = [torch.float32, torch.bfloat16]
+    kw = dict(pattern=make_pattern(radius=radius, g0=g0, ng=ng, id_mode=id_mode, m=m, P=P, r=r), valid_len=vl, tuning=tuning)
+  got = device_call(arrays, dtype, backward=False, scale_before_add=scale_before_add, **kw)
+  assert 'lse' in got
+  check_against(got, oracle_call(arrays, mask, ids, scale_before_add=scale_before_add, backward=False), dtype)
 
 
 @pytest.mark.parametrize('dtype', DTYPES, ids=['f32', 'bf16'])

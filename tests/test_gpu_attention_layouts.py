@@ -2,8 +2,8 @@
 
 Every case calls the kernels twice, on contiguous tensors and on views that live in NaN-poisoned storages
 (tests/_cases.py `strided_view`), and asserts
-  (a) the strided result within the standing tolerances of the dense fp64 oracle (output and lse: fp32 1e-3, bf16 2e-2;
-      gradients: fp32 2e-3 absolute, bf16 3e-2 of max |grad| -- the values of the neighbouring files), and
+  (a) the strided result within the standing tolerances of the dense fp64 oracle (output and lse, gradients: the bars
+      of tests/_cases.py, through tests/_parity.py `check_against`), and
   (b) the strided result BIT FOR BIT equal to the contiguous call on the same route: addresses do not enter the
       arithmetic, and no route's instruction order depends on the layout.
 Gradient storages are pre-filled with the poison pattern and must hold it outside the views afterwards.
@@ -20,16 +20,12 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import attention as oa
-from tests._cases import (LAYOUTS, assert_gaps_untouched, attention_inputs, bf16_round, dense_side_inputs, strided_view,
-                          _int_view)
-from tests.test_gpu_image_grid import grid_side_inputs
-from tests.test_gpu_packed import packed_side_inputs
+from tests._cases import (BF16_GRAD_TOL, BF16_TOL, F32_GRAD_TOL, LAYOUTS, assert_gaps_untouched, dense_side_inputs,
+                          grad_error, parity_inputs, strided_view, _int_view)
+from tests._parity import GRAD_NAMES, check_against, oracle_call, to_dev
 
 pytestmark = pytest.mark.gpu
 
-F32_TOL = 1e-3
-BF16_TOL = 2e-2
 DT = {'f32': torch.float32, 'bf16': torch.bfloat16}
 DROP_P, DROP_SEED = 0.1, 0x5EED_0123_4567
 
@@ -64,34 +60,26 @@ class Problem:
     c = self.cfg = CASES[case]
     self.dtype = DT[dt]
     B, S, N, D, R = c['B'], c['S'], c['N'], c['D'], c['R']
-    q, k, v, emb, bias = attention_inputs(B, S, N, R, seed=17, D=D)
-    dout = np.random.default_rng(117).standard_normal(q.shape).astype(np.float32)
+    q, k, v, emb, bias, dout = parity_inputs(B, S, N, R, self.dtype, seed=17, D=D)
     if broadcast == 'broadcast_heads':
       k, v = (np.broadcast_to(x[:, :, :1], x.shape).copy() for x in (k, v))
     if broadcast == 'broadcast_batch':
       k, v = (np.broadcast_to(x[:1], x.shape).copy() for x in (k, v))
-    if self.dtype == torch.bfloat16:
-      q, k, v, emb, bias, dout = (bf16_round(x) for x in (q, k, v, emb, bias, dout))
     self.np = dict(q=q, k=k, v=v, emb=emb, bias=bias, dout=dout)
     kind, m = c['kind'], c['m']
-    if kind == 'pattern':
-      mask, ids = dense_side_inputs(B, S, c.get('valid'), c['radius'], c['g0'], c['ng'], c['id_mode'], m, c.get('P', 0), c.get('r', 0))
-    elif kind == 'dense':
-      mask, ids = dense_side_inputs(B, S, None, 1 << 30, 0, 0, c['id_mode'], m)
-    elif kind == 'packed':
+    if kind == 'packed':
       self.ids = mmt_amd.example_ids_from_lengths(c['lengths'], S).numpy()
-      mask, ids = packed_side_inputs(self.ids, c['radius'], c['g0'], c['ng'], c['id_mode'], m)
-    else:
-      mask, ids = grid_side_inputs(B, S, None, c['radius'], c['g0'], c['ng'], c['id_mode'], m, c['P'], 0, c['a'], c['g'])
+    mask, ids = dense_side_inputs(B, S, c.get('valid'), c.get('radius', 1 << 30), c.get('g0', 0), c.get('ng', 0), c['id_mode'],
+                                  m, c.get('P', 0), c.get('r', 0), a=c.get('a', 0), g=c.get('g', 2),
+                                  example_ids=self.ids if kind == 'packed' else None)
     self.mask, self.rel_ids = mask, ids
     self.dropout = dropout
     self._ref = None
-    dev = lambda x, t=self.dtype: torch.from_numpy(x).cuda().to(t).contiguous()
-    self.t = {n: dev(x) for n, x in self.np.items()}
+    self.t = {n: to_dev(x, self.dtype) for n, x in self.np.items()}
     pat_kw = dict(local_radius=c.get('radius', 1 << 30), global_start=c.get('g0', 0), n_global=c.get('ng', 0),
                   id_mode=c['id_mode'], max_dist=m, patches_per_row=c.get('P', 0), core_layers=c.get('r', 0))
     if kind == 'dense':
-      self.kw = dict(att_mask=dev(mask, torch.int32), relative_att_ids=dev(ids, torch.int32))
+      self.kw = dict(att_mask=to_dev(mask, torch.int32), relative_att_ids=to_dev(ids, torch.int32))
     elif kind == 'packed':
       self.kw = dict(pattern=mmt_amd.AttentionPattern(**pat_kw), example_ids=torch.from_numpy(self.ids).cuda())
     elif kind == 'grid':
@@ -107,40 +95,18 @@ class Problem:
   def ref(self):
     """The dense fp64 oracle: computed once per problem, shared by every test on it, never written."""
     if self._ref is None:
-      from mmt_amd import step_scalars
-      n, c = self.np, self.cfg
-      okw = {}
-      if self.dropout:
-        assert step_scalars.epoch_ptr(torch.device('cuda:0')) is None
-        seed = (DROP_SEED + step_scalars.host_epoch(torch.device('cuda:0'))) & ((1 << 64) - 1)
-        keep, keep_prob = oa.dropout_keep_mask(c['B'], c['N'], c['S'], self.dropout, seed)
-        okw = dict(keep_mask=keep, keep_prob=keep_prob)
-      args = (n['q'], n['k'], n['v'], n['emb'], n['bias'], self.mask, self.rel_ids)
-      out, lse = oa.relative_attention_fwd(*args, **okw)
-      self._ref = dict(oa.relative_attention_bwd(n['dout'], *args, **okw), out=out, lse=lse)
+      self._ref = oracle_call(tuple(self.np.values()), self.mask, self.rel_ids,
+                              dropout=(self.dropout, DROP_SEED) if self.dropout else None)
     return self._ref
 
   # ---- assertion (a) ----
   def check_forward(self, out, lse, what=''):
-    tol = F32_TOL if self.dtype == torch.float32 else BF16_TOL
-    got = out.float().cpu().numpy()
-    assert np.isfinite(got).all(), f'{what}: non-finite output'
-    err, lerr = np.abs(got - self.ref['out']).max(), np.abs(lse.cpu().numpy() - self.ref['lse']).max()
-    print(f'{what}: max |out - oracle| = {err:.3e}, max |lse - oracle| = {lerr:.3e}')
-    assert err < tol and lerr < tol, f'{what}: max |out - oracle| = {err}, max |lse - oracle| = {lerr}'
+    check_against({'out': out, 'lse': lse}, {n: self.ref[n] for n in ('out', 'lse')}, self.dtype, what)
 
   def check_grads(self, grads, what='', only=None):
-    for name, g in zip(('dq', 'dk', 'dv', 'drel_emb', 'drel_bias'), grads):
-      if only is not None and name not in only:
-        continue
-      got, want = g.float().cpu().numpy(), self.ref[name]
-      assert np.isfinite(got).all(), f'{what}: non-finite {name}'
-      if self.dtype == torch.float32:
-        err, tol = np.abs(got - want).max(), 2e-3
-      else:
-        err, tol = np.abs(got - want).max() / max(1.0, np.abs(want).max()), 3e-2
-      print(f'{what}: {name} err = {err:.3e}')
-      assert err < tol, f'{what}: {name} err = {err}'
+    names = GRAD_NAMES if only is None else only
+    assert len(grads) == len(names)
+    check_against(dict(zip(names, grads)), {n: self.ref[n] for n in names}, self.dtype, what)
 
 
 @functools.lru_cache(maxsize=None)
@@ -229,7 +195,7 @@ def run_backward(case, dt, tuning, layout, dropout=0.0):
     assert got.data_ptr() == g.data_ptr() and got.stride() == g.stride()
   p.check_grads(base, what + ' (contiguous)')
   p.check_grads(grads, what)
-  for name, got, want in zip(('dq', 'dk', 'dv', 'drel_emb', 'drel_bias'), grads, base):
+  for name, got, want in zip(GRAD_NAMES, grads, base):
     assert_same_bits(got, want, f'{what} {name}')
   for view, storage in gviews + views:
     assert_gaps_untouched(storage, view)
@@ -329,7 +295,7 @@ def test_strided_out_and_dout_through_the_c_entry_points(case, dt, tuning, layou
   assert_same_bits(out, base_out, what + ' out')
   assert_same_bits(lse, base_lse, what + ' lse')
   p.check_grads(grads, what)
-  for name, got, want in zip(('dq', 'dk', 'dv', 'drel_emb', 'drel_bias'), grads, base):
+  for name, got, want in zip(GRAD_NAMES, grads, base):
     assert_same_bits(got, want, f'{what} {name}')
   for view, storage in gviews + views + [(out, out_storage), (dout, dout_storage)]:
     assert_gaps_untouched(storage, view)
@@ -363,7 +329,7 @@ def test_forward_on_broadcast_k_and_v(case, dt, tuning, layout):
 def test_autograd_sums_the_gradient_of_expanded_k_and_v(case, dt, axis):
   """`relative_attention` on `k.expand(...)`: the gradient that reaches the un-expanded leaf is the oracle's dk summed
   over the broadcast axis.  Tolerance: each of the T summed terms carries the gradient bound of the other tests (fp32
-  2e-3 absolute; bf16 3e-2 of max |grad|, the per-term maximum), so T times that."""
+  F32_GRAD_TOL absolute; bf16 BF16_GRAD_TOL of max |grad|, the per-term maximum), so T times that."""
   import mmt_amd
   lay = 'broadcast_heads' if axis == 2 else 'broadcast_batch'
   p = problem(case, dt, 0.0, lay)
@@ -380,7 +346,7 @@ def test_autograd_sums_the_gradient_of_expanded_k_and_v(case, dt, axis):
     want = p.ref[name].sum(axis=axis, keepdims=True)
     got = leaf.grad.float().cpu().numpy()
     assert got.shape == want.shape and np.isfinite(got).all()
-    tol = T * (2e-3 if dt == 'f32' else 3e-2 * max(1.0, np.abs(p.ref[name]).max()))
+    tol = T * (F32_GRAD_TOL if dt == 'f32' else BF16_GRAD_TOL * max(1.0, np.abs(p.ref[name]).max()))
     err = np.abs(got - want).max()
     print(f'{case}-{dt}-{lay}: {name} summed over {T} terms, max abs err {err:.3e} (tolerance {tol:.3e})')
     assert err < tol, f'{name}: {err}'
@@ -486,7 +452,7 @@ def test_row_stride_near_the_limit(operand):
       torch.cuda.synchronize()
       what = f'{operand} at the stride limit, backward {tuning}'
       p.check_grads(grads, what)
-      for name, got, want in zip(('dq', 'dk', 'dv', 'drel_emb', 'drel_bias'), grads, base):
+      for name, got, want in zip(GRAD_NAMES, grads, base):
         assert_same_bits(got, want, f'{what} {name}')
       assert_gaps_untouched(gstorage, gview)
     assert_gaps_untouched(storage, view)
@@ -551,11 +517,11 @@ def test_batch_and_head_strides_beyond_2_31_elements(case, which):
       assert err < tol and lerr < tol, (err, lerr)
       for name, g in zip(('dq', 'dk', 'dv'), grads):
         want = p.ref[name][:1]
-        e = np.abs(g.float().cpu().numpy() - want).max() / max(1.0, np.abs(want).max())
-        assert e < 3e-2, f'{name}: {e}'
+        e = grad_error(g.float().cpu().numpy(), want, torch.bfloat16)
+        assert e < BF16_GRAD_TOL, f'{name}: {e}'
     assert_same_bits(out, base_out, what + ' out')
     assert_same_bits(lse, base_lse, what + ' lse')
-    for name, got, want in zip(('dq', 'dk', 'dv', 'drel_emb', 'drel_bias'), grads, base):
+    for name, got, want in zip(GRAD_NAMES, grads, base):
       assert_same_bits(got, want, f'{what} {name}')
     for s, views in zip(storages, (ins, gouts)):
       assert_gaps_untouched(s, views)

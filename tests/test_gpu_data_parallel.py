@@ -11,7 +11,7 @@ import torch
 import torch.multiprocessing as mp
 
 import __graft_entry__  # noqa: F401
-from tests.test_gpu_encoder import tiny_experiment
+from tests._parity import tiny_experiment
 
 pytestmark = pytest.mark.gpu
 

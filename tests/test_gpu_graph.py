@@ -92,7 +92,7 @@ def test_trainer_loop_graphed_equals_eager(tmp_path, monkeypatch, micro):
   """`train.run_experiment` (new batch every step, metrics updated inside the step, checkpoint at the end): the logs of
   the graphed loop equal the eager loop's, and both checkpoints carry the same step count and parameters -- also with
   the reference's micro-batch accumulation inside the recorded step (two micro-steps, the reducer armed for the last)."""
-  from tests.test_gpu_encoder import tiny_experiment
+  from tests._parity import tiny_experiment
   from mmt_amd import checkpoint, train
   logs, ckpts = {}, {}
   for mode in ('0', '1'):
@@ -222,7 +222,7 @@ def test_a_capture_that_fails_inside_backward_leaves_no_queued_work(monkeypatch)
 def test_classification_trainer_loop_graphed_equals_eager(tmp_path, monkeypatch):
   """The same comparison for `mmt/classification` (its own train_step surface: logits of one head, AUC / accuracy
   metrics updated inside the recorded step)."""
-  from tests.test_gpu_encoder import tiny_experiment
+  from tests._parity import tiny_experiment
   from mmt_amd import configs, train
   pre = tiny_experiment(S=256, radius=32, n_global=8)
   logs, params = {}, {}

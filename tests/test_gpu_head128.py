@@ -2,107 +2,45 @@
 the dense oracle (fp32 and bf16), the structured route against the dense operator under dropout, every kernel-selection
 switch, strided views of a fused qkv tensor, one config-3-shaped call and a train step of a tiny model.
 
-Tolerances as test_gpu_attention_fwd.py / test_gpu_attention_bwd.py / test_gpu_encoder.py."""
+Tolerances: the standing bars of tests/_cases.py; test_gpu_encoder.py's for the encoder."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import attention as oa
-from tests._cases import attention_inputs, bf16_round
-from tests.test_gpu_image_grid import grid_side_inputs
+from tests._cases import BF16_GRAD_TOL, BF16_TOL, DTYPES, dense_side_inputs, grad_error, grad_tol, out_tol, parity_inputs
+from tests._parity import (ACCUM_SEED, assert_structured_equals_dense_under_dropout, assert_train_step_matches_oracle,
+                           check_against, dense_inputs_cpu, device_call, make_pattern, oracle_call, tiny_experiment, to_dev,
+                           tuning_bits)
 
 pytestmark = pytest.mark.gpu
 
 D = 128
-F32_TOL = 1e-3
-BF16_TOL = 2e-2
-DTYPES = [torch.float32, torch.bfloat16]
-
-
-def _inputs(B, S, N, R, dtype, seed):
-  q, k, v, emb, bias = attention_inputs(B, S, N, R, seed, D=D)
-  dout = np.random.default_rng(seed + 100).standard_normal(q.shape).astype(np.float32)
-  if dtype == torch.bfloat16:
-    q, k, v, dout = (bf16_round(x) for x in (q, k, v, dout))
-    emb = None if emb is None else bf16_round(emb)
-    bias = None if bias is None else bf16_round(bias)
-  return q, k, v, emb, bias, dout
 
 
 def _pattern(radius, g0, ng, id_mode, m, P, r, a):
-  import mmt_amd
-  return mmt_amd.AttentionPattern(local_radius=radius, global_start=g0, n_global=ng, id_mode=id_mode, max_dist=m,
-                                  patches_per_row=P, core_layers=r, grid_radius=a, grid_start=2 if a else 0)
+  return make_pattern(radius=radius, g0=g0, ng=ng, id_mode=id_mode, m=m, P=P, r=r, a=a, g=2 if a else 0)
 
 
 def run(B, S, N, R, dtype, *, radius=1 << 30, g0=0, ng=0, id_mode=1, m=12, P=0, r=0, a=0, valid=None, seed=0,
-        backward=True, tuning=0, dense=False, no_bias=False, scale_before_add=False, accum=False, oracle=True):
-  """One D = 128 call (structured pattern, or the dense operator fed the oracle's [B,S,S] side inputs) against the
-  dense oracle.  Returns (out, grads) as numpy arrays for comparisons between calls."""
-  import mmt_amd
+        tuning=0, dense=False, no_bias=False, scale_before_add=False, accum=False, oracle=True):
+  """One D = 128 call (structured pattern, or the dense operator fed the oracle's [B,S,S] side inputs), forward and
+  backward through autograd, against the dense oracle.  Returns the device results for comparisons between calls."""
   if R == 0:
     id_mode = 0
-  q, k, v, emb, bias, dout = _inputs(B, S, N, R, dtype, seed)
-  if no_bias:
-    bias = None
-  mask, ids = grid_side_inputs(B, S, valid, radius, g0, ng, id_mode, m, P or 1, r, a)
-  dev = lambda x, dt=dtype: None if x is None else torch.from_numpy(x).cuda().to(dt).contiguous()
-  tq, tk, tv, te, tb = (None if x is None else dev(x).requires_grad_(True) for x in (q, k, v, emb, bias))
-  vl = None if valid is None else torch.tensor(valid, dtype=torch.int32, device='cuda:0')
+  arrays = parity_inputs(B, S, N, R, dtype, seed, D=D, use_bias=not no_bias)
+  mask, ids = dense_side_inputs(B, S, valid, radius, g0, ng, id_mode, m, P or 1, r, a=a)
   if dense:
-    kw = dict(att_mask=torch.from_numpy(mask).cuda(),
-              relative_att_ids=None if ids is None else torch.from_numpy(ids).cuda())
+    kw = dict(att_mask=to_dev(mask, torch.int32), relative_att_ids=to_dev(ids, torch.int32))
   else:
+    vl = None if valid is None else torch.tensor(valid, dtype=torch.int32, device='cuda:0')
     kw = dict(pattern=_pattern(radius, g0, ng, id_mode, m, P, r, a), valid_len=vl)
-  kw.update(tuning=tuning, scale_before_add=scale_before_add)
-  seed_grads = {}
-  if backward:
-    out = mmt_amd.relative_attention(tq, tk, tv, te, tb, **kw)
-    if accum and R:                              # MMT_FLAG_ACCUM_REL_GRADS: added onto what the buffers hold
-      seed_grads = {'drel_emb': np.full(emb.shape, 0.25, np.float32)}
-      if bias is not None:
-        seed_grads['drel_bias'] = np.full(bias.shape, -0.5, np.float32)
-      demb = torch.from_numpy(seed_grads['drel_emb']).cuda()
-      dbias = torch.from_numpy(seed_grads['drel_bias']).cuda() if bias is not None else None
-      lse = mmt_amd.relative_attention_forward(tq.detach(), tk.detach(), tv.detach(), te.detach(),
-                                               None if tb is None else tb.detach(), **kw)[1]
-      mmt_amd.relative_attention_backward(dev(dout), tq.detach(), tk.detach(), tv.detach(), te.detach(),
-                                          None if tb is None else tb.detach(), out.detach(), lse,
-                                          rel_grads_accum=(demb, dbias), **kw)
-    out.backward(dev(dout))
-  else:
-    out, _ = mmt_amd.relative_attention_forward(tq, tk, tv, te, tb, **kw)
-  torch.cuda.synchronize()
-  got_out = out.detach().float().cpu().numpy()
-  assert got_out.shape == (B, S, N, D)
-  grads = {}
-  if backward:
-    for name, t in (('dq', tq), ('dk', tk), ('dv', tv), ('drel_emb', te), ('drel_bias', tb)):
-      if t is not None:
-        grads[name] = t.grad.float().cpu().numpy()
-    if seed_grads:
-      grads['drel_emb'] = demb.cpu().numpy()
-      if dbias is not None:
-        grads['drel_bias'] = dbias.cpu().numpy()
-  if not oracle:
-    return got_out, grads
-  ref, _ = oa.relative_attention_fwd(q, k, v, emb, bias, mask, ids, scale_after_add=not scale_before_add)
-  tol = F32_TOL if dtype == torch.float32 else BF16_TOL
-  assert np.isfinite(got_out).all()
-  err = np.abs(got_out - ref).max()
-  assert err < tol, f'max |out - oracle| = {err}'
-  if backward:
-    want = oa.relative_attention_bwd(dout, q, k, v, emb, bias, mask, ids, scale_after_add=not scale_before_add)
-    for name, got in grads.items():
-      w = want[name] + seed_grads.get(name, 0.0)
-      assert np.isfinite(got).all(), name
-      if dtype == torch.float32:
-        e = np.abs(got - w).max()
-        assert e < 2e-3, f'{name}: max abs err {e}'
-      else:
-        e = np.abs(got - w).max() / max(1.0, np.abs(w).max())
-        assert e < 3e-2, f'{name}: max err relative to max |grad| = {e}'
-  return got_out, grads
+  got = device_call(arrays, dtype, accum=accum, tuning=tuning, scale_before_add=scale_before_add, **kw)
+  assert got['out'].shape == (B, S, N, D)
+  if oracle:
+    ref = oracle_call(arrays, mask, ids, scale_before_add=scale_before_add)
+    check_against(got, ref, dtype, seed_grads=ACCUM_SEED if accum else None)
+  return got
 
 
 CASES = [
@@ -147,62 +85,47 @@ def test_head128_flags_and_no_bias(dtype):
 def test_head128_structured_equals_dense_operator_under_dropout(dtype):
   import mmt_amd
   B, S, N, R = 2, 320, 2, 32
-  cfg = dict(radius=24, g0=146, ng=8, id_mode=1, m=12, P=12, r=0, a=0)
-  q, k, v, emb, bias, dout = _inputs(B, S, N, R, dtype, seed=7)
+  arrays = parity_inputs(B, S, N, R, dtype, seed=7, D=D)
   valid = torch.tensor([320, 250], dtype=torch.int32, device='cuda:0')
-  pat = _pattern(**cfg)
+  pat = _pattern(radius=24, g0=146, ng=8, id_mode=1, m=12, P=12, r=0, a=0)
   si_ = mmt_amd.side_inputs(pat, valid, torch.zeros_like(valid), S, materialize_pattern=True, want_segment_ids=False)
-  results = []
-  for dense in (False, True):
-    ts = [torch.from_numpy(x).cuda().to(dtype).requires_grad_(True) for x in (q, k, v, emb, bias)]
-    kw = dict(att_mask=si_['att_mask'], relative_att_ids=si_['relative_att_ids']) if dense else \
-        dict(pattern=pat, valid_len=valid)
-    out = mmt_amd.relative_attention(*ts, dropout_p=0.1, dropout_seed=1234, **kw)
-    out.backward(torch.from_numpy(dout).cuda().to(dtype))
-    results.append([out.detach().float()] + [t.grad.float() for t in ts])
-  torch.cuda.synchronize()
-  for name, a_, b_ in zip(('out', 'dq', 'dk', 'dv', 'drel_emb', 'drel_bias'), *results):
-    scale = max(1.0, float(b_.abs().max()))
-    err = float((a_ - b_).abs().max()) / scale
-    assert err < (2e-3 if dtype == torch.float32 else 3e-2), (name, err)
+  assert_structured_equals_dense_under_dropout(arrays, dtype, dict(pattern=pat, valid_len=valid),
+                                               dict(att_mask=si_['att_mask'], relative_att_ids=si_['relative_att_ids']))
 
 
 @pytest.mark.parametrize('dtype', DTYPES, ids=['f32', 'bf16'])
 def test_head128_every_tuning_bit_gives_the_default_bitwise(dtype):
   """Every switch routes head size 128 to the same general kernels: outputs and gradients equal bit for bit."""
-  from mmt_amd import _lib
-  bits = {n: getattr(_lib, n) for n in dir(_lib) if n.startswith('MMT_TUNE_')}
+  bits = tuning_bits()
   assert bits
   cfg = dict(B=2, S=288, N=2, R=32, m=12, radius=64, g0=146, ng=8, valid=[288, 200])
-  base_out, base_grads = run(dtype=dtype, **cfg)
+  base = run(dtype=dtype, **cfg)
   for name, bit in sorted(bits.items()):
-    out, grads = run(dtype=dtype, tuning=bit, oracle=False, **cfg)
-    assert np.array_equal(out, base_out), name
-    for g in base_grads:
-      assert np.array_equal(grads[g], base_grads[g]), (name, g)
+    got = run(dtype=dtype, tuning=bit, oracle=False, **cfg)
+    assert got.keys() == base.keys()
+    for g in base:
+      assert torch.equal(got[g], base[g]), (name, g)
 
 
 @pytest.mark.parametrize('dtype', DTYPES, ids=['f32', 'bf16'])
 def test_head128_strided_views_of_fused_qkv(dtype):
   import mmt_amd
   B, S, N, R = 2, 200, 2, 32
-  q, k, v, emb, bias, dout = _inputs(B, S, N, R, dtype, seed=3)
+  q, k, v, emb, bias, dout = parity_inputs(B, S, N, R, dtype, seed=3, D=D)
   qkv = torch.from_numpy(np.stack([q, k, v], axis=2)).cuda().to(dtype).requires_grad_(True)   # [B,S,3,N,128]
   te, tb = (torch.from_numpy(x).cuda().to(dtype).requires_grad_(True) for x in (emb, bias))
   pat = _pattern(radius=32, g0=70, ng=8, id_mode=1, m=12, P=0, r=0, a=0)
   out = mmt_amd.relative_attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], te, tb, pattern=pat)
   out.backward(torch.from_numpy(dout).cuda().to(dtype))
   torch.cuda.synchronize()
-  from tests._cases import dense_side_inputs
   mask, ids = dense_side_inputs(B, S, None, 32, 70, 8, 1, 12)
   ref, _ = oa.relative_attention_fwd(q, k, v, emb, bias, mask, ids)
-  tol = F32_TOL if dtype == torch.float32 else BF16_TOL
-  assert np.abs(out.detach().float().cpu().numpy() - ref).max() < tol
+  assert np.abs(out.detach().float().cpu().numpy() - ref).max() < out_tol(dtype)
   want = oa.relative_attention_bwd(dout, q, k, v, emb, bias, mask, ids)
   g = qkv.grad.float().cpu().numpy()
   for i, name in enumerate(('dq', 'dk', 'dv')):
-    e = np.abs(g[:, :, i] - want[name]).max() / (1.0 if dtype == torch.float32 else max(1.0, np.abs(want[name]).max()))
-    assert e < (2e-3 if dtype == torch.float32 else 3e-2), (name, e)
+    e = grad_error(g[:, :, i], want[name], dtype)
+    assert e < grad_tol(dtype), (name, e)
 
 
 def test_head128_config3_shape():
@@ -210,7 +133,7 @@ def test_head128_config3_shape():
   bf16): two heads against the oracle, every head finite."""
   import mmt_amd
   B, S, N, R = 1, 4096, 6, 32
-  q, k, v, emb, bias, dout = _inputs(B, S, N, R, torch.bfloat16, seed=11)
+  q, k, v, emb, bias, dout = parity_inputs(B, S, N, R, torch.bfloat16, seed=11, D=D)
   pat = _pattern(radius=64, g0=3971, ng=8, id_mode=1, m=12, P=0, r=0, a=0)
   dev = lambda x: torch.from_numpy(x).cuda().to(torch.bfloat16).requires_grad_(True)
   ts = [dev(x) for x in (q, k, v, emb, bias)]
@@ -218,7 +141,6 @@ def test_head128_config3_shape():
   out.backward(torch.from_numpy(dout).cuda().to(torch.bfloat16))
   torch.cuda.synchronize()
   assert torch.isfinite(out).all() and all(torch.isfinite(t.grad).all() for t in ts)
-  from tests._cases import dense_side_inputs
   mask, ids = dense_side_inputs(B, S, None, 64, 3971, 8, 1, 12)
   hs = [0, 5]
   sl = lambda x: np.ascontiguousarray(x[:, :, hs])
@@ -227,14 +149,13 @@ def test_head128_config3_shape():
   want = oa.relative_attention_bwd(sl(dout), sl(q), sl(k), sl(v), emb[:, hs], bias[:, hs], mask, ids)
   for name, t in (('dq', ts[0]), ('dk', ts[1]), ('dv', ts[2])):
     got = t.grad.float().cpu().numpy()[:, :, hs]
-    assert np.abs(got - want[name]).max() / max(1.0, np.abs(want[name]).max()) < 3e-2, name
+    assert np.abs(got - want[name]).max() / max(1.0, np.abs(want[name]).max()) < BF16_GRAD_TOL, name
   for name, t in (('drel_emb', ts[3]), ('drel_bias', ts[4])):
     got = t.grad.float().cpu().numpy()[:, hs]
-    assert np.abs(got - want[name]).max() / max(1.0, np.abs(want[name]).max()) < 3e-2, name
+    assert np.abs(got - want[name]).max() / max(1.0, np.abs(want[name]).max()) < BF16_GRAD_TOL, name
 
 
 def _head128_experiment():
-  from tests.test_gpu_encoder import tiny_experiment
   exp = tiny_experiment(S=256, radius=32, n_global=8)
   exp.override({'task': {'model': {'encoder': {'mmt': dict(hidden_size=256, num_attention_heads=2)},
                                    'cls_heads': [{'inner_dim': 256, 'num_classes': 2, 'name': 'itm'}]}}})
@@ -243,8 +164,6 @@ def _head128_experiment():
 
 def test_head128_encoder_train_step_against_oracle_autograd():
   import mmt_amd
-  from oracle import encoder as oenc
-  from tests.test_gpu_encoder import dense_inputs_cpu
   exp = _head128_experiment()
   task = mmt_amd.tasks.get_task(exp.task)
   torch.manual_seed(1)
@@ -254,20 +173,7 @@ def test_head128_encoder_train_step_against_oracle_autograd():
   out = model(**inputs, training=False)
   loss = task.build_losses(labels, out)
   loss.backward()
-  sd = {k: v.detach().cpu().double().requires_grad_(True) for k, v in model.named_parameters()}
-  cpu_in = dense_inputs_cpu(inputs, exp.task.train_data)
-  cpu_lab = {k: v.cpu() for k, v in labels.items()}
-  ref_loss = oenc.pretraining_loss(sd, model.encoder.get_config(), cpu_in, cpu_lab)
-  ref_loss.backward()
-  assert abs(float(loss) - float(ref_loss.detach())) < 1e-3
-  for name, p in model.named_parameters():
-    want = sd[name].grad
-    if want is None:
-      assert p.grad is None or float(p.grad.abs().max()) == 0, name
-      continue
-    got = p.grad.detach().cpu().double()
-    err = float((got - want).abs().max()) / max(1e-3, float(want.abs().max()))
-    assert err < 2e-3, (name, err)
+  assert_train_step_matches_oracle(model, loss, dense_inputs_cpu(inputs, exp.task.train_data), labels)
 
 
 def test_head128_graphed_train_step_equals_eager():

@@ -1,10 +1,9 @@
 """2-D relative ids at the image's position (`MMT_IDS_2D_IMAGE`, id_mode 3) on the GPU.
 
-Expected ids are written from the definition (tests/test_ids_image_origin_host.py: image_origin_ids -- the oracle's 2-D
-generator for the image x image block placed at [g, g + P^2), the two part ids across, the 1-D clipped id elsewhere);
-expected attention is the dense fp64 oracle fed those ids and the materialised mask.  Ids and masks are bit-exact.
-Tolerances are the standing ones of test_gpu_attention_fwd.py / _bwd.py (fp32 output 1e-3, bf16 output 2e-2, fp32
-gradients 2e-3 absolute, bf16 gradients 3e-2 of max |grad|) and of test_gpu_encoder.py for the encoder."""
+Expected ids are written from the definition (tests/_cases.py: image_origin_ids -- the oracle's 2-D generator for the
+image x image block placed at [g, g + P^2), the two part ids across, the 1-D clipped id elsewhere); expected attention
+is the dense fp64 oracle fed those ids and the materialised mask.  Ids and masks are bit-exact.  Tolerances are the
+standing bars of tests/_cases.py, and test_gpu_encoder.py's for the encoder."""
 import json
 import os
 
@@ -12,24 +11,19 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import attention as oa
 from oracle import side_inputs as si
-from tests._cases import attention_inputs, bf16_round
-from tests.test_ids_image_origin_host import image_origin_ids
-from tests.test_image_grid_host import grid_mask
+from tests._cases import DTYPES, composed, dense_side_inputs, image_origin_ids, parity_inputs
+from tests._parity import (assert_runs_agree, assert_structured_equals_dense_under_dropout, check_against, device_call,
+                           make_pattern, oracle_call, tiny_experiment, tuning_bits)
 
 pytestmark = pytest.mark.gpu
 
-F32_TOL = 1e-3
-BF16_TOL = 2e-2
-DTYPES = [torch.float32, torch.bfloat16]
+DROP_SEED = 4321
 GOLDEN = json.load(open(os.path.join(os.path.dirname(__file__), 'golden', 'feature_utils_golden.json')))
 
 
-def _pattern(id_mode=3, *, radius=1 << 30, g0=0, ng=0, m, P, r, g=2, a=0):
-  import mmt_amd
-  return mmt_amd.AttentionPattern(local_radius=radius, global_start=g0, n_global=ng, id_mode=id_mode, max_dist=m,
-                                  patches_per_row=P, core_layers=r, grid_radius=a, grid_start=g)
+def _pattern(id_mode=3, **kw):
+  return make_pattern(id_mode=id_mode, **kw)
 
 
 def _device_ids(pat, S, B=1, **kw):
@@ -67,76 +61,13 @@ def test_origin_zero_gives_the_reference_golden_matrices(case):
 
 
 # ---- shared runner ---------------------------------------------------------------------------------------------------
-def _inputs(B, S, N, R, dtype, seed, D=64):
-  q, k, v, emb, bias = attention_inputs(B, S, N, R, seed, D)
-  dout = np.random.default_rng(seed + 100).standard_normal(q.shape).astype(np.float32)
-  if dtype == torch.bfloat16:
-    q, k, v, emb, bias, dout = (bf16_round(x) for x in (q, k, v, emb, bias, dout))
-  return q, k, v, emb, bias, dout
-
-
 def expected_side_inputs(B, S, valid, radius, g0, ng, m, P, r, g, a=0):
   """Dense [B,S,S] mask (band / global / segmented, ORed with grid & segmented when a > 0) and the ids of id_mode 3."""
-  valid = valid if valid is not None else [S] * B
-  gm = grid_mask(S, g, P, a)
-  masks = []
-  for vl in valid:
-    ex = np.arange(S) < vl
-    masks.append(si.sparse_pattern_mask(S, vl, min(radius, S), g0, ng) | (gm & (ex[:, None] == ex[None, :])))
-  ids = np.broadcast_to(image_origin_ids(S, m, P, r, g), (B, S, S)).astype(np.int32).copy()
-  return np.stack(masks).astype(np.int32), ids
+  return dense_side_inputs(B, S, valid, radius, g0, ng, 3, m, P, r, a=a, g=g)
 
 
-def device_call(arrays, dtype, *, dropout=0.0, **kw):
-  """Forward and backward through autograd; returns (out, {grad name: tensor}) as fp32 tensors on the device."""
-  import mmt_amd
-  q, k, v, emb, bias, dout = arrays
-  dev = lambda x: torch.from_numpy(x).cuda().to(dtype).contiguous()
-  ts = [dev(x).requires_grad_(True) for x in (q, k, v, emb, bias)]
-  if dropout:
-    kw.update(dropout_p=dropout, dropout_seed=4321)
-  out = mmt_amd.relative_attention(*ts, **kw)
-  out.backward(dev(dout))
-  torch.cuda.synchronize()
-  return out.detach().float(), {n: t.grad.float() for n, t in zip(('dq', 'dk', 'dv', 'drel_emb', 'drel_bias'), ts)}
-
-
-def oracle_call(arrays, mask, ids, B, N, S, dropout=0.0):
-  from mmt_amd import step_scalars
-  q, k, v, emb, bias, dout = arrays
-  okw = {}
-  if dropout:
-    assert step_scalars.epoch_ptr(torch.device('cuda:0')) is None
-    dseed = (4321 + step_scalars.host_epoch(torch.device('cuda:0'))) & ((1 << 64) - 1)
-    keep, keep_prob = oa.dropout_keep_mask(B, N, S, dropout, dseed)
-    okw.update(keep_mask=keep, keep_prob=keep_prob)
-  ref, _ = oa.relative_attention_fwd(q, k, v, emb, bias, mask, ids, **okw)
-  return ref, oa.relative_attention_bwd(dout, q, k, v, emb, bias, mask, ids, **okw)
-
-
-def check_against(got, ref, want, dtype, label=''):
-  out, grads = got
-  out = out.cpu().numpy()
-  assert np.isfinite(out).all(), label
-  err = np.abs(out - ref).max()
-  print(f'{label} max |out - oracle| = {err:.3e}')
-  assert err < (F32_TOL if dtype == torch.float32 else BF16_TOL), f'{label} max |out - oracle| = {err}'
-  for name, g in grads.items():
-    g, w = g.cpu().numpy(), want[name]
-    assert np.isfinite(g).all(), (label, name)
-    if dtype == torch.float32:
-      e = np.abs(g - w).max()
-      print(f'{label} {name}: max abs err {e:.3e}')
-      assert e < 2e-3, f'{label} {name}: max abs err {e}'
-    else:
-      e = np.abs(g - w).max() / max(1.0, np.abs(w).max())
-      print(f'{label} {name}: max err relative to max |grad| = {e:.3e}')
-      assert e < 3e-2, f'{label} {name}: max err relative to max |grad| = {e}'
-
-
-def _tuning_bits():
-  from mmt_amd import _lib
-  return {n: getattr(_lib, n) for n in dir(_lib) if n.startswith('MMT_TUNE_')}
+def drop_kw(dropout):
+  return dict(dropout_p=dropout, dropout_seed=DROP_SEED) if dropout else {}
 
 
 # ---- 2. forward and every gradient against the oracle ----------------------------------------------------------------
@@ -151,15 +82,15 @@ def _tuning_bits():
 def test_forward_and_backward_against_oracle(g, radius, ng, dtype, D):
   B, S, N, R, P, r, m = 2, 96, 2, 49, 6, 2, 12
   valid = [96, 90]
-  arrays = _inputs(B, S, N, R, dtype, seed=g + ng, D=D)
+  arrays = parity_inputs(B, S, N, R, dtype, seed=g + ng, D=D)
   mask, ids = expected_side_inputs(B, S, valid, radius, g + P * P, ng, m, P, r, g)
   pat = _pattern(radius=radius, g0=g + P * P, ng=ng, m=m, P=P, r=r, g=g)
   vl = torch.tensor(valid, dtype=torch.int32, device='cuda:0')
   for dropout in (0.0, 0.1):
-    ref, want = oracle_call(arrays, mask, ids, B, N, S, dropout)
-    for name, bit in [('default', 0)] + sorted(_tuning_bits().items()):
-      got = device_call(arrays, dtype, dropout=dropout, pattern=pat, valid_len=vl, tuning=bit)
-      check_against(got, ref, want, dtype, f'[{name} p={dropout}]')
+    ref = oracle_call(arrays, mask, ids, dropout=(dropout, DROP_SEED) if dropout else None)
+    for name, bit in [('default', 0)] + sorted(tuning_bits().items()):
+      got = device_call(arrays, dtype, pattern=pat, valid_len=vl, tuning=bit, **drop_kw(dropout))
+      check_against(got, ref, dtype, f'[{name} p={dropout}]')
 
 
 # ---- 3. the lean look-up path: all-image tiles with an origin off the tile boundary ---------------------------------
@@ -169,7 +100,7 @@ LEAN = dict(S=1152, N=1, R=49, P=32, r=2, m=12, radius=64)      # r = 2: table w
 @pytest.fixture(scope='module')
 def lean_case():
   c = LEAN
-  arrays = _inputs(1, c['S'], c['N'], c['R'], torch.bfloat16, seed=11)
+  arrays = parity_inputs(1, c['S'], c['N'], c['R'], torch.bfloat16, seed=11)
   return arrays
 
 
@@ -182,11 +113,11 @@ def test_lean_lookup_tiles_against_oracle(lean_case, r):
   S, g = c['S'], 2
   assert g % 32 and g + 31 < 32 + 31 and 32 * 31 + 31 < g + c['P'] ** 2 < S     # all-image tiles exist, both ends are mixed
   mask, ids = expected_side_inputs(1, S, None, c['radius'], 0, 0, c['m'], c['P'], c['r'], g)
-  ref, want = oracle_call(lean_case, mask, ids, 1, c['N'], S)
+  ref = oracle_call(lean_case, mask, ids)
   pat = _pattern(radius=c['radius'], m=c['m'], P=c['P'], r=c['r'], g=g)
   from mmt_amd import _lib
   for form, bit in (('handover-window', 0), ('handover-wave', _lib.MMT_TUNE_BWD_HO_PER_WAVE), ('recompute', _lib.MMT_TUNE_BWD_NO_HANDOVER)):
-    check_against(device_call(lean_case, torch.bfloat16, pattern=pat, tuning=bit), ref, want, torch.bfloat16, f'[{form}]')
+    check_against(device_call(lean_case, torch.bfloat16, pattern=pat, tuning=bit), ref, torch.bfloat16, f'[{form}]')
 
 
 # ---- 4. structured equals dense --------------------------------------------------------------------------------------
@@ -194,22 +125,15 @@ def test_lean_lookup_tiles_against_oracle(lean_case, r):
 def test_structured_equals_dense_operator_on_materialised_side_inputs(dtype):
   import mmt_amd
   B, S, N, R, P, r, m, g = 2, 96, 2, 49, 6, 2, 12, 2
-  arrays = _inputs(B, S, N, R, dtype, seed=7)
+  arrays = parity_inputs(B, S, N, R, dtype, seed=7)
   valid = torch.tensor([96, 81], dtype=torch.int32, device='cuda:0')
   pat = _pattern(radius=8, g0=g + P * P, ng=8, m=m, P=P, r=r, g=g)
   si_ = mmt_amd.side_inputs(pat, valid, torch.zeros_like(valid), S, materialize_pattern=True, want_segment_ids=False)
   mask, ids = expected_side_inputs(B, S, valid.tolist(), 8, g + P * P, 8, m, P, r, g)
   assert np.array_equal(si_['att_mask'].cpu().numpy(), mask) and np.array_equal(si_['relative_att_ids'].cpu().numpy(), ids)
-  a = device_call(arrays, dtype, dropout=0.1, pattern=pat, valid_len=valid)
-  b = device_call(arrays, dtype, dropout=0.1, att_mask=si_['att_mask'], relative_att_ids=si_['relative_att_ids'])
-  err = float((a[0] - b[0]).abs().max())                   # the output: absolute, the oracle cases' bound
-  print(f'out: max abs diff {err:.3e}')
-  assert err < (F32_TOL if dtype == torch.float32 else BF16_TOL), ('out', err)
-  for name in a[1]:                                        # the gradients: 2e-3 absolute (fp32), 3e-2 of max |grad| (bf16)
-    x, y = a[1][name], b[1][name]
-    err = float((x - y).abs().max()) / (1.0 if dtype == torch.float32 else max(1.0, float(y.abs().max())))
-    print(f'{name}: {err:.3e}')
-    assert err < (2e-3 if dtype == torch.float32 else 3e-2), (name, err)
+  assert_structured_equals_dense_under_dropout(      # the output: absolute; the gradients: the oracle cases' bars
+      arrays, dtype, dict(pattern=pat, valid_len=valid),
+      dict(att_mask=si_['att_mask'], relative_att_ids=si_['relative_att_ids']), seed=DROP_SEED, standing_bars=True)
 
 
 # ---- 5. g = 0 is MMT_IDS_2D ------------------------------------------------------------------------------------------
@@ -220,14 +144,14 @@ def test_origin_zero_equals_mode_2_bitwise(shape, lean_case):
     kw = dict(radius=c['radius'], g0=1100, ng=8, m=c['m'], P=c['P'], r=c['r'])
   else:
     dtype = torch.float32 if shape == 'general-f32' else torch.bfloat16
-    arrays = _inputs(2, 96, 2, 49, dtype, seed=3, D=64 if shape == 'general-f32' else 128)
+    arrays = parity_inputs(2, 96, 2, 49, dtype, seed=3, D=64 if shape == 'general-f32' else 128)
     kw = dict(radius=8, g0=40, ng=8, m=12, P=6, r=2)
     vl = torch.tensor([96, 77], dtype=torch.int32, device='cuda:0')
-  a = device_call(arrays, dtype, dropout=0.1, pattern=_pattern(3, g=0, **kw), valid_len=vl)
-  b = device_call(arrays, dtype, dropout=0.1, pattern=_pattern(2, **kw), valid_len=vl)
-  assert torch.equal(a[0], b[0])
-  for n in b[1]:
-    assert torch.equal(a[1][n], b[1][n]), n
+  a = device_call(arrays, dtype, pattern=_pattern(3, g=0, **kw), valid_len=vl, **drop_kw(0.1))
+  b = device_call(arrays, dtype, pattern=_pattern(2, **kw), valid_len=vl, **drop_kw(0.1))
+  assert a.keys() == b.keys() and len(b) == 6
+  for n in b:
+    assert torch.equal(a[n], b[n]), n
 
 
 # ---- 6. with the grid term: ids and grid read one origin ------------------------------------------------------------
@@ -235,31 +159,15 @@ def test_origin_zero_equals_mode_2_bitwise(shape, lean_case):
 def test_with_the_grid_term_against_oracle(dtype):
   B, S, N, R, P, r, m, g = 2, 96, 2, 49, 6, 2, 12, 2
   valid = [96, 70]
-  arrays = _inputs(B, S, N, R, dtype, seed=5)
+  arrays = parity_inputs(B, S, N, R, dtype, seed=5)
   mask, ids = expected_side_inputs(B, S, valid, 4, g + P * P, 8, m, P, r, g, a=1)
   assert (mask != expected_side_inputs(B, S, valid, 4, g + P * P, 8, m, P, r, g)[0]).any()      # the grid adds pairs
-  ref, want = oracle_call(arrays, mask, ids, B, N, S)
   pat = _pattern(radius=4, g0=g + P * P, ng=8, m=m, P=P, r=r, g=g, a=1)
   vl = torch.tensor(valid, dtype=torch.int32, device='cuda:0')
-  check_against(device_call(arrays, dtype, pattern=pat, valid_len=vl), ref, want, dtype)
+  check_against(device_call(arrays, dtype, pattern=pat, valid_len=vl), oracle_call(arrays, mask, ids), dtype)
 
 
 # ---- 7. packed multimodal rows: every example's image at its own g --------------------------------------------------
-def composed_origin(lengths, S, radius, m, P, r, g):
-  """Every run of a row (its examples and the padding tail) alone at the start of a row of its own length, on the
-  diagonal of [S,S]; a run shorter than g + P^2 keeps the leading part of the ids of one that long."""
-  B = len(lengths)
-  mask = np.zeros((B, S, S), np.int32)
-  rel = np.zeros((B, S, S), np.int32)
-  for b, row in enumerate(lengths):
-    at = 0
-    for L in list(row) + ([S - sum(row)] if sum(row) < S else []):
-      mask[b, at:at + L, at:at + L] = si.sparse_pattern_mask(L, L, min(radius, L))
-      rel[b, at:at + L, at:at + L] = image_origin_ids(max(L, g + P * P), m, P, r, g)[:L, :L]
-      at += L
-  return mask, rel
-
-
 @pytest.mark.parametrize('dtype', DTYPES, ids=['f32', 'bf16'])
 @pytest.mark.parametrize('radius', [8, 1 << 30], ids=['r8', 'full'])
 def test_packed_rows_each_example_sees_its_own_image(radius, dtype):
@@ -267,15 +175,14 @@ def test_packed_rows_each_example_sees_its_own_image(radius, dtype):
   S, N, R, P, r, m, g = 128, 2, 49, 6, 2, 12, 2
   lengths = [[50, 70], [77, 45]]                         # second examples start off the tile boundaries; tails of 8 and 6
   ex_ids, starts, _, _ = mmt_amd.packed_example_layout(lengths, [[True, True]] * 2, S)
-  mask, rel = composed_origin(lengths, S, radius, m, P, r, g)
+  mask, rel = composed(lengths, S, radius, 3, m, P, r, g=g)      # every run alone, its image at its own g
   # not what MMT_IDS_2D composes (image at local 0), and not the row-aligned ids either
   assert (rel[0, :50, :50] != si.relative_ids_from_desc(50, 2, m, P, r)).any()
   assert ((rel[0, 50:120, 50:120] != image_origin_ids(S, m, P, r, g)[50:120, 50:120]) & (mask[0, 50:120, 50:120] != 0)).any()
-  arrays = _inputs(2, S, N, R, dtype, seed=9)
-  ref, want = oracle_call(arrays, mask, rel, 2, N, S)
+  arrays = parity_inputs(2, S, N, R, dtype, seed=9)
   pat = _pattern(radius=radius, m=m, P=P, r=r, g=g)
   got = device_call(arrays, dtype, pattern=pat, example_ids=ex_ids.cuda(), example_starts=starts.cuda())
-  check_against(got, ref, want, dtype)
+  check_against(got, oracle_call(arrays, mask, rel), dtype)
 
 
 # ---- 8. encoder level -------------------------------------------------------------------------------------------------
@@ -284,7 +191,6 @@ def test_encoder_structured_equals_dense_side_inputs():
   the structured pattern and the encoder fed the dense side inputs agree, forward and parameter gradients."""
   import mmt_amd
   from mmt_amd import _lib
-  from tests.test_gpu_encoder import tiny_experiment
   exp = tiny_experiment(S=256, core=2, R=49)
   exp.task.train_data.relative_att_align_image = True
   task = mmt_amd.tasks.get_task(exp.task)
@@ -309,10 +215,5 @@ def test_encoder_structured_equals_dense_side_inputs():
     loss.backward()
     runs.append((float(loss.detach()), seq.float().cpu(),
                  {n: p.grad.detach().double().cpu() for n, p in model.named_parameters() if p.grad is not None}))
-  (l0, s0, g0), (l1, s1, g1) = runs
-  assert abs(l0 - l1) < 1e-3
-  assert s0.shape == (2, 256, 128) and float((s0 - s1).abs().max()) < 1e-3
-  assert g0.keys() == g1.keys()
-  for name in g0:
-    err = float((g0[name] - g1[name]).abs().max()) / max(1e-3, float(g1[name].abs().max()))
-    assert err < 2e-3, (name, err)
+  assert runs[0][1].shape == (2, 256, 128)
+  assert_runs_agree(runs)

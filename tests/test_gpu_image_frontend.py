@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_image_frontend import CONFIGS, batch, check_outputs, restatement
+from tests._cases import CONFIGS, batch, check_outputs, restatement
 
 pytestmark = pytest.mark.gpu
 

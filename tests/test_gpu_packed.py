@@ -1,21 +1,17 @@
 """Packed examples on the structured kernels (`example_ids=`, `MMT_FLAG_EXAMPLE_IDS`) on the GPU.
 
 The oracle mask is `sparse_pattern_mask(S, S, radius, g0, ng) & make_segmented_att_mask(ids)` fed to the dense fp64
-oracle; tolerances are the standing ones of test_gpu_image_grid.py (fp32 output 1e-3, bf16 output 2e-2, fp32
-gradients 2e-3 absolute, bf16 gradients 3e-2 of max |grad|)."""
+oracle; tolerances are the standing bars of tests/_cases.py."""
 import numpy as np
 import pytest
 import torch
 
-from oracle import attention as oa
-from oracle import side_inputs as si
-from tests._cases import attention_inputs, bf16_round
+from tests._cases import DTYPES, dense_side_inputs, grad_error, grad_tol, out_tol, parity_inputs
+from tests._parity import (ACCUM_SEED, GRAD_NAMES, assert_structured_equals_dense_under_dropout,
+                           assert_train_step_matches_oracle, check_against, device_call, make_pattern, oracle_call,
+                           tiny_experiment, tuning_bits)
 
 pytestmark = pytest.mark.gpu
-
-F32_TOL = 1e-3
-BF16_TOL = 2e-2
-DTYPES = [torch.float32, torch.bfloat16]
 
 
 def ids_from_lengths(lengths, S):
@@ -23,92 +19,30 @@ def ids_from_lengths(lengths, S):
   return mmt_amd.example_ids_from_lengths(lengths, S).numpy()
 
 
-def packed_side_inputs(ids, radius, g0, ng, id_mode, m, P=0, r=0, gidx=None, extra=None):
-  """Dense [B,S,S] mask + relative ids of a packed pattern: band / global mask (no length) ANDed with the segmented
-  mask of the example ids.  `extra` [S,S] bool (an image grid) is ORed into the pattern before the AND."""
+def packed_side_inputs(ids, radius, g0, ng, id_mode, m, P=0, r=0, gidx=None, a=0):
+  """Dense [B,S,S] mask + relative ids of a packed pattern: band / global (/ grid) mask, no length, ANDed with the
+  segmented mask of the example ids."""
   B, S = ids.shape
-  pat = si.sparse_pattern_mask(S, S, min(radius, S), g0, ng, gidx)
-  if extra is not None:
-    pat = pat | extra
-  mask = np.stack([pat & si.make_segmented_att_mask(ids[b]) for b in range(B)]).astype(np.int32)
-  rel = None
-  if id_mode:
-    rel = np.broadcast_to(si.relative_ids_from_desc(S, id_mode, m, P, r), (B, S, S)).astype(np.int32).copy()
-  return mask, rel
-
-
-def _pattern(radius, g0, ng, id_mode, m, P=0, r=0, **kw):
-  import mmt_amd
-  return mmt_amd.AttentionPattern(local_radius=radius, global_start=g0, n_global=ng, id_mode=id_mode, max_dist=m,
-                                  patches_per_row=P, core_layers=r, **kw)
-
-
-def _inputs(B, S, N, R, dtype, seed, D=64):
-  q, k, v, emb, bias = attention_inputs(B, S, N, R, seed, D)
-  dout = np.random.default_rng(seed + 100).standard_normal(q.shape).astype(np.float32)
-  if dtype == torch.bfloat16:
-    q, k, v, dout = (bf16_round(x) for x in (q, k, v, dout))
-    emb = None if emb is None else bf16_round(emb)
-    bias = None if bias is None else bf16_round(bias)
-  return q, k, v, emb, bias, dout
-
-
-def check_against(got_out, grads, ref, want, dtype, seed_grads=None):
-  tol = F32_TOL if dtype == torch.float32 else BF16_TOL
-  assert np.isfinite(got_out).all()
-  err = np.abs(got_out - ref).max()
-  print(f'max |out - oracle| = {err:.3e}')
-  assert err < tol, f'max |out - oracle| = {err}'
-  for name, got in grads.items():
-    w = want[name] + (seed_grads or {}).get(name, 0.0)
-    assert np.isfinite(got).all(), name
-    if dtype == torch.float32:
-      e = np.abs(got - w).max()
-      print(f'{name}: max abs err {e:.3e}')
-      assert e < 2e-3, f'{name}: max abs err {e}'
-    else:
-      e = np.abs(got - w).max() / max(1.0, np.abs(w).max())
-      print(f'{name}: max err relative to max |grad| = {e:.3e}')
-      assert e < 3e-2, f'{name}: max err relative to max |grad| = {e}'
+  return dense_side_inputs(B, S, None, radius, g0, ng, id_mode, m, P, r, gidx, a, example_ids=ids)
 
 
 def run_packed(N, R, dtype, *, ids, radius=1 << 30, g0=0, ng=0, id_mode=1, m=3, P=0, r=0, D=64, seed=0, tuning=0,
-               accum=False, scale_before_add=False, oracle=True, pattern_kw=None, extra=None, gidx=None):
+               accum=False, scale_before_add=False, oracle=True, a=0, gidx=None):
   """Structured call with example ids (forward, backward through autograd) against the dense oracle.  Returns the
-  device results (out, grads) as torch tensors for comparisons between calls."""
-  import mmt_amd
+  device results for comparisons between calls."""
   if R == 0:
     id_mode = 0
   ids = np.asarray(ids, np.int32)
   B, S = ids.shape
-  q, k, v, emb, bias, dout = _inputs(B, S, N, R, dtype, seed, D)
-  dev = lambda x, dt=dtype: None if x is None else torch.from_numpy(x).cuda().to(dt).contiguous()
-  tq, tk, tv, te, tb = (None if x is None else dev(x).requires_grad_(True) for x in (q, k, v, emb, bias))
-  pat = _pattern(radius, g0, ng, id_mode, m, P, r, **(pattern_kw or {}))
-  tids = torch.from_numpy(ids).cuda()
-  kw = dict(pattern=pat, example_ids=tids, tuning=tuning, scale_before_add=scale_before_add)
-  out = mmt_amd.relative_attention(tq, tk, tv, te, tb, **kw)
-  seed_grads = {}
-  if accum and R:                              # MMT_FLAG_ACCUM_REL_GRADS: added onto what the buffers hold
-    seed_grads = {'drel_emb': np.full(emb.shape, 0.25, np.float32), 'drel_bias': np.full(bias.shape, -0.5, np.float32)}
-    demb, dbias = (torch.from_numpy(seed_grads[n]).cuda() for n in ('drel_emb', 'drel_bias'))
-    det = [t.detach() for t in (tq, tk, tv, te, tb)]
-    lse = mmt_amd.relative_attention_forward(*det, **kw)[1]
-    mmt_amd.relative_attention_backward(dev(dout), *det, out.detach(), lse, rel_grads_accum=(demb, dbias), **kw)
-  out.backward(dev(dout))
-  torch.cuda.synchronize()
-  t_out = out.detach().float()
-  t_grads = {n: t.grad.float() for n, t in (('dq', tq), ('dk', tk), ('dv', tv), ('drel_emb', te), ('drel_bias', tb))
-             if t is not None}
-  if accum and R:
-    t_grads['drel_emb'], t_grads['drel_bias'] = demb, dbias
+  arrays = parity_inputs(B, S, N, R, dtype, seed, D)
+  pat = make_pattern(radius=radius, g0=g0, ng=ng, id_mode=id_mode, m=m, P=P, r=r, a=a, gidx=gidx)
+  got = device_call(arrays, dtype, accum=accum, pattern=pat, example_ids=torch.from_numpy(ids).cuda(), tuning=tuning,
+                    scale_before_add=scale_before_add)
   if oracle:
-    mask, rel = packed_side_inputs(ids, radius, g0, ng, id_mode, m, P, r, gidx, extra)
-    okw = dict(scale_after_add=not scale_before_add)
-    ref, _ = oa.relative_attention_fwd(q, k, v, emb, bias, mask, rel, **okw)
-    want = oa.relative_attention_bwd(dout, q, k, v, emb, bias, mask, rel, **okw)
-    check_against(t_out.cpu().numpy(), {n: g.cpu().numpy() for n, g in t_grads.items()}, ref, want, dtype, seed_grads)
-  return t_out, t_grads
+    mask, rel = packed_side_inputs(ids, radius, g0, ng, id_mode, m, P, r, gidx, a)
+    ref = oracle_call(arrays, mask, rel, scale_before_add=scale_before_add)
+    check_against(got, ref, dtype, seed_grads=ACCUM_SEED if accum else None)
+  return got
 
 
 def _alternating(S, period=2):
@@ -169,8 +103,8 @@ def test_single_breakpoint_equals_valid_len(radius, ng, dtype):
   bp = np.zeros((B, S), np.int32)
   bp[np.arange(B), np.array(vl) - 1] = 1
   assert (mmt_amd.example_ids_from_breakpoints(torch.from_numpy(bp)).numpy() == ids).all()
-  q, k, v, emb, bias, dout = _inputs(B, S, N, R, dtype, seed=3)
-  pat = _pattern(radius, 120, ng, 1, 12)
+  q, k, v, emb, bias, dout = parity_inputs(B, S, N, R, dtype, seed=3)
+  pat = make_pattern(radius=radius, g0=120, ng=ng, id_mode=1, m=12)
   results = []
   for packed in (True, False):
     ts = [torch.from_numpy(x).cuda().to(dtype).requires_grad_(True) for x in (q, k, v, emb, bias)]
@@ -180,13 +114,13 @@ def test_single_breakpoint_equals_valid_len(radius, ng, dtype):
     out.backward(torch.from_numpy(dout).cuda().to(dtype))
     results.append([out.detach().float()] + [t.grad.float() for t in ts])
   torch.cuda.synchronize()
-  for name, a_, b_ in zip(('out', 'dq', 'dk', 'dv', 'drel_emb', 'drel_bias'), *results):
+  for name, a_, b_ in zip(('out',) + GRAD_NAMES, *results):
     err = float((a_ - b_).abs().max()) / max(1.0, float(b_.abs().max()))
     print(f'{name}: max |ids - valid_len| = {err:.3e}')
     if dtype == torch.float32:
       assert torch.equal(a_, b_), (name, err)
     else:
-      assert err < (BF16_TOL if name == 'out' else 3e-2), (name, err)
+      assert err < (out_tol(dtype) if name == 'out' else grad_tol(dtype)), (name, err)
 
 
 @pytest.mark.parametrize('dtype', DTYPES, ids=['f32', 'bf16'])
@@ -198,8 +132,8 @@ def test_packed_equals_separate_calls(radius, dtype):
   import mmt_amd
   N, R, L, n = 2, 32, 256, 4
   S = L * n
-  q, k, v, emb, bias, dout = _inputs(1, S, N, R, dtype, seed=11)
-  pat = _pattern(radius, 0, 0, 1, 12)
+  q, k, v, emb, bias, dout = parity_inputs(1, S, N, R, dtype, seed=11)
+  pat = make_pattern(radius=radius, id_mode=1, m=12)
   cu = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda().to(dtype)
   ts = [cu(x).requires_grad_(True) for x in (q, k, v)]
   ids = torch.from_numpy(ids_from_lengths([[L] * n], S)).cuda()
@@ -213,47 +147,25 @@ def test_packed_equals_separate_calls(radius, dtype):
     o.backward(cu(dout[:, sl]))
     torch.cuda.synchronize()
     for name, a_, b_ in zip(('out', 'dq', 'dk', 'dv'), [x[:, sl] for x in packed], [o.detach().float()] + [t.grad.float() for t in te]):
-      err = float((a_ - b_).abs().max())
-      print(f'example {e} {name}: max |packed - separate| = {err:.3e}')
-      if name == 'out':
-        assert err < (F32_TOL if dtype == torch.float32 else BF16_TOL), (e, name, err)
-      elif dtype == torch.float32:
-        assert err < 2e-3, (e, name, err)
-      else:
-        assert err / max(1.0, float(b_.abs().max())) < 3e-2, (e, name, err)
+      a_, b_ = a_.cpu().numpy(), b_.cpu().numpy()
+      err = np.abs(a_ - b_).max() if name == 'out' else grad_error(a_, b_, dtype)
+      print(f'example {e} {name}: |packed - separate| = {err:.3e}')
+      assert err < (out_tol(dtype) if name == 'out' else grad_tol(dtype)), (e, name, err)
 
 
 @pytest.mark.parametrize('dtype', DTYPES, ids=['f32', 'bf16'])
 def test_structured_packed_equals_dense_operator_under_dropout(dtype):
   """The packed call on the structured kernels and the dense operator on the materialised mask draw the same keep
   mask (dropout 0.1, same seed) and agree in forward and backward."""
-  import mmt_amd
   N, R = 2, 32
   ids = ids_from_lengths([[100, 140, 80], [51, 200, 40]], 320)
   B, S = ids.shape
   cfg = dict(radius=6, g0=146, ng=8, id_mode=1, m=12)
-  q, k, v, emb, bias, dout = _inputs(B, S, N, R, dtype, seed=7)
+  arrays = parity_inputs(B, S, N, R, dtype, seed=7)
   mask, rel = packed_side_inputs(ids, **cfg)
-  pat = _pattern(**cfg)
-  results = []
-  for dense in (False, True):
-    ts = [torch.from_numpy(x).cuda().to(dtype).requires_grad_(True) for x in (q, k, v, emb, bias)]
-    kw = dict(att_mask=torch.from_numpy(mask).cuda(), relative_att_ids=torch.from_numpy(rel).cuda()) if dense else \
-        dict(pattern=pat, example_ids=torch.from_numpy(ids).cuda())
-    out = mmt_amd.relative_attention(*ts, dropout_p=0.1, dropout_seed=1234, **kw)
-    out.backward(torch.from_numpy(dout).cuda().to(dtype))
-    results.append([out.detach().float()] + [t.grad.float() for t in ts])
-  torch.cuda.synchronize()
-  for name, a_, b_ in zip(('out', 'dq', 'dk', 'dv', 'drel_emb', 'drel_bias'), *results):
-    scale = max(1.0, float(b_.abs().max()))
-    err = float((a_ - b_).abs().max()) / scale
-    print(f'{name}: {err:.3e}')
-    assert err < (2e-3 if dtype == torch.float32 else 3e-2), (name, err)
-
-
-def _tuning_bits():
-  from mmt_amd import _lib
-  return {n: getattr(_lib, n) for n in dir(_lib) if n.startswith('MMT_TUNE_')}
+  assert_structured_equals_dense_under_dropout(
+      arrays, dtype, dict(pattern=make_pattern(**cfg), example_ids=torch.from_numpy(ids).cuda()),
+      dict(att_mask=torch.from_numpy(mask).cuda(), relative_att_ids=torch.from_numpy(rel).cuda()))
 
 
 @pytest.mark.parametrize('dtype', DTYPES, ids=['f32', 'bf16'])
@@ -262,12 +174,12 @@ def test_every_tuning_bit_gives_the_bitwise_result_of_the_defaults(ng, dtype):
   """With example ids every lean / window / plane-walk / sliding-window / hand-over path declines: each MMT_TUNE_*
   bit runs the kernels `tuning = 0` runs, bit for bit."""
   cfg = dict(N=2, R=32, m=12, radius=16, g0=146, ng=ng, ids=ids_from_lengths([[100, 120, 68], [288]], 288))
-  base_out, base_grads = run_packed(dtype=dtype, **cfg)
-  for name, bit in sorted(_tuning_bits().items()):
-    out, grads = run_packed(dtype=dtype, tuning=bit, oracle=False, **cfg)
-    assert torch.equal(out, base_out), name
-    for g in base_grads:
-      assert torch.equal(grads[g], base_grads[g]), (name, g)
+  base = run_packed(dtype=dtype, **cfg)
+  for name, bit in sorted(tuning_bits().items()):
+    got = run_packed(dtype=dtype, tuning=bit, oracle=False, **cfg)
+    assert got.keys() == base.keys()
+    for g in base:
+      assert torch.equal(got[g], base[g]), (name, g)
 
 
 @pytest.mark.parametrize('dtype', DTYPES, ids=['f32', 'bf16'])
@@ -275,15 +187,13 @@ def test_every_tuning_bit_gives_the_bitwise_result_of_the_defaults(ng, dtype):
 def test_grid_or_listed_globals_with_example_ids_take_the_dense_route(form, dtype):
   """Patterns the structured kernels refuse with example ids -- an image grid, a listed global set -- are served
   through the dense operator on the materialised mask ANDed with the ids' segmented mask, and match the oracle."""
-  from tests.test_image_grid_host import grid_mask
   S = 192
   ids = ids_from_lengths([[80, 70, 42], [150, 30]], S)
   if form == 'grid':
-    run_packed(2, 32, dtype, ids=ids, radius=4, g0=146, ng=8, m=12, P=12, pattern_kw=dict(grid_radius=1, grid_start=2),
-               extra=grid_mask(S, 2, 12, 1))
+    run_packed(2, 32, dtype, ids=ids, radius=4, g0=146, ng=8, m=12, P=12, a=1)
   else:
     gidx = (0, 50, 103, 140)
-    run_packed(2, 32, dtype, ids=ids, radius=4, g0=0, ng=4, m=12, pattern_kw=dict(global_index=gidx), gidx=gidx)
+    run_packed(2, 32, dtype, ids=ids, radius=4, g0=0, ng=4, m=12, gidx=gidx)
 
 
 def test_config3_shape_packed_against_oracle():
@@ -298,8 +208,6 @@ def test_tiny_encoder_train_step_with_example_ids_matches_oracle():
   """A tiny pretraining model (2 layers, fused path, radius 32, 8 globals) fed `example_ids` instead of `valid_len`:
   loss and every parameter gradient against the float64 dense CPU oracle fed the dense mask of the same ids."""
   import mmt_amd
-  from oracle import encoder as oenc
-  from tests.test_gpu_encoder import tiny_experiment
   exp = tiny_experiment(S=256, radius=32, n_global=8)
   task = mmt_amd.tasks.get_task(exp.task)
   torch.manual_seed(1)
@@ -315,22 +223,9 @@ def test_tiny_encoder_train_step_with_example_ids_matches_oracle():
   out = model(**inputs, training=False)
   loss = task.build_losses(labels, out)
   loss.backward()
-  sd = {k: v.detach().cpu().double().requires_grad_(True) for k, v in model.named_parameters()}
   cpu_in = {k: v.detach().cpu() for k, v in inputs.items() if torch.is_tensor(v)}
   mask, rel = packed_side_inputs(ids, pat.local_radius, pat.global_start, pat.n_global, pat.id_mode, pat.max_dist,
                                  pat.patches_per_row, pat.core_layers)
   cpu_in['att_mask'] = torch.from_numpy(mask)
   cpu_in['relative_att_ids'] = torch.from_numpy(rel)
-  cpu_lab = {k: v.cpu() for k, v in labels.items()}
-  ref_loss = oenc.pretraining_loss(sd, model.encoder.get_config(), cpu_in, cpu_lab)
-  ref_loss.backward()
-  print(f'loss {float(loss):.6f} oracle {float(ref_loss):.6f}')
-  assert abs(float(loss) - float(ref_loss)) < 1e-3
-  for name, p in model.named_parameters():
-    want = sd[name].grad
-    if want is None:
-      assert p.grad is None or float(p.grad.abs().max()) == 0, name
-      continue
-    got = p.grad.detach().cpu().double()
-    err = float((got - want).abs().max()) / max(1e-3, float(want.abs().max()))
-    assert err < 2e-3, (name, err)
+  assert_train_step_matches_oracle(model, loss, cpu_in, labels)

@@ -4,55 +4,20 @@ what it would see alone at the start of a row.
 The oracle states that directly: for each run of equal ids of length L the single-example `sparse_pattern_mask(L, L, ..)`
 (ORed with `grid_mask` where the pattern has a grid) and `relative_ids_from_desc(L, ..)` go on the diagonal of [S,S],
 everything off the blocks is masked, and the result is fed to the dense fp64 oracle.  A padding tail is a run like any
-other.  Tolerances are the standing ones of test_gpu_packed.py (fp32 output 1e-3, bf16 output 2e-2, fp32 gradients 2e-3
-absolute, bf16 gradients 3e-2 of max |grad|).
+other (tests/_cases.py `composed`).  Tolerances are the standing bars of tests/_cases.py.
 
 Every 2-D case asserts on the CPU, before the GPU call, that the composed ids of every example after the first of a row
 differ from the row-aligned ids on an allowed pair: the case cannot pass on row-aligned semantics."""
-import numpy as np
 import pytest
 import torch
 
-from oracle import attention as oa
 from oracle import side_inputs as si
-from tests.test_gpu_packed import BF16_TOL, DTYPES, F32_TOL, _inputs, _pattern, check_against
-from tests.test_image_grid_host import grid_mask
+from tests._cases import DTYPES, ENC_GRAD_TOL, ENC_TOL, composed, parity_inputs, runs_of
+from tests._parity import ACCUM_SEED, check_against, device_call, make_pattern, oracle_call, tiny_experiment
 
 pytestmark = pytest.mark.gpu
 
-
-def runs_of(row, S):
-  """Run lengths of a row: its examples and, if they do not fill it, the padding tail."""
-  row = [int(n) for n in row]
-  return row + ([S - sum(row)] if sum(row) < S else [])
-
-
-def single_example(L, radius, id_mode, m, P, r, grid, g0=0, ng=0):
-  """([L,L] mask, [L,L] ids | None) of one example alone at the start of a row of its own length.  A run shorter than the
-  image keeps the leading part of the ids of a P^2-long one (its positions below P^2 are image positions)."""
-  mask = si.sparse_pattern_mask(L, L, min(radius, L), g0, ng).astype(bool)
-  if grid:
-    mask = mask | grid_mask(L, grid[1], P, grid[0])
-  ids = None
-  if id_mode:
-    Lp = max(L, P * P) if id_mode == 2 else L
-    ids = si.relative_ids_from_desc(Lp, id_mode, m, P, r)[:L, :L]
-  return mask.astype(np.int32), ids
-
-
-def composed(lengths, S, radius, id_mode, m, P=0, r=0, grid=None, g0=0, ng=0):
-  B = len(lengths)
-  mask = np.zeros((B, S, S), np.int32)
-  rel = np.zeros((B, S, S), np.int32) if id_mode else None
-  for b, row in enumerate(lengths):
-    at = 0
-    for L in runs_of(row, S):
-      pm, pi = single_example(L, radius, id_mode, m, P, r, grid, g0, ng)
-      mask[b, at:at + L, at:at + L] = pm
-      if rel is not None:
-        rel[b, at:at + L, at:at + L] = pi
-      at += L
-  return mask, rel
+DROP_SEED = 4321
 
 
 def assert_differs_from_row_aligned(lengths, S, mask, rel, id_mode, m, P, r):
@@ -76,52 +41,27 @@ def layout(lengths, S):
 def run_origin(dtype, *, lengths, S, N=2, R, radius=1 << 30, id_mode=2, m, P=0, r=0, D=64, grid=None, g0=0, ng=0, seed=0,
                accum=False, scale_before_add=False, dropout=0.0, zero_starts=False, starts=True, oracle=True):
   """Structured (or, with global tokens, dense-route) call with example ids and starts, forward and backward through
-  autograd, against the composed oracle.  Returns (out, grads) as torch tensors."""
-  import mmt_amd
-  from mmt_amd import step_scalars
+  autograd, against the composed oracle.  Returns the device results."""
   ids, st = layout(lengths, S)
   if zero_starts:
     st = torch.zeros_like(st)
-  B = ids.shape[0]
   if oracle:
     mask, rel = composed(lengths, S, radius, id_mode, m, P, r, grid, g0, ng)
     if id_mode == 2:
       assert_differs_from_row_aligned(lengths, S, mask, rel, id_mode, m, P, r)
-  q, k, v, emb, bias, dout = _inputs(B, S, N, R, dtype, seed, D)
-  dev = lambda x, dt=dtype: torch.from_numpy(x).cuda().to(dt).contiguous()
-  tq, tk, tv, te, tb = (dev(x).requires_grad_(True) for x in (q, k, v, emb, bias))
-  gkw = dict(grid_radius=grid[0], grid_start=grid[1]) if grid else {}
-  pat = _pattern(radius, g0, ng, id_mode, m, P, r, **gkw)
-  kw = dict(pattern=pat, example_ids=ids.cuda(), scale_before_add=scale_before_add)
+  arrays = parity_inputs(ids.shape[0], S, N, R, dtype, seed, D)
+  a, g = grid or (0, 2)
+  kw = dict(pattern=make_pattern(radius=radius, g0=g0, ng=ng, id_mode=id_mode, m=m, P=P, r=r, a=a, g=g),
+            example_ids=ids.cuda(), scale_before_add=scale_before_add)
   if starts:
     kw['example_starts'] = st.cuda()
   if dropout:
-    kw.update(dropout_p=dropout, dropout_seed=4321)
-  out = mmt_amd.relative_attention(tq, tk, tv, te, tb, **kw)
-  seed_grads = {}
-  if accum:
-    seed_grads = {'drel_emb': np.full(emb.shape, 0.25, np.float32), 'drel_bias': np.full(bias.shape, -0.5, np.float32)}
-    demb, dbias = (torch.from_numpy(seed_grads[n]).cuda() for n in ('drel_emb', 'drel_bias'))
-    det = [t.detach() for t in (tq, tk, tv, te, tb)]
-    lse = mmt_amd.relative_attention_forward(*det, **kw)[1]
-    mmt_amd.relative_attention_backward(dev(dout), *det, out.detach(), lse, rel_grads_accum=(demb, dbias), **kw)
-  out.backward(dev(dout))
-  torch.cuda.synchronize()
-  t_out = out.detach().float()
-  t_grads = {n: t.grad.float() for n, t in (('dq', tq), ('dk', tk), ('dv', tv), ('drel_emb', te), ('drel_bias', tb))}
-  if accum:
-    t_grads['drel_emb'], t_grads['drel_bias'] = demb, dbias
+    kw.update(dropout_p=dropout, dropout_seed=DROP_SEED)
+  got = device_call(arrays, dtype, accum=accum, **kw)
   if oracle:
-    okw = dict(scale_after_add=not scale_before_add)
-    if dropout:
-      assert step_scalars.epoch_ptr(torch.device('cuda:0')) is None
-      dseed = (4321 + step_scalars.host_epoch(torch.device('cuda:0'))) & ((1 << 64) - 1)
-      keep, keep_prob = oa.dropout_keep_mask(B, N, S, dropout, dseed)
-      okw.update(keep_mask=keep, keep_prob=keep_prob)
-    ref, _ = oa.relative_attention_fwd(q, k, v, emb, bias, mask, rel, **okw)
-    want = oa.relative_attention_bwd(dout, q, k, v, emb, bias, mask, rel, **okw)
-    check_against(t_out.cpu().numpy(), {n: g.cpu().numpy() for n, g in t_grads.items()}, ref, want, dtype, seed_grads)
-  return t_out, t_grads
+    ref = oracle_call(arrays, mask, rel, scale_before_add=scale_before_add, dropout=(dropout, DROP_SEED) if dropout else None)
+    check_against(got, ref, dtype, seed_grads=ACCUM_SEED if accum else None)
+  return got
 
 
 FULL = dict(R=33, m=3, P=4, r=1, S=150, lengths=[[30, 45, 51, 24], [61, 18, 40, 31]])
@@ -163,11 +103,11 @@ def test_zero_starts_without_grid_equal_example_ids_alone_bitwise(id_mode):
   """Starts that are all zero make every local position the row position: the call computes, on kernels of the same
   code, what the call with `example_ids` alone computes -- fp32, bit for bit, forward and the five gradients."""
   cfg = dict(BAND, id_mode=id_mode, R=49 if id_mode == 2 else 32)
-  a_out, a_grads = run_origin(torch.float32, zero_starts=True, oracle=False, **cfg)
-  b_out, b_grads = run_origin(torch.float32, starts=False, oracle=False, **cfg)
-  assert torch.equal(a_out, b_out)
-  for n in b_grads:
-    assert torch.equal(a_grads[n], b_grads[n]), n
+  a = run_origin(torch.float32, zero_starts=True, oracle=False, **cfg)
+  b = run_origin(torch.float32, starts=False, oracle=False, **cfg)
+  assert a.keys() == b.keys() and len(b) == 6
+  for n in b:
+    assert torch.equal(a[n], b[n]), n
 
 
 @pytest.mark.parametrize('dtype', DTYPES, ids=['f32', 'bf16'])
@@ -186,7 +126,6 @@ ENC_S = 512
 def packed_model():
   """Tiny pretraining model (L = 2, H = 128, 2-D ids, P = 14) and one packed batch: four imaged examples in two rows."""
   import mmt_amd
-  from tests.test_gpu_encoder import tiny_experiment
   exp = tiny_experiment(S=256, core=2, R=49)
   task = mmt_amd.tasks.get_task(exp.task)
   torch.manual_seed(0)
@@ -226,7 +165,7 @@ def test_packed_encoder_rows_match_each_example_alone(packed_model):
                                 torch.ones(1, L, L, dtype=torch.int32), torch.from_numpy(rel)[None], pm['patches'][e:e + 1])
     err = float((got[b, at:at + L].double() - want[0]).abs().max())
     print(f'example {e}: max |packed - alone| = {err:.3e}')
-    assert err < 1e-3, (e, err)
+    assert err < ENC_TOL, (e, err)
 
 
 def test_packed_classification_logits_match_each_example_alone(packed_model):
@@ -244,14 +183,14 @@ def test_packed_classification_logits_match_each_example_alone(packed_model):
                   attention_pattern=pat, training=False)['itm_logits'].float().cpu()
     err = float((logits[e] - alone[0]).abs().max())
     print(f'example {e}: max |packed - alone| logits = {err:.3e}')
-    assert err < 1e-3, (e, err)
+    assert err < ENC_TOL, (e, err)
 
 
 def test_packed_embedding_gradients_fused_against_torch_branch():
   """The one-kernel assembly with `example_starts` / `patch_slots` (`mmt_embed_fwd_packed` / `mmt_embed_bwd_packed`)
   against the torch branch of `embed` on the same packed rows: output and the gradients of the word table, the position
   table (gathered by LOCAL position), the patch projection weight / bias (through the compact `dpatch` scatter) and the
-  LayerNorm, at test_gpu_encoder.py's fp32 tolerances (1e-3 output, 2e-3 of max |grad|).  Row 0 holds an example without
+  LayerNorm, at test_gpu_encoder.py's fp32 tolerances (ENC_TOL output, ENC_GRAD_TOL of max |grad|).  Row 0 holds an example without
   an image and an imaged one too short for its nine patches (the rest of its `dpatch` entry stays zero); both rows end
   in a padding tail."""
   import mmt_amd
@@ -286,9 +225,9 @@ def test_packed_embedding_gradients_fused_against_torch_branch():
   out_t, g_t = run(False)
   err = float((out_f - out_t).abs().max())
   print(f'max |fused - torch| = {err:.3e}')
-  assert err < 1e-3
+  assert err < ENC_TOL
   for n in names:
     assert float(g_t[n].abs().max()) > 0, n
     e = float((g_f[n] - g_t[n]).abs().max()) / max(1e-3, float(g_t[n].abs().max()))
     print(f'{n}: {e:.3e}')
-    assert e < 2e-3, (n, e)
+    assert e < ENC_GRAD_TOL, (n, e)

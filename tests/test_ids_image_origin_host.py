@@ -1,33 +1,17 @@
 """2-D relative ids at the image's position (`MMT_IDS_2D_IMAGE`, id_mode 3), host side: the numpy restatement the GPU
-tests feed the oracle, the library's argument checks (no GPU needed), the descriptor packing and the data-config key."""
+tests feed the oracle (tests/_cases.py `image_origin_ids`), the library's argument checks (no GPU needed), the
+descriptor packing and the data-config key."""
 import ctypes
 import glob
 import itertools
 import os
 import warnings
 
-import numpy as np
 import pytest
 
 import __graft_entry__  # noqa: F401  (sets sys.path)
 from oracle import side_inputs as si
-
-
-def image_origin_ids(S, m, P, r, g):
-  """[S,S] ids of id_mode 3 from its definition (include/mmt_attn.h): the reference generator's image x image block
-  placed at [g, g + P^2), text_part_id on image rows x other columns, image_part_id on other rows x image columns,
-  the 1-D clipped id of k - q (on sequence positions) everywhere else."""
-  I = P * P
-  gen = si.MmtRelativePositionGenerator(P, r, m)
-  block = gen.make_relative_att_ids(I, 1)[0]                     # [I,I]: the sequence is the image
-  image_part = I + 8 + 2 * m + 1
-  ids = si.RelativePositionGenerator1D(m).make_relative_att_ids(S, 1)[0].astype(np.int32).copy()
-  img = np.zeros(S, bool)
-  img[g:g + I] = True
-  ids[img, :] = image_part + 1                                   # text_part_id
-  ids[np.ix_(~img, img)] = image_part
-  ids[np.ix_(img, img)] = block
-  return ids
+from tests._cases import image_origin_ids
 
 
 @pytest.mark.parametrize('S,m,P,r,g', [(9, 12, 2, 1, 2), (40, 3, 5, 2, 7), (30, 4, 4, 1, 14)])

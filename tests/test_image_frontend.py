@@ -1,6 +1,6 @@
 """Image front end (mmt_amd/feature_pipeline.images_to_patch_features, C entry point mmt_image_patches) without a GPU.
 
-The yardstick is `restatement` below: float64 numpy, written from the reference's text (`decode_fn`,
+The yardstick is `restatement` (tests/_cases.py): float64 numpy, written from the reference's text (`decode_fn`,
 src/data/data_utils.py:195-222; MPP label ids :448-481) and independent of the torch and HIP code.  It keeps the
 reference's own order -- normalise, THEN resize (:204-205) -- while the product resizes once and normalises afterwards.
 The float half is unpinned: tensorflow is not installed where these tests were written, so tf.image.resize itself
@@ -11,84 +11,7 @@ import numpy as np
 import pytest
 import torch
 
-MEAN = np.array([0.485, 0.456, 0.406], dtype=np.float64)
-SOURCE_SIZES = [(1, 1), (5, 7), (37, 23), (64, 48)]          # + (image_size, image_size); see batch()
-CONFIGS = [(32, 16), (24, 8), (20, 8)]                       # (image_size, patch_size); 20 / 8: remainder dropped, P = 2
-EDGE_EPS = 1e-3                                              # ids: patches this close to a bin edge are left out
-SEED = 20211
-
-
-def _axis(n_in, n_out):
-  src = (np.arange(n_out, dtype=np.float64) + 0.5) * n_in / n_out - 0.5
-  fl = np.floor(src)
-  return np.maximum(fl, 0).astype(np.int64), np.minimum(np.ceil(src), n_in - 1).astype(np.int64), src - fl
-
-
-def resize_bilinear(x, size):
-  """tf.image.resize(x, [size, size]) with TF2 defaults, float64: half-pixel centres, no antialiasing, 2x2 taps;
-  horizontal lerp (top, bottom), then vertical."""
-  y0, y1, ty = _axis(x.shape[0], size)
-  x0, x1, tx = _axis(x.shape[1], size)
-  tx, ty = tx[None, :, None], ty[:, None, None]
-  top = x[y0][:, x0] + (x[y0][:, x1] - x[y0][:, x0]) * tx
-  bot = x[y1][:, x0] + (x[y1][:, x1] - x[y1][:, x0]) * tx
-  return top + (bot - top) * ty
-
-
-def patches(im, patch_size):
-  P = im.shape[0] // patch_size
-  im = im[:P * patch_size, :P * patch_size]
-  return im.reshape(P, patch_size, P, patch_size, 3).transpose(0, 2, 1, 3, 4).reshape(P * P, patch_size * patch_size * 3)
-
-
-def restatement(images, image_size, patch_size, flip=None, bits=0):
-  """The six steps for a list of uint8 [h, w, 3] arrays.  Returns normalised, unnormalised [B, P*P, E] float64, label
-  ids [B, P*P] (or None) and, per patch, the distance of the closest channel mean (x255) to a bin edge."""
-  norm, unnorm = [], []
-  for b, u8 in enumerate(images):
-    x = u8.astype(np.float64) / 255.0
-    n = resize_bilinear((x - MEAN) / MEAN, image_size)       # the reference's order: normalise, then resize
-    r = resize_bilinear(x, image_size)
-    if flip is not None and flip[b]:
-      n, r = n[:, ::-1], r[:, ::-1]
-    norm.append(patches(n, patch_size)); unnorm.append(patches(r, patch_size))
-  norm, unnorm = np.stack(norm), np.stack(unnorm)
-  ids = dist = None
-  if bits:
-    bin_size = 256 // 2 ** bits
-    avg = (unnorm * 255.0).reshape(*unnorm.shape[:2], patch_size * patch_size, 3).mean(-2)
-    digit = np.minimum(np.floor(avg / bin_size), 2 ** bits - 1).astype(np.int64)
-    ids = (digit * (2 ** bits) ** np.arange(3)).sum(-1).astype(np.int32)
-    dist = np.abs(avg / bin_size - np.round(avg / bin_size)).max(-1) * bin_size
-  return norm, unnorm, ids, dist
-
-
-def batch(image_size, seed=SEED):
-  rng = np.random.default_rng(seed)
-  return [rng.integers(0, 256, size=(h, w, 3), dtype=np.uint8) for h, w in SOURCE_SIZES + [(image_size, image_size)]]
-
-
-def check_outputs(out, images, image_size, patch_size, flip, bits, bf16=False):
-  """The issue's bounds: fp32 |out - ref| <= 1e-5 (three lerps and a scale, each at most one ulp on values <= 1.5,
-  amplified by 1 / 0.406: below 1e-6, ten times that allowed); bf16 |out - ref| <= 2^-8 |ref| + 1e-5; ids bit-equal
-  away from bin edges, with at most 2 % of the patches left out."""
-  norm, unnorm, ids, dist = restatement(images, image_size, patch_size, flip, bits)
-  got = out['patch_embeddings'].double().cpu().numpy()
-  assert got.shape == norm.shape
-  err = np.abs(got - norm)
-  print('normalised max err', err.max())
-  assert (err <= (2.0 ** -8 * np.abs(norm) + 1e-5 if bf16 else 1e-5)).all(), err.max()
-  if 'unnormalized_patch_embeddings' in out:
-    err = np.abs(out['unnormalized_patch_embeddings'].double().cpu().numpy() - unnorm).max()
-    print('unnormalised max err', err)
-    assert err <= 1e-5, err
-  if bits:
-    keep = dist > EDGE_EPS
-    print('patches left out', int((~keep).sum()), 'of', keep.size)
-    assert (~keep).mean() <= 0.02
-    assert np.array_equal(out['mpp_label_ids'].cpu().numpy()[keep], ids[keep])
-  P = image_size // patch_size
-  assert out['num_image_wordpieces'] == 2 + P * P
+from tests._cases import CONFIGS, EDGE_EPS, batch, check_outputs, patches, restatement
 
 
 def test_the_fixed_seed_keeps_the_restatement_within_the_edge_cap():

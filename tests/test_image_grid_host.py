@@ -1,5 +1,5 @@
 """Image-grid term of the structured pattern (SURVEY.md App. A.5 `grid_radius`), host side: the numpy restatement the
-GPU tests feed the oracle, the descriptor packing (`mmt_mask_desc.image_grid`, ABI 4), the library's argument errors
+GPU tests feed the oracle (tests/_cases.py `grid_mask`), the descriptor packing (`mmt_mask_desc.image_grid`, ABI 4), the library's argument errors
 (no GPU needed) and the data-config plumbing."""
 import ctypes
 import itertools
@@ -8,17 +8,7 @@ import numpy as np
 import pytest
 
 import __graft_entry__  # noqa: F401  (sets sys.path)
-
-
-def grid_mask(S, g, P, a):
-  """grid(q,k) of include/mmt_attn.h as an [S,S] bool array: both in the image [g, g + P^2), at most `a` image rows
-  and `a` columns apart (raster order, no wrap across rows)."""
-  pos = np.arange(S)
-  x = pos - g
-  img = (x >= 0) & (x < P * P)
-  row, col = np.where(img, x // P, 0), np.where(img, x % P, 0)
-  return (a > 0) & img[:, None] & img[None, :] & (np.abs(row[:, None] - row[None, :]) <= a) & \
-      (np.abs(col[:, None] - col[None, :]) <= a)
+from tests._cases import grid_mask
 
 
 @pytest.mark.parametrize('S,g,P,a', [(40, 2, 5, 1), (64, 2, 7, 2), (50, 0, 7, 3), (30, 5, 4, 0), (100, 3, 9, 8)])

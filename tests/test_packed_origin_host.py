@@ -10,7 +10,7 @@ import torch
 
 import __graft_entry__  # noqa: F401  (sets sys.path)
 from oracle import side_inputs as si
-from tests.test_image_grid_host import grid_mask
+from tests._cases import grid_mask
 
 
 @pytest.fixture(scope='module')

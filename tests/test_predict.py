@@ -57,7 +57,7 @@ def test_recall_at_k_matches_definition_and_handles_missing_pairs(tmp_path):
 def test_predict_runs_the_classification_model(tmp_path):
   import mmt_amd
   from mmt_amd import configs, predict as P
-  from tests.test_gpu_encoder import tiny_experiment
+  from tests._parity import tiny_experiment
   exp = tiny_experiment(S=256, radius=32, n_global=8)
   cexp = configs.get_exp_config('mmt/retrieval')
   cexp.override({'task': {'model': {'encoder': exp.task.model.encoder.as_dict(),

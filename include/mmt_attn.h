@@ -77,8 +77,17 @@ enum {
                                         numbers, never a stray access): rel_id(lq, lk), grid(lq, lk) -- an example sees what it would
                                         see alone at the start of a row.  Every run of equal ids is an example, a padding tail too;
                                         an id must name ONE run of its row (two runs sharing an id are undefined with starts).
-                                        Takes an image grid; n_global > 0 is MMT_E_UNSUPPORTED (per-example global tokens: dense
-                                        operator).  The general kernels; without the flag every call is what it was. */
+                                        Takes an image grid; n_global > 0 is MMT_E_UNSUPPORTED without MMT_FLAG_EXAMPLE_GLOBALS
+                                        (per-example global tokens).  The general kernels; without the flag every call is what it was. */
+#define MMT_FLAG_EXAMPLE_GLOBALS 16u /* per-example global tokens, with MMT_FLAG_EXAMPLE_IDS | MMT_FLAG_EXAMPLE_STARTS only (MMT_E_INVALID
+                                        otherwise): the contiguous range [global_start, global_start + n_global) is read at local
+                                        positions too, global(lq) || global(lk) -- every example has its global tokens where it would
+                                        have them alone at the start of a row.  An example shorter than global_start has none; one
+                                        that ends inside the range has its leading part.  Served by the structured (general) kernels,
+                                        with or without an image grid; a block that holds a global token walks its whole example.
+                                        With n_global == 0 the flag changes nothing.  A listed set (global_index) is refused as ever;
+                                        MMT_IDS_2D_IMAGE with n_global > 0 is MMT_E_UNSUPPORTED (dense operator).  Without the flag
+                                        every call is what it was. */
 
 /* Kernel-selection switches (mmt_attn_desc.tuning; ABI 4).  0 = the library's defaults.  They choose between kernels
  * that compute the same result (parity tests flip them to reach every kernel; they replace the MMT_* environment
@@ -102,7 +111,7 @@ enum {
  *   mask(q,k) = segmented(q,k) && (|q-k| <= local_radius || global(q) || global(k) || grid(q,k)),
  *   with MMT_FLAG_EXAMPLE_STARTS (lq = q - start[b,q], lk = k - start[b,k]):
  *   mask(q,k) = ids[b,q] == ids[b,k] && (|q-k| <= local_radius || global(lq) || global(lk) || grid(lq,lk)),
- *   rel_id(q,k) = rel_id(lq,lk)   (the structured kernels take n_global = 0 only there),
+ *   rel_id(q,k) = rel_id(lq,lk)   (the structured kernels take n_global > 0 there with MMT_FLAG_EXAMPLE_GLOBALS),
  *   global(x) = global_start <= x < global_start + n_global, or -- with global_index --
  *   x is one of the n_global listed positions.  The structured kernels take the contiguous
  *   form only; a listed set is served by materialising the mask (mmt_side_inputs with

@@ -18,7 +18,7 @@ int g_last_handover = 0;   // the last backward asked for the P hand-over
 const void* g_last_epoch = nullptr;   // the device epoch word the last attention launch was given
 int g_last_pack = 0;       // the last general forward / backward launch was asked for the PACK (example ids) instantiations
 int g_last_family = 0;     // the last backward launcher called: 0 the general kernels, 1 the lean ones
-int g_last_tu = 0;         // the last general forward / backward launcher called: 0 plain, 1 origin, 2 image translation unit
+int g_last_tu = 0;         // the last general forward / backward launcher called: 0 plain, 1 origin, 2 image, 3 globals translation unit
 char g_trace[4096] = "";   // every stand-in called since the last reset, with the routing fields it was given (route table only)
 int g_trace_len = -1;      // -1: not recording
 void stub_trace_reset(void) { g_trace[0] = 0; g_trace_len = 0; }
@@ -43,7 +43,7 @@ void trace(const char* fmt, ...) {
   if (n > 0) g_trace_len = std::min<int>(g_trace_len + n, sizeof(g_trace) - 1);
 }
 long off(const void* p) { return p ? (long)(static_cast<const unsigned char*>(p) - g_ws_lo) : -1; }   // workspace offset, -1 = NULL
-const char* const kTuName[] = {"plain", "origin", "image"};
+const char* const kTuName[] = {"plain", "origin", "image", "globals"};
 
 void kv(const char* key, long v, long dflt = 0) { if (v != dflt) trace(" %s=%ld", key, v); }   // fields at their default are left out
 
@@ -111,6 +111,7 @@ namespace mmt {
 hipError_t launch_attn_fwd(const FwdParams& p, int mode, bool bf16, int pack, hipStream_t) { return fwd_general(p, mode, bf16, pack, 0); }
 hipError_t launch_attn_fwd_origin(const FwdParams& p, int mode, bool bf16, int pack, hipStream_t) { return fwd_general(p, mode, bf16, pack, 1); }
 hipError_t launch_attn_fwd_image(const FwdParams& p, int mode, bool bf16, int pack, hipStream_t) { return fwd_general(p, mode, bf16, pack, 2); }
+hipError_t launch_attn_fwd_globals(const FwdParams& p, int mode, bool bf16, int pack, hipStream_t) { return fwd_general(p, mode, bf16, pack, 3); }
 hipError_t launch_attn_fwd_band_bf16(const FwdParams& p, hipStream_t) {
   ++g_launches; g_last_kind = 2; g_last_epoch = p.epoch; g_last_pack = 0;
   trace_fwd("fwd_lean", p);
@@ -158,6 +159,7 @@ hipError_t launch_rows_combine(const FwdParams& p, bool, hipStream_t) {
 hipError_t launch_attn_bwd(const BwdParams& p, int mode, bool bf16, int pack, hipStream_t) { return bwd_general(p, mode, bf16, pack, 0); }
 hipError_t launch_attn_bwd_origin(const BwdParams& p, int mode, bool bf16, int pack, hipStream_t) { return bwd_general(p, mode, bf16, pack, 1); }
 hipError_t launch_attn_bwd_image(const BwdParams& p, int mode, bool bf16, int pack, hipStream_t) { return bwd_general(p, mode, bf16, pack, 2); }
+hipError_t launch_attn_bwd_globals(const BwdParams& p, int mode, bool bf16, int pack, hipStream_t) { return bwd_general(p, mode, bf16, pack, 3); }
 hipError_t launch_attn_bwd_band_bf16(const BwdParams& p, hipStream_t) { g_last_family = 1; return bwd_any(p, "bwd_lean", 0); }
 hipError_t launch_side_inputs(const SideParams&, hipStream_t) { ++g_launches; g_last_kind = 6; return hipSuccess; }
 hipError_t launch_write_step_scalars(unsigned long long*, float*, unsigned long long, float, float, float, hipStream_t) { ++g_launches; g_last_kind = 7; return hipSuccess; }

@@ -71,8 +71,9 @@ __device__ __forceinline__ TileWalk band_walk(const PatternDev& pat, int x0, int
 // Mask bit and relative-table column of one (q,k) pair (col < 0: no relative term).
 // PACK (packed examples, kBand without a grid): the segmented term is `seg_ids`, the caller's compare of the two example ids.
 // ORG (per-example origin, PACK only): lq, lk = the two positions local to their example -- what rel_id and the grid term
-// read; the band and the 1-D column keep k - q (an allowed pair shares its start).  No global term (refused on the host).
-template <int MODE, bool GEN, bool GRID, bool PACK = false, bool ORG = false, typename P>
+// read; the band and the 1-D column keep k - q (an allowed pair shares its start).
+// GLB (per-example global tokens, ORG only): the global term on (lq, lk); without it ORG has no global term (n_global = 0).
+template <int MODE, bool GEN, bool GRID, bool PACK = false, bool ORG = false, bool GLB = false, typename P>
 __device__ __forceinline__ void pair_mask_col(const P& p, int b, int valid_len, int q, int k,
                                               bool& keep, int& col, bool seg_ids = false, int lq = 0, int lk = 0) {
   int id = -1;
@@ -83,7 +84,7 @@ __device__ __forceinline__ void pair_mask_col(const P& p, int b, int valid_len, 
     if (p.rel_ids) id = p.rel_ids[off];
     if ((unsigned)id < (unsigned)p.R) col = id;
   } else if (GEN) {
-    if constexpr (ORG) keep = pattern_mask_origin<GRID>(p.pat, p.grid, seg_ids, q, k, lq, lk);
+    if constexpr (ORG) keep = pattern_mask_origin<GRID, GLB>(p.pat, p.grid, seg_ids, q, k, lq, lk);
     else if constexpr (PACK) keep = pattern_mask_packed(p.pat, seg_ids, q, k);
     else keep = pattern_mask<GRID>(p.pat, p.grid, valid_len, q, k);
     if (p.pat.id_mode) id = ORG ? rel_id<kImageTU>(p.pat, lq, lk, p.ids_go) : rel_id<kImageTU>(p.pat, q, k, p.ids_go);
@@ -93,7 +94,8 @@ __device__ __forceinline__ void pair_mask_col(const P& p, int b, int valid_len, 
     const unsigned W = (unsigned)p.pat.radius;
     const bool near = (unsigned)(d + (int)W) <= 2u * W;
     const bool seg = PACK ? seg_ids : (k < valid_len) == (q < valid_len);
-    if constexpr (ORG) keep = (int)seg & ((int)near | (int)(GRID && in_grid(p.pat, p.grid, lq, lk)));
+    if constexpr (GLB) keep = (int)seg & ((int)near | (int)is_global(p.pat, lk) | (int)is_global(p.pat, lq) | (int)(GRID && in_grid(p.pat, p.grid, lq, lk)));
+    else if constexpr (ORG) keep = (int)seg & ((int)near | (int)(GRID && in_grid(p.pat, p.grid, lq, lk)));
     else keep = (int)seg & ((int)near | (int)is_global(p.pat, k) | (int)is_global(p.pat, q) | (int)(GRID && in_grid(p.pat, p.grid, q, k)));
     if (p.pat.id_mode == 1) col = min(max(d, -p.pat.m), p.pat.m) + p.pat.m;
   }
@@ -165,7 +167,9 @@ __device__ __forceinline__ void build_table(const P& p, int n, const Frag<T, DH>
 // row block's range.  A chunk of the global rows with no tile left writes zero partials, which the combine sums.
 // ORG: as attn_fwd_kernel -- p.valid_len names [B,2,S] ids and starts, ids and grid term on local positions (so the table
 // gradients are bucketed by the local id), the same two walks with a grid; attn_bwd_origin.hip.
-template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH, bool PACK = false, bool ORG = false>
+// GLB: as attn_fwd_kernel -- per-example global tokens, no split items: a block with a global row walks its example(s)
+// whole, any other block the union / span around its rows' global ranges; attn_bwd_globals.hip.
+template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH, bool PACK = false, bool ORG = false, bool GLB = false>
 __global__ __launch_bounds__(256, (sizeof(T) == 2 && DH == 64 ? 2 : 1)) void attn_bwd_dq_kernel(const BwdParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x & 63;
@@ -204,7 +208,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && DH == 64 ? 2 : 1)) void att
   const unsigned qc = (unsigned)min(q, p.S - 1);
   const int valid_len = PACK ? 0 : (p.valid_len ? p.valid_len[b] : p.S);
   constexpr bool CUR = GRID || PACK;      // the walk is a cursor (t_cur, t_nxt), not a count
-  constexpr bool OG = ORG && GRID;        // origin + grid: GridWalk (one example in the rows) or PackWalk over the row
+  constexpr bool OG = ORG && (GRID || GLB);   // origin + grid / per-example globals: GridWalk (one example in the rows) or PackWalk over the row
   const T* Q = reinterpret_cast<const T*>(p.q) + (long)b * p.qs[0] + (long)n * p.qs[2];
   const T* K = reinterpret_cast<const T*>(p.k) + (long)b * p.ks[0] + (long)n * p.ks[2];
   const T* V = reinterpret_cast<const T*>(p.v) + (long)b * p.vs[0] + (long)n * p.vs[2];
@@ -244,12 +248,25 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && DH == 64 ? 2 : 1)) void att
     if constexpr (OG) {
       const int st0 = __builtin_amdgcn_readfirstlane(qst);
       one_ex = pw.lo == pw.hi && __all(qst == st0);
+      bool grow = false;                       // GLB: the block holds a global token -- it sees its whole example
+      if constexpr (GLB) {
+        grow = __any(q_ok && is_global(p.pat, lq));      // (rows past S take the last row's start: not rows)
+        one_ex = one_ex && !grow;
+      }
       if (one_ex) {
         int t_hi;
         gw.init_origin(p.pat, p.grid, q0, p.S, st0);
+        if constexpr (GLB) gw.init_origin_globals(p.pat, p.S, st0);
         gw.span(w.b0, t_hi);
         w.lenB = t_hi - w.b0 + 1;
         pw.n_it = w.lenB;
+      } else if constexpr (GLB && !GRID) {
+        if (!grow) {
+          int t_hi;
+          pw.span_globals(p.pat, q0, qst, w.b0, t_hi);
+          w.lenB = t_hi - w.b0 + 1;
+          pw.n_it = w.lenB;
+        }
       }
       t_cur = og_next();
     } else {
@@ -334,7 +351,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && DH == 64 ? 2 : 1)) void att
     for (int i = 0; i < 16; ++i) {
       const int kk = k0 + kap(i, h);
       bool keep;
-      if constexpr (ORG) pair_mask_col<MODE, GEN, GRID, true, true>(p, b, valid_len, q, kk, keep, cols[i], __shfl(kid, kap(i, h), 64) == qid,
+      if constexpr (ORG) pair_mask_col<MODE, GEN, GRID, true, true, GLB>(p, b, valid_len, q, kk, keep, cols[i], __shfl(kid, kap(i, h), 64) == qid,
                                                                     lq, local_pos(kk, __shfl(kst, kap(i, h), 64), p.S));
       else if constexpr (PACK) pair_mask_col<MODE, GEN, GRID, true>(p, b, valid_len, q, kk, keep, cols[i], __shfl(kid, kap(i, h), 64) == qid);
       else pair_mask_col<MODE, GEN, GRID>(p, b, valid_len, q, kk, keep, cols[i]);
@@ -513,7 +530,9 @@ __global__ __launch_bounds__(DH) void attn_bwd_dq_combine_kernel(const BwdParams
 // ones do, whose figures are kept as they were).  So are the DH = 128 ones (dk2, dk3, dv2, dv3: head dims 64 .. 127).
 // PACK: the same walk over query tiles against the key block's id range (the pattern is symmetric); built like the GRID ones.
 // ORG: likewise -- the key's start and local position on the lane, start r of the current / next query tile by shuffle.
-template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH, bool PACK = false, bool ORG = false>
+// GLB: the dQ pass's rule with keys and queries swapped (the pattern is symmetric): a key block that holds a global key
+// walks every query tile of its example(s), ascending -- the dK / dV sums keep one fixed order.
+template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH, bool PACK = false, bool ORG = false, bool GLB = false>
 __global__ __launch_bounds__(256, ((sizeof(T) == 2 && !GRID && !PACK && DH == 64) ? 2 : 1)) void attn_bwd_dkv_kernel(const BwdParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x & 63;
@@ -551,7 +570,7 @@ __global__ __launch_bounds__(256, ((sizeof(T) == 2 && !GRID && !PACK && DH == 64
   const unsigned kc = (unsigned)min(k, p.S - 1);
   const int valid_len = PACK ? 0 : (p.valid_len ? p.valid_len[b] : p.S);
   constexpr bool CUR = GRID || PACK;      // the walk is a cursor (t_cur, t_nxt), not a count
-  constexpr bool OG = ORG && GRID;        // origin + grid: GridWalk (one example in the keys) or PackWalk over the row
+  constexpr bool OG = ORG && (GRID || GLB);   // origin + grid / per-example globals: GridWalk (one example in the keys) or PackWalk over the row
   const T* Q = reinterpret_cast<const T*>(p.q) + (long)b * p.qs[0] + (long)n * p.qs[2];
   const T* K = reinterpret_cast<const T*>(p.k) + (long)b * p.ks[0] + (long)n * p.ks[2];
   const T* V = reinterpret_cast<const T*>(p.v) + (long)b * p.vs[0] + (long)n * p.vs[2];
@@ -592,12 +611,25 @@ __global__ __launch_bounds__(256, ((sizeof(T) == 2 && !GRID && !PACK && DH == 64
     if constexpr (OG) {
       const int st0 = __builtin_amdgcn_readfirstlane(kst);
       one_ex = pw.lo == pw.hi && __all(kst == st0);
+      bool grow = false;                       // GLB: the block holds a global token -- it sees its whole example
+      if constexpr (GLB) {
+        grow = __any(k_ok && is_global(p.pat, lk));      // (keys past S likewise)
+        one_ex = one_ex && !grow;
+      }
       if (one_ex) {
         int t_hi;
         gw.init_origin(p.pat, p.grid, k0, p.S, st0);
+        if constexpr (GLB) gw.init_origin_globals(p.pat, p.S, st0);
         gw.span(w.b0, t_hi);
         w.lenB = t_hi - w.b0 + 1;
         pw.n_it = w.lenB;
+      } else if constexpr (GLB && !GRID) {
+        if (!grow) {
+          int t_hi;
+          pw.span_globals(p.pat, k0, kst, w.b0, t_hi);
+          w.lenB = t_hi - w.b0 + 1;
+          pw.n_it = w.lenB;
+        }
       }
       t_cur = og_next();
     } else {
@@ -665,7 +697,7 @@ __global__ __launch_bounds__(256, ((sizeof(T) == 2 && !GRID && !PACK && DH == 64
     for (int i = 0; i < 16; ++i) {
       const int qq = q0 + kap(i, h);
       bool keep;
-      if constexpr (ORG) pair_mask_col<MODE, GEN, GRID, true, true>(p, b, valid_len, qq, k, keep, cols[i], __shfl(qid, kap(i, h), 64) == kid,
+      if constexpr (ORG) pair_mask_col<MODE, GEN, GRID, true, true, GLB>(p, b, valid_len, qq, k, keep, cols[i], __shfl(qid, kap(i, h), 64) == kid,
                                                                     local_pos(qq, __shfl(qst, kap(i, h), 64), p.S), lk);
       else if constexpr (PACK) pair_mask_col<MODE, GEN, GRID, true>(p, b, valid_len, qq, k, keep, cols[i], __shfl(qid, kap(i, h), 64) == kid);
       else pair_mask_col<MODE, GEN, GRID>(p, b, valid_len, qq, k, keep, cols[i]);
@@ -843,7 +875,7 @@ static void allow_lds(K kernel, int bytes) {
                                                    hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
-template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH, bool PACK, bool ORG>
+template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH, bool PACK, bool ORG, bool GLB>
 static hipError_t launch_bwd_one(const BwdParams& p_in, hipStream_t st) {
   BwdParams p = p_in;
   p.red_per_plane = ((p.S + 127) >> 7) * 4;               // one dE partial per wave (32 rows)
@@ -851,16 +883,16 @@ static hipError_t launch_bwd_one(const BwdParams& p_in, hipStream_t st) {
   const int per_bn = (p.n_chunks * p.n_gblk + 3) / 4;
   dim3 grid(p.n_band_blocks + (MODE == kBand ? per_bn * p.B * p.N : 0));
   const int lds_a = 4 * BwdLds<T, Rp, DH>::kDq, lds_b = 4 * BwdLds<T, Rp, DH>::kDkv;
-  allow_lds(attn_bwd_dq_kernel<T, MODE, Rp, GEN, GRID, DH, PACK, ORG>, lds_a);
-  allow_lds(attn_bwd_dkv_kernel<T, MODE, Rp, GEN, GRID, DH, PACK, ORG>, lds_b);
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<T, MODE, Rp, GEN, GRID, DH, PACK, ORG>), grid, dim3(256), lds_a, st, p);
+  allow_lds(attn_bwd_dq_kernel<T, MODE, Rp, GEN, GRID, DH, PACK, ORG, GLB>, lds_a);
+  allow_lds(attn_bwd_dkv_kernel<T, MODE, Rp, GEN, GRID, DH, PACK, ORG, GLB>, lds_b);
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<T, MODE, Rp, GEN, GRID, DH, PACK, ORG, GLB>), grid, dim3(256), lds_a, st, p);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (MODE == kBand && p.n_gblk > 0) {
     hipLaunchKernelGGL((attn_bwd_dq_combine_kernel<T, DH>), dim3(p.pat.ng, p.B * p.N), dim3(DH), 0, st, p);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
-  hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, MODE, Rp, GEN, GRID, DH, PACK, ORG>), grid, dim3(256), lds_b, st, p);
+  hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, MODE, Rp, GEN, GRID, DH, PACK, ORG, GLB>), grid, dim3(256), lds_b, st, p);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if (MODE == kBand && p.n_gblk > 0) {
     hipLaunchKernelGGL((attn_bwd_dkv_combine_kernel<T, DH>), dim3(p.pat.ng, p.B * p.N), dim3(DH), 0, st, p);
@@ -873,27 +905,27 @@ static hipError_t launch_bwd_one(const BwdParams& p_in, hipStream_t st) {
   return e;
 }
 
-template <typename T, int MODE, bool GEN, bool GRID, int DH, bool PACK = false, bool ORG = false>
+template <typename T, int MODE, bool GEN, bool GRID, int DH, bool PACK = false, bool ORG = false, bool GLB = false>
 static hipError_t launch_bwd_rp(const BwdParams& p, hipStream_t st) {
-  if (p.Rp == 32) return launch_bwd_one<T, MODE, 32, GEN, GRID, DH, PACK, ORG>(p, st);
-  if (p.Rp == 64) return launch_bwd_one<T, MODE, 64, GEN, GRID, DH, PACK, ORG>(p, st);
-  return launch_bwd_one<T, MODE, 128, GEN, GRID, DH, PACK, ORG>(p, st);
+  if (p.Rp == 32) return launch_bwd_one<T, MODE, 32, GEN, GRID, DH, PACK, ORG, GLB>(p, st);
+  if (p.Rp == 64) return launch_bwd_one<T, MODE, 64, GEN, GRID, DH, PACK, ORG, GLB>(p, st);
+  return launch_bwd_one<T, MODE, 128, GEN, GRID, DH, PACK, ORG, GLB>(p, st);
 }
 
 // GEN and GRID of one (PACK, ORG) pair, as far as this translation unit holds them: as attn_fwd.hip's launch_band
-template <typename T, int DH, bool PACK, bool ORG, bool GRIDS>
+template <typename T, int DH, bool PACK, bool ORG, bool GRIDS, bool GLB = false>
 static hipError_t launch_bwd_band(const BwdParams& p, hipStream_t st) {
   const bool table = kTu.table_ids && (p.pat.id_mode == 0 || p.perm_1d), grd = GRIDS && p.grid.ga > 0;
-  if constexpr (kTu.table_ids && GRIDS) if (table && grd) return launch_bwd_rp<T, kBand, false, true, DH, PACK, ORG>(p, st);
-  if constexpr (kTu.table_ids) if (table) return launch_bwd_rp<T, kBand, false, false, DH, PACK, ORG>(p, st);
-  if constexpr (GRIDS) if (grd) return launch_bwd_rp<T, kBand, true, true, DH, PACK, ORG>(p, st);      // image grid: its own instantiations
-  return launch_bwd_rp<T, kBand, true, false, DH, PACK, ORG>(p, st);
+  if constexpr (kTu.table_ids && GRIDS) if (table && grd) return launch_bwd_rp<T, kBand, false, true, DH, PACK, ORG, GLB>(p, st);
+  if constexpr (kTu.table_ids) if (table) return launch_bwd_rp<T, kBand, false, false, DH, PACK, ORG, GLB>(p, st);
+  if constexpr (GRIDS) if (grd) return launch_bwd_rp<T, kBand, true, true, DH, PACK, ORG, GLB>(p, st);      // image grid: its own instantiations
+  return launch_bwd_rp<T, kBand, true, false, DH, PACK, ORG, GLB>(p, st);
 }
 
 template <typename T, int DH>
 static hipError_t launch_bwd_t(const BwdParams& p, int mode, int pack, hipStream_t st) {
   if constexpr (kTu.dense) if (mode == kDense) return launch_bwd_rp<T, kDense, true, false, DH>(p, st);
-  if constexpr (kTu.pack_origin) if (pack == kPackOrigin) return launch_bwd_band<T, DH, true, true, true>(p, st);
+  if constexpr (kTu.pack_origin) if (pack == kPackOrigin) return launch_bwd_band<T, DH, true, true, true, kTu.globals>(p, st);
   if constexpr (kTu.pack_ids) if (pack == kPackIds) return launch_bwd_band<T, DH, true, false, false>(p, st);
   if constexpr (kTu.pack_none) if (pack == kPackNone) return launch_bwd_band<T, DH, false, false, true>(p, st);
   return hipErrorInvalidValue;
@@ -905,7 +937,7 @@ hipError_t MMT_TU(launch_attn_bwd)(const BwdParams& p, int mode, bool bf16, int 
   return bf16 ? launch_bwd_t<__bf16, 64>(p, mode, pack, st) : launch_bwd_t<float, 64>(p, mode, pack, st);
 }
 
-#if !defined(MMT_IMAGE_TU) && !defined(MMT_ORIGIN_TU)
+#if !defined(MMT_IMAGE_TU) && !defined(MMT_ORIGIN_TU) && !defined(MMT_GLOBALS_TU)
 // the lean path's stand-alone combine / reduce launches (attn_bwd_band.hip): head size 64 only
 hipError_t launch_bwd_dq_combine(const BwdParams& p, bool bf16, hipStream_t st) {
   dim3 grid(p.pat.ng, p.B * p.N);

@@ -45,10 +45,21 @@ constexpr bool kImageTU = false;
 // eight at a time by the id-range test -- over the span of GridWalk's union around the example's image, keeping the
 // tiles of that union, for a block whose 32 rows lie in one example (so the walk is cut to the example: with ids that
 // name one run each, nothing outside it passes the test), and over every tile of the row for a block that straddles
-// examples.  No global tokens (refused on the host), hence no rows items.
+// examples.  No rows items: n_global > 0 comes with GLB only.
+// GLB = true (ORG only; attn_fwd_globals.hip, MMT_FLAG_EXAMPLE_GLOBALS): per-example global tokens -- the global term reads
+// local positions, global(lq) || global(lk).  Per-example global rows are scattered over the row, so there are no rows items
+// and no split-rows plan; the band item walks, with or without a grid, the way the ORG + GRID forms do:
+//   a row of the block is a global row  -> every tile of the row is a candidate, the id-range test cuts the walk to the
+//                                          block's example(s), which it walks whole;
+//   else, one example in the block      -> GridWalk's union (band, the tiles of [start + g0, start + g0 + ng), grid
+//                                          intervals) over its span, kept where has() names the tile;
+//   else (several examples)             -> the tiles from the lowest to the highest that any row's band or global range
+//                                          touches (PackWalk::span_globals; with a grid the whole row), id-range filtered.
+// Candidates ascend and each is judged once: no tile is visited twice.  All three are supersets of the allowed pairs;
+// the element test decides.  GLB = false instantiations are the kernels as before.
 // The ORG bf16 head-size-64 forms are held to two workgroups per CU (256 VGPRs): left to itself the allocator takes 260 for
 // some of them and halves the occupancy (207 -> 363 us at 16 x 256, 2-D ids).
-template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH, bool PACK = false, bool ORG = false>
+template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH, bool PACK = false, bool ORG = false, bool GLB = false>
 __global__ __launch_bounds__(256, (ORG && sizeof(T) == 2 && DH == 64) ? 2 : 1) void attn_fwd_kernel(const FwdParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x & 63;
@@ -83,7 +94,7 @@ __global__ __launch_bounds__(256, (ORG && sizeof(T) == 2 && DH == 64) ? 2 : 1) v
   const bool q_ok = q < p.S;
   const int valid_len = PACK ? 0 : (p.valid_len ? p.valid_len[b] : p.S);
   constexpr bool CUR = GRID || PACK;      // the walk is a cursor (t_cur, t_nxt), not a count
-  constexpr bool OG = ORG && GRID;        // origin + grid: GridWalk (one example in the rows) or PackWalk over the row
+  constexpr bool OG = ORG && (GRID || GLB);   // origin + grid / per-example globals: GridWalk (one example in the rows) or PackWalk over the row
 
   const T* Q = reinterpret_cast<const T*>(p.q) + (long)b * p.qs[0] + (long)n * p.qs[2];
   const T* K = reinterpret_cast<const T*>(p.k) + (long)b * p.ks[0] + (long)n * p.ks[2];
@@ -146,12 +157,25 @@ __global__ __launch_bounds__(256, (ORG && sizeof(T) == 2 && DH == 64) ? 2 : 1) v
     if constexpr (OG) {
       const int st0 = __builtin_amdgcn_readfirstlane(qst);
       one_ex = pw.lo == pw.hi && __all(qst == st0);
+      bool grow = false;                       // GLB: a row of the block is a global row -- it sees its whole example
+      if constexpr (GLB) {
+        grow = __any(q_ok && is_global(p.pat, lq));      // (rows past S take the last row's start: not rows)
+        one_ex = one_ex && !grow;
+      }
       if (one_ex) {
         int t_hi;
         gw.init_origin(p.pat, p.grid, q0, p.S, st0);
+        if constexpr (GLB) gw.init_origin_globals(p.pat, p.S, st0);
         gw.span(b0, t_hi);
         lenB = t_hi - b0 + 1;
         pw.n_it = lenB;
+      } else if constexpr (GLB && !GRID) {
+        if (!grow) {
+          int t_hi;
+          pw.span_globals(p.pat, q0, qst, b0, t_hi);
+          lenB = t_hi - b0 + 1;
+          pw.n_it = lenB;
+        }
       }
       t_cur = og_next();
     } else {
@@ -205,7 +229,8 @@ __global__ __launch_bounds__(256, (ORG && sizeof(T) == 2 && DH == 64) ? 2 : 1) v
   const float* trow = tab + r * kTStride(Rp);
   // whole q-block on one side of valid_len?  (needed for the fast path)
   const bool qblk_valid = q0 + 31 < valid_len, qblk_pad = q0 >= valid_len;
-  const bool qblk_plain = q0 + 31 < p.S && !(p.pat.ng > 0 && q0 + 31 >= p.pat.g0 && q0 < p.pat.g0 + p.pat.ng);
+  // (GLB: a tile the fast path takes lies inside one example and inside the band -- every pair is allowed, global or not)
+  const bool qblk_plain = q0 + 31 < p.S && (GLB || !(p.pat.ng > 0 && q0 + 31 >= p.pat.g0 && q0 < p.pat.g0 + p.pat.ng));
 
   for (int it = 0; CUR ? t_cur != GridWalk::kEnd : it < n_it; ++it, t_cur = t_nxt, kid = kid_nxt, kst = kst_nxt) {
     const int k0 = (CUR ? t_cur : tile_at(it)) * 32;
@@ -258,7 +283,7 @@ __global__ __launch_bounds__(256, (ORG && sizeof(T) == 2 && DH == 64) ? 2 : 1) v
       // branch-free pattern mask, 1-D (permuted table) or no ids
       const int kb = k0 + 4 * h, d0 = kb - q;
       const unsigned W = (unsigned)p.pat.radius;
-      const bool qv = q < valid_len, gq = is_global(p.pat, q);
+      const bool qv = q < valid_len, gq = is_global(p.pat, GLB ? lq : q);
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int ci = (i & 3) + 8 * (i >> 2);
@@ -267,7 +292,11 @@ __global__ __launch_bounds__(256, (ORG && sizeof(T) == 2 && DH == 64) ? 2 : 1) v
         const bool gk = (unsigned)(kk - p.pat.g0) < (unsigned)p.pat.ng;
         const bool seg = PACK ? __shfl(kid, 4 * h + ci, 64) == qid : (kk < valid_len) == qv;
         bool keep;
-        if constexpr (ORG) keep = (int)seg & ((int)near | (int)(GRID && in_grid(p.pat, p.grid, lq, local_pos(kk, __shfl(kst, 4 * h + ci, 64), p.S))));
+        if constexpr (GLB) {
+          const int lk = local_pos(kk, __shfl(kst, 4 * h + ci, 64), p.S);
+          keep = (int)seg & ((int)near | (int)gq | (int)is_global(p.pat, lk) | (int)(GRID && in_grid(p.pat, p.grid, lq, lk)));
+        }
+        else if constexpr (ORG) keep = (int)seg & ((int)near | (int)(GRID && in_grid(p.pat, p.grid, lq, local_pos(kk, __shfl(kst, 4 * h + ci, 64), p.S))));
         else keep = (int)seg & ((int)near | (int)gk | (int)gq | (int)(GRID && in_grid(p.pat, p.grid, q, kk)));
         float rel = 0.f;
         if (id_mode == 1) rel = trow[min(max(d, -mdist), mdist) + mdist];
@@ -290,7 +319,7 @@ __global__ __launch_bounds__(256, (ORG && sizeof(T) == 2 && DH == 64) ? 2 : 1) v
         } else {
           int lk = kk;
           if constexpr (ORG) lk = local_pos(kk, __shfl(kst, kap(i, h), 64), p.S);
-          if constexpr (ORG) keep = pattern_mask_origin<GRID>(p.pat, p.grid, __shfl(kid, kap(i, h), 64) == qid, q, kk, lq, lk);
+          if constexpr (ORG) keep = pattern_mask_origin<GRID, GLB>(p.pat, p.grid, __shfl(kid, kap(i, h), 64) == qid, q, kk, lq, lk);
           else if constexpr (PACK) keep = pattern_mask_packed(p.pat, __shfl(kid, kap(i, h), 64) == qid, q, kk);
           else keep = pattern_mask<GRID>(p.pat, p.grid, valid_len, q, kk);
           if (id_mode) id = ORG ? rel_id<kImageTU>(p.pat, lq, lk, p.ids_go) : rel_id<kImageTU>(p.pat, q, kk, p.ids_go);
@@ -449,37 +478,37 @@ __global__ __launch_bounds__(DH) void attn_rows_combine_kernel(const FwdParams p
 }
 
 // ------------------------------------ launchers -----------------------------------------
-template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH, bool PACK, bool ORG>
+template <typename T, int MODE, int Rp, bool GEN, bool GRID, int DH, bool PACK, bool ORG, bool GLB>
 static hipError_t launch_one(const FwdParams& p, dim3 grid, hipStream_t st) {
   const int lds = 4 * WaveLds<T, Rp, DH>::kBytes;
   if (lds > 64 * 1024)               // (the 128-wide table: relative vocabularies of 65..128 ids; DH = 128 from Rp = 64)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<T, MODE, Rp, GEN, GRID, DH, PACK, ORG>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  hipLaunchKernelGGL((attn_fwd_kernel<T, MODE, Rp, GEN, GRID, DH, PACK, ORG>), grid, dim3(256), lds, st, p);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<T, MODE, Rp, GEN, GRID, DH, PACK, ORG, GLB>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  hipLaunchKernelGGL((attn_fwd_kernel<T, MODE, Rp, GEN, GRID, DH, PACK, ORG, GLB>), grid, dim3(256), lds, st, p);
   return hipGetLastError();
 }
 
-template <typename T, int MODE, bool GEN, bool GRID, int DH, bool PACK = false, bool ORG = false>
+template <typename T, int MODE, bool GEN, bool GRID, int DH, bool PACK = false, bool ORG = false, bool GLB = false>
 static hipError_t launch_rp(const FwdParams& p, dim3 grid, hipStream_t st) {
-  if (p.R <= 32) return launch_one<T, MODE, 32, GEN, GRID, DH, PACK, ORG>(p, grid, st);
-  if (p.R <= 64) return launch_one<T, MODE, 64, GEN, GRID, DH, PACK, ORG>(p, grid, st);
-  return launch_one<T, MODE, 128, GEN, GRID, DH, PACK, ORG>(p, grid, st);
+  if (p.R <= 32) return launch_one<T, MODE, 32, GEN, GRID, DH, PACK, ORG, GLB>(p, grid, st);
+  if (p.R <= 64) return launch_one<T, MODE, 64, GEN, GRID, DH, PACK, ORG, GLB>(p, grid, st);
+  return launch_one<T, MODE, 128, GEN, GRID, DH, PACK, ORG, GLB>(p, grid, st);
 }
 
 // GEN and GRID of one (PACK, ORG) pair, as far as this translation unit holds them (kTu, attn_kernels.h).  GRIDS = false:
 // the pair has no GRID instantiation (example ids never come with a grid: refused on the host).
-template <typename T, int DH, bool PACK, bool ORG, bool GRIDS>
+template <typename T, int DH, bool PACK, bool ORG, bool GRIDS, bool GLB = false>
 static hipError_t launch_band(const FwdParams& p, dim3 grid, hipStream_t st) {
   const bool table = kTu.table_ids && (p.pat.id_mode == 0 || p.perm_1d), grd = GRIDS && p.grid.ga > 0;
-  if constexpr (kTu.table_ids && GRIDS) if (table && grd) return launch_rp<T, kBand, false, true, DH, PACK, ORG>(p, grid, st);
-  if constexpr (kTu.table_ids) if (table) return launch_rp<T, kBand, false, false, DH, PACK, ORG>(p, grid, st);
-  if constexpr (GRIDS) if (grd) return launch_rp<T, kBand, true, true, DH, PACK, ORG>(p, grid, st);      // image grid: its own instantiations
-  return launch_rp<T, kBand, true, false, DH, PACK, ORG>(p, grid, st);
+  if constexpr (kTu.table_ids && GRIDS) if (table && grd) return launch_rp<T, kBand, false, true, DH, PACK, ORG, GLB>(p, grid, st);
+  if constexpr (kTu.table_ids) if (table) return launch_rp<T, kBand, false, false, DH, PACK, ORG, GLB>(p, grid, st);
+  if constexpr (GRIDS) if (grd) return launch_rp<T, kBand, true, true, DH, PACK, ORG, GLB>(p, grid, st);      // image grid: its own instantiations
+  return launch_rp<T, kBand, true, false, DH, PACK, ORG, GLB>(p, grid, st);
 }
 
 template <typename T, int DH>
 static hipError_t launch_t(const FwdParams& p, int mode, int pack, dim3 grid, hipStream_t st) {
   if constexpr (kTu.dense) if (mode == kDense) return launch_rp<T, kDense, true, false, DH>(p, grid, st);
-  if constexpr (kTu.pack_origin) if (pack == kPackOrigin) return launch_band<T, DH, true, true, true>(p, grid, st);
+  if constexpr (kTu.pack_origin) if (pack == kPackOrigin) return launch_band<T, DH, true, true, true, kTu.globals>(p, grid, st);
   if constexpr (kTu.pack_ids) if (pack == kPackIds) return launch_band<T, DH, true, false, false>(p, grid, st);
   if constexpr (kTu.pack_none) if (pack == kPackNone) return launch_band<T, DH, false, false, true>(p, grid, st);
   return hipErrorInvalidValue;
@@ -493,7 +522,7 @@ hipError_t MMT_TU(launch_attn_fwd)(const FwdParams& p, int mode, bool bf16, int 
   return bf16 ? launch_t<__bf16, 64>(p, mode, pack, grid, st) : launch_t<float, 64>(p, mode, pack, grid, st);
 }
 
-#if !defined(MMT_IMAGE_TU) && !defined(MMT_ORIGIN_TU)
+#if !defined(MMT_IMAGE_TU) && !defined(MMT_ORIGIN_TU) && !defined(MMT_GLOBALS_TU)
 template <int DH>
 static hipError_t launch_rows_combine_dh(const FwdParams& p, bool bf16, hipStream_t st) {
   dim3 grid(p.pat.ng, p.B * p.N);

@@ -55,22 +55,27 @@ struct FwdParams {
 // pack (the general launchers): the PACK instantiations -- p.valid_len holds example ids [B,S] (kPackIds), or ids and example
 // starts [B,2,S] (kPackOrigin: the ORG instantiations).  A launcher argument, not a field: the parameter blocks stay what they were.
 enum { kPackNone = 0, kPackIds = 1, kPackOrigin = 2 };
-// The general kernels are three translation units per direction (attn_fwd.hip / attn_bwd.hip alone, and compiled again as
-// .._origin.hip and .._image.hip), each with the same launcher under its own name; the host's route (mmt_api.hip) names the unit.
-struct TuSet { bool dense, table_ids, pack_none, pack_ids, pack_origin; };   // table_ids: GEN = false (no ids, permuted 1-D table) beside GEN = true
+// The general kernels are four translation units per direction (attn_fwd.hip / attn_bwd.hip alone, and compiled again as
+// .._origin.hip, .._image.hip and .._globals.hip), each with the same launcher under its own name; the host's route
+// (mmt_api.hip) names the unit.
+struct TuSet { bool dense, table_ids, pack_none, pack_ids, pack_origin, globals; };   // table_ids: GEN = false (no ids, permuted 1-D table) beside GEN = true; globals: the pack_origin forms are the GLB ones
 #if defined(MMT_IMAGE_TU)         // MMT_IDS_2D_IMAGE away from origin 0: the ids are generated, with every kind of packing
-constexpr TuSet kTu = {false, false, true, true, true};
+constexpr TuSet kTu = {false, false, true, true, true, false};
 #define MMT_TU(launcher) launcher##_image
 #elif defined(MMT_ORIGIN_TU)      // example starts (the ORG instantiations)
-constexpr TuSet kTu = {false, true, false, false, true};
+constexpr TuSet kTu = {false, true, false, false, true, false};
 #define MMT_TU(launcher) launcher##_origin
+#elif defined(MMT_GLOBALS_TU)     // example starts with per-example global tokens (MMT_FLAG_EXAMPLE_GLOBALS: the ORG + GLB instantiations)
+constexpr TuSet kTu = {false, true, false, false, true, true};
+#define MMT_TU(launcher) launcher##_globals
 #else
-constexpr TuSet kTu = {true, true, true, true, false};
+constexpr TuSet kTu = {true, true, true, true, false, false};
 #define MMT_TU(launcher) launcher
 #endif
 hipError_t launch_attn_fwd(const FwdParams& p, int mode, bool bf16, int pack, hipStream_t st);
 hipError_t launch_attn_fwd_origin(const FwdParams& p, int mode, bool bf16, int pack, hipStream_t st);   // attn_fwd_origin.hip
 hipError_t launch_attn_fwd_image(const FwdParams& p, int mode, bool bf16, int pack, hipStream_t st);    // attn_fwd_image.hip
+hipError_t launch_attn_fwd_globals(const FwdParams& p, int mode, bool bf16, int pack, hipStream_t st);  // attn_fwd_globals.hip
 hipError_t launch_rows_combine(const FwdParams& p, bool bf16, hipStream_t st);
 hipError_t launch_attn_fwd_band_bf16(const FwdParams& p, hipStream_t st);   // attn_fwd_band.hip
 hipError_t launch_attn_fwd_win_bf16(const FwdParams& p, hipStream_t st);    // attn_fwd_win.hip
@@ -132,6 +137,7 @@ struct BwdParams {
 hipError_t launch_attn_bwd(const BwdParams& p, int mode, bool bf16, int pack, hipStream_t st);
 hipError_t launch_attn_bwd_origin(const BwdParams& p, int mode, bool bf16, int pack, hipStream_t st);   // attn_bwd_origin.hip
 hipError_t launch_attn_bwd_image(const BwdParams& p, int mode, bool bf16, int pack, hipStream_t st);    // attn_bwd_image.hip
+hipError_t launch_attn_bwd_globals(const BwdParams& p, int mode, bool bf16, int pack, hipStream_t st);  // attn_bwd_globals.hip
 hipError_t launch_attn_bwd_band_bf16(const BwdParams& p, hipStream_t st);   // attn_bwd_band.hip
 hipError_t launch_bwd_dq_combine(const BwdParams& p, bool bf16, hipStream_t st);
 hipError_t launch_bwd_dkv_combine(const BwdParams& p, bool bf16, hipStream_t st);

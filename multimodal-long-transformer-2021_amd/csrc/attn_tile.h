@@ -40,6 +40,14 @@ struct GridWalk {
     img_lo = min(start + grid.gs, S - 1); img_hi = min(img_lo + grid.gI - 1, S - 1);
     ia = max(x0, img_lo); ib = min(x0 + 31, img_hi);
   }
+  // Per-example global tokens (the GLB instantiations), after init_origin: the range moves with the example's start,
+  // [start + g0, start + g0 + ng) cut at the end of the row.  Not cut at the example's end, as the image.
+  __device__ __forceinline__ void init_origin_globals(const PatternDev& pat, int S, int start) {
+    const int lo = start + pat.g0;
+    const bool any = pat.ng > 0 && lo < S;
+    glob_lo = any ? lo >> 5 : 1;
+    glob_hi = any ? min(lo + pat.ng - 1, S - 1) >> 5 : 0;
+  }
   // first and last tile of the union (the band is never empty: it holds the block's own tile)
   __device__ __forceinline__ void span(int& t_lo, int& t_hi) const {
     t_lo = next(0);
@@ -87,6 +95,21 @@ struct PackWalk {
   // start of the example of position x (MMT_FLAG_EXAMPLE_STARTS only: `ids` is plane 0 of the row's [2,S], the starts
   // are plane 1), clamped into [0, S)
   __device__ __forceinline__ int start_at(int x) const { return min(max(ids[S + min(x, S - 1)], 0), S - 1); }
+  // Per-example global tokens, a block of several examples none of whose rows is a global one: the candidates run from
+  // the lowest to the highest tile that the block's band or the global range of any of its rows' examples touches
+  // (st = the row's example start, the same in both halves); the id-range test filters them.
+  __device__ __forceinline__ void span_globals(const PatternDev& pat, int x0, int st, int& t_lo, int& t_hi) const {
+    int mn = st, mx = st;
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) {
+      mn = min(mn, __shfl_xor(mn, o, 64));
+      mx = max(mx, __shfl_xor(mx, o, 64));
+    }
+    mn = __builtin_amdgcn_readfirstlane(mn);
+    mx = __builtin_amdgcn_readfirstlane(mx);
+    t_lo = max(min(x0 - pat.radius, mn + pat.g0), 0) >> 5;
+    t_hi = min(max(x0 + 31 + pat.radius, mx + pat.g0 + pat.ng - 1), S - 1) >> 5;
+  }
   // [lo, hi] over the 32 rows x0 .. x0 + 31 (own = id of row x0 + (lane & 31), the same in both halves)
   __device__ __forceinline__ void init(const int32_t* row_ids, int own, int S_, int n_it_, bool skip) {
     ids = row_ids; S = S_; n_it = n_it_; base = -8; hits = 0;

@@ -91,16 +91,25 @@ int check_desc(const mmt_attn_desc* d) {
 // MMT_FLAG_EXAMPLE_IDS (mask.valid_len names the [B,S] example ids): its argument errors.  Asked for structured calls and
 // by mmt_workspace_bytes only -- with a dense att_mask the flag is ignored like the rest of desc->mask.
 // MMT_FLAG_EXAMPLE_STARTS (valid_len names [B,2,S]: ids and example starts) goes with the ids flag only; it takes the image
-// grid -- every example has its image at its own origin -- and refuses global tokens: per example they are scattered row
-// groups, which the split-rows plan (one contiguous range per row) does not describe.
+// grid -- every example has its image at its own origin.  Global tokens are then per example, scattered row groups that the
+// split-rows plan (one contiguous range per row) does not describe: refused, unless MMT_FLAG_EXAMPLE_GLOBALS asks for the
+// kernels that walk them without that plan (contiguous range form; not with MMT_IDS_2D_IMAGE, whose translation unit
+// has no such instantiations).
 int check_packed(const mmt_attn_desc* d) {
   const bool starts = d->flags & MMT_FLAG_EXAMPLE_STARTS;
+  if ((d->flags & MMT_FLAG_EXAMPLE_GLOBALS) && !(starts && (d->flags & MMT_FLAG_EXAMPLE_IDS)))
+    return fail(MMT_E_INVALID, "MMT_FLAG_EXAMPLE_GLOBALS needs MMT_FLAG_EXAMPLE_IDS | MMT_FLAG_EXAMPLE_STARTS: per-example global tokens are read at positions local to the starts");
   if (starts && !(d->flags & MMT_FLAG_EXAMPLE_IDS)) return fail(MMT_E_INVALID, "MMT_FLAG_EXAMPLE_STARTS needs MMT_FLAG_EXAMPLE_IDS: the starts are plane 1 of [B,2,S] behind the ids");
   if (!(d->flags & MMT_FLAG_EXAMPLE_IDS)) return MMT_OK;
   if (!d->mask.valid_len)
     return starts ? fail(MMT_E_INVALID, "MMT_FLAG_EXAMPLE_STARTS: mask.valid_len must name the [B,2,S] example ids and starts, it is NULL")
                   : fail(MMT_E_INVALID, "MMT_FLAG_EXAMPLE_IDS: mask.valid_len must name the [B,S] example ids, it is NULL");
   if (starts) {
+    if (d->mask.n_global > 0 && (d->flags & MMT_FLAG_EXAMPLE_GLOBALS)) {
+      if (d->mask.id_mode == MMT_IDS_2D_IMAGE)
+        return fail(MMT_E_UNSUPPORTED, "per-example global tokens with MMT_IDS_2D_IMAGE: no structured kernel (materialise att_mask / rel_ids and use the dense operator)");
+      return MMT_OK;
+    }
     if (d->mask.n_global > 0)
       return fail(MMT_E_UNSUPPORTED, "example starts with global tokens: per-example global tokens are scattered row groups with no structured kernel (materialise att_mask / rel_ids and use the dense operator)");
     return MMT_OK;
@@ -141,7 +150,7 @@ mmt::GridDev make_grid(const mmt_mask_desc& m) {
 // Route: which kernel family and which translation unit serve a call.  Decided once, from the descriptor (make_route);
 // the plan, both entry points and the launchers read it and none of them asks the question again.
 enum { kGeneral = 0, kLean = 1 };                    // Route::family
-enum { kTuPlain = 0, kTuOrigin = 1, kTuImage = 2 };  // Route::tu: attn_{fwd,bwd}.hip, .._origin.hip, .._image.hip
+enum { kTuPlain = 0, kTuOrigin = 1, kTuImage = 2, kTuGlobals = 3 };  // Route::tu: attn_{fwd,bwd}.hip, .._origin.hip, .._image.hip, .._globals.hip
 struct Route {
   int pack;            // kPackNone / kPackIds / kPackOrigin (attn_kernels.h); none with a dense att_mask
   int perm_1d;         // 1-D ids with R >= 2m+1: table columns permuted, fast path allowed
@@ -190,11 +199,13 @@ Route make_route(const mmt_attn_desc* d, bool dense) {
   r.family = general_only(r, id_mode, d->R) ? kGeneral : kLean;
   // MMT_IDS_2D_IMAGE away from origin 0 and example starts have general kernels of their own
   r.tu = dense ? kTuPlain : ((id_mode == MMT_IDS_2D && ids_origin(m) != 0) ? kTuImage : (r.pack == mmt::kPackOrigin ? kTuOrigin : kTuPlain));
+  // per-example global tokens (MMT_FLAG_EXAMPLE_GLOBALS, checked: with starts, not MMT_IDS_2D_IMAGE); n_global = 0 is the origin call
+  if (r.tu == kTuOrigin && (d->flags & MMT_FLAG_EXAMPLE_GLOBALS) && m.n_global > 0) r.tu = kTuGlobals;
   return r;
 }
 
-constexpr decltype(&mmt::launch_attn_fwd) kGeneralFwd[] = {mmt::launch_attn_fwd, mmt::launch_attn_fwd_origin, mmt::launch_attn_fwd_image};
-constexpr decltype(&mmt::launch_attn_bwd) kGeneralBwd[] = {mmt::launch_attn_bwd, mmt::launch_attn_bwd_origin, mmt::launch_attn_bwd_image};
+constexpr decltype(&mmt::launch_attn_fwd) kGeneralFwd[] = {mmt::launch_attn_fwd, mmt::launch_attn_fwd_origin, mmt::launch_attn_fwd_image, mmt::launch_attn_fwd_globals};
+constexpr decltype(&mmt::launch_attn_bwd) kGeneralBwd[] = {mmt::launch_attn_bwd, mmt::launch_attn_bwd_origin, mmt::launch_attn_bwd_image, mmt::launch_attn_bwd_globals};
 
 struct Plan {
   bool split_rows;   // structured pattern with global ROWS handled by the kRows pass
@@ -218,7 +229,8 @@ int handover_slots(const mmt_attn_desc* d, const Route& r) {
 Plan make_plan(const mmt_attn_desc* d, bool dense, const Route& r) {
   Plan pl{};
   const int n_tiles = (d->S + 31) / 32;
-  pl.split_rows = !dense && d->mask.n_global > 0 && d->mask.local_radius < d->S;
+  // (per-example global tokens are scattered over the row: their kernels walk them inside the band items, no rows items)
+  pl.split_rows = !dense && d->mask.n_global > 0 && d->mask.local_radius < d->S && r.tu != kTuGlobals;
   pl.n_rowblk = pl.split_rows ? (d->mask.n_global + 31) / 32 : 0;
   pl.n_chunks = pl.split_rows ? (n_tiles + kChunkTiles - 1) / kChunkTiles : 0;
   // head size 128 runs the general kernels only: none of the window / plane-walk / sliding-window workspace below

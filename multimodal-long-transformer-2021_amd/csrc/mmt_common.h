@@ -126,10 +126,11 @@ __device__ __forceinline__ bool pattern_mask_packed(const PatternDev& p, bool se
 // x < S) and table indices only inside their ranges -- garbage starts give wrong numbers, never a stray access.
 __device__ __forceinline__ int local_pos(int x, int start, int S) { return min(max(x - start, 0), S - 1); }
 // ... and the mask under it: the band on row positions (an allowed pair shares its start: k - q is lk - lq), the grid on
-// local ones.  No global term: per-example global tokens are refused on the host (scattered row groups).
-template <bool GRID>
+// local ones.  GLB (MMT_FLAG_EXAMPLE_GLOBALS): the global term on local positions as well -- every example has its global
+// tokens at [g0, g0 + ng) of its own; GLB = false instantiations (n_global = 0) do not evaluate it.
+template <bool GRID, bool GLB = false>
 __device__ __forceinline__ bool pattern_mask_origin(const PatternDev& p, const GridDev& g, bool seg, int q, int k, int lq, int lk) {
-  return seg && (abs(q - k) <= p.radius || (GRID && in_grid(p, g, lq, lk)));
+  return seg && (abs(q - k) <= p.radius || (GLB && (is_global(p, lq) || is_global(p, lk))) || (GRID && in_grid(p, g, lq, lk)));
 }
 
 // ---------------------------------------------------------------------------------------

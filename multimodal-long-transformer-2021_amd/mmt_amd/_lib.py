@@ -21,6 +21,7 @@ MMT_FLAG_SCALE_BEFORE_ADD = 1
 MMT_FLAG_ACCUM_REL_GRADS = 2
 MMT_FLAG_EXAMPLE_IDS = 4      # mask.valid_len names int32 [B,S] example ids (packed rows) instead of [B] lengths
 MMT_FLAG_EXAMPLE_STARTS = 8   # with EXAMPLE_IDS: mask.valid_len names int32 [B,2,S], ids and each position's example start
+MMT_FLAG_EXAMPLE_GLOBALS = 16  # with EXAMPLE_IDS | EXAMPLE_STARTS: the global range is read at local positions (per-example global tokens)
 
 
 def image_grid(radius: int, start: int) -> int:

@@ -17,8 +17,10 @@ The segmented term of a pattern comes from `valid_len` (int32 [B]: one example a
 Packed MULTIMODAL examples add `example_starts` (int32 [B,S], with `example_ids` only): the first position of the example
 each position belongs to.  Relative ids, the image grid and the global range are then read at positions local to the
 example (`x - start`), so that an example in a packed row sees what it would see alone at the start of a row
-(`input_utils.packed_example_layout` builds ids and starts).  The structured kernels take this with an image grid and
-without global tokens; with global tokens the dense operator is fed the composed mask and ids.
+(`input_utils.packed_example_layout` builds ids and starts).  The structured kernels take this with an image grid and with
+a contiguous range of global tokens (`MMT_FLAG_EXAMPLE_GLOBALS`: every example has its global tokens at its own
+[global_start, global_start + n_global)); a listed global set, and global tokens with id_mode 3, go to the dense operator,
+which is fed the composed mask and ids.
 """
 from __future__ import annotations
 
@@ -205,7 +207,8 @@ def clear_pattern_cache() -> None:
 def _resolve_pattern(pattern, att_mask, rel_ids, valid_len, q, example_ids=None, example_starts=None):
   """Listed global sets: contiguous runs become the range form, anything else the dense operator's inputs.  So does,
   with example ids, a pattern with an image grid (the structured kernels refuse that pair) -- unless example starts are
-  given: they take the grid on the structured kernels, and send global tokens of any form to the dense operator."""
+  given: they take the grid and a contiguous global range on the structured kernels (`_make_desc` sets
+  MMT_FLAG_EXAMPLE_GLOBALS), and send a listed set, or global tokens under id_mode 3, to the dense operator."""
   if example_ids is not None and (att_mask is not None or rel_ids is not None):
     raise ValueError('example_ids go with a pattern: dense att_mask/relative_att_ids already hold the segmented mask')
   if pattern is None:
@@ -213,7 +216,7 @@ def _resolve_pattern(pattern, att_mask, rel_ids, valid_len, q, example_ids=None,
   if pattern.global_index is not None:
     pattern = pattern.normalized()
   if example_starts is not None:
-    structured = pattern.global_index is None and pattern.n_global == 0
+    structured = pattern.global_index is None and (pattern.n_global == 0 or int(pattern.id_mode) != _lib.MMT_IDS_2D_IMAGE)
   else:
     structured = pattern.global_index is None and not (example_ids is not None and pattern.grid_radius > 0)
   if structured:
@@ -283,6 +286,8 @@ def _make_desc(q, k, v, out, R, pattern, valid_len, scale, mask_value, scale_bef
     valid_len = example_ids
     if example_starts is not None:   # ... and with starts, both planes of one [B,2,S] tensor (kept alive by the descriptor)
       d.flags |= _lib.MMT_FLAG_EXAMPLE_STARTS
+      if pattern is not None and pattern.global_index is None and pattern.n_global > 0:
+        d.flags |= _lib.MMT_FLAG_EXAMPLE_GLOBALS     # per-example global tokens: the range at local positions
       valid_len = d._origin_planes = _origin_planes(example_ids, example_starts)
   d.mask = (pattern or AttentionPattern(id_mode=_lib.MMT_IDS_NONE)).to_desc(valid_len, q.device)
   d.tuning = int(tuning)

@@ -261,6 +261,31 @@ int mmt_embed_bwd_packed(const mmt_embed_desc* desc, const void* dout, const int
                          const int32_t* example_starts, const int32_t* patch_slots, int32_t n_examples,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* All pairs from separate sets (retrieval; the reference's loader enumerates image x text combinations,
+ * src/data/retrieval_dataloader.py:139-195): mmt_embed_fwd on the batch whose row b is image image_entry[b] followed by
+ * text text_entry[b], without that batch ever being materialised.  Forward only (the loader is for prediction only).
+ *   image_entry, text_entry  int32 [B]  row of the image / text table for pair b; an entry is valid when (unsigned)entry < n
+ *   prefix_ids   int32 [n_img], n_img = patch_start + n_patch   the shared image-side word ids ([CLS] [PATCH] patch ids)
+ *   text_ids     int32 [n_texts, Lt], Lt = S - n_img             zero-padded text ids (data_utils.py:272-276)
+ *   text_len     int32 [n_texts]                                 text length in wordpieces
+ *   patch_proj   [n_images, n_patch, H] in `dtype`               projected patches of the image table
+ * With i = image_entry[b], t = text_entry[b], for position s of row b:
+ *   word   = s < n_img ? prefix_ids[s] : (t valid ? text_ids[t][s - n_img] : 0)
+ *   n_text = t valid ? clamp(text_len[t], 0, Lt) : 0
+ *   seg    = s < n_img ? 1 : (s > n_img && s < n_img + n_text ? 2 : 0)        (data_utils.py:350-361)
+ *   out    = LN(word_table[word]) + seg_table[seg] (+ pos_table[s])
+ *            (+ patch_proj[i][s - patch_start] + patch_bias when i valid and 0 <= s - patch_start < n_patch)
+ *   valid_len_out[b] = n_img + n_text                                          (int32 [B])
+ * Same arithmetic in the same order as mmt_embed_fwd: the result equals mmt_embed_fwd on the materialised batch bit
+ * for bit.  Garbage entries, lengths and ids give the numbers of the rule, never a stray access.  desc->rows = B * S;
+ * desc->dropout_p != 0 is MMT_E_UNSUPPORTED; n_img >= S is MMT_E_INVALID; mean / rstd are not produced. */
+int mmt_embed_fwd_pairs(const mmt_embed_desc* desc, const int32_t* image_entry, const int32_t* text_entry,
+                        const int32_t* prefix_ids, const int32_t* text_ids, const int32_t* text_len, int32_t n_images,
+                        int32_t n_texts, const float* word_table, const float* seg_table,
+                        const float* pos_table /* nullable */, const float* gamma, const float* beta,
+                        const void* patch_proj /* nullable */, const float* patch_bias /* nullable */, void* out,
+                        int32_t* valid_len_out, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Per-row softmax cross-entropy of wide logits (the tied 30522-way MLM head):
  *   loss[row] = logsumexp(logits[row, :]) - logits[row, labels[row]]       (natural log; lse saved)

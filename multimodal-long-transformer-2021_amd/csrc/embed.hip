@@ -49,6 +49,11 @@ struct EmbedParams {
   // position's example in patch [n_ex, n_patch, H] (-1: no image); rows of pos_table
   const int *starts, *slots;
   int n_ex, pos_rows;
+  // all pairs from separate sets (mmt_embed_fwd_pairs; the PAIR instantiations): row b is image image_entry[b] with text
+  // text_entry[b]; ids, segments and the valid length follow from the two tables, patch is [n_images, n_patch, H]
+  const int *image_entry, *text_entry, *prefix_ids, *text_ids, *text_len;
+  int n_images, n_texts;
+  int* valid_len_out;
 };
 
 // Packed rows: position s of row b as a position of its example (clamped into [0, S): garbage starts give wrong
@@ -64,19 +69,52 @@ __device__ __forceinline__ PackedPos packed_pos(const EmbedParams& p, long row, 
   return o;
 }
 
+// Pair rows: word id, segment id and patch entry of position s of pair b, and the pair's text length.  Entries are compared
+// unsigned and the length is clamped into [0, Lt]: garbage entries and lengths give the numbers of the rule in
+// mmt_layer.h, never a stray access (n_img < S is checked by the entry point, so Lt >= 1).
+struct PairPos { int id, sg, e, n_text; };
+__device__ __forceinline__ PairPos pair_pos(const EmbedParams& p, int b, int s) {
+  PairPos o;
+  const int n_img = p.patch_start + p.n_patch, lt = p.S - n_img;
+  const int t = p.text_entry[b];
+  const bool t_ok = (unsigned)t < (unsigned)p.n_texts;
+  o.e = p.image_entry[b];
+  o.n_text = t_ok ? min(max(p.text_len[t], 0), lt) : 0;
+  if (s < n_img) { o.id = p.prefix_ids[s]; o.sg = 1; }
+  else {
+    o.id = t_ok ? p.text_ids[(long)t * lt + (s - n_img)] : 0;
+    o.sg = (s > n_img && s < n_img + o.n_text) ? 2 : 0;
+  }
+  return o;
+}
+
 // PK: packed multimodal rows -- the position row is the one of the LOCAL position, the patch row that of the example's entry.
-template <typename T, int NCH, bool PK = false>
+// PAIR: ids and segments come from pair_pos, the patch row is that of the pair's image; no mean / rstd (forward only).
+template <typename T, int NCH, bool PK = false, bool PAIR = false>
 __global__ __launch_bounds__(256) void embed_fwd_kernel(const EmbedParams p) {
   const SeedPair sd = effective_seed(p.seed_lo, p.seed_hi, p.epoch);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nch = p.H >> 3;
   const float invH = 1.f / (float)p.H;
   for (long row = (long)blockIdx.x * 4 + wave; row < p.rows; row += (long)gridDim.x * 4) {
-    const int id = p.word_ids[row], sg = p.seg_ids[row];
+    int id, sg;
+    PairPos pq;
+    if constexpr (PAIR) {
+      const int pb = (int)(row / p.S);
+      pq = pair_pos(p, pb, (int)(row - (long)pb * p.S));
+      id = pq.id; sg = pq.sg;
+    } else {
+      id = p.word_ids[row]; sg = p.seg_ids[row];
+    }
     const bool id_ok = (unsigned)id < (unsigned)p.vocab, sg_ok = (unsigned)sg < (unsigned)p.seg_vocab;
     const int b = (int)(row / p.S), s = (int)(row - (long)b * p.S);
     int pj = s - p.patch_start, pe = b, ps = s;        // patch row, patch entry, position row
     bool has_patch = p.patch != nullptr && (unsigned)pj < (unsigned)p.n_patch;
+    if constexpr (PAIR) {
+      pe = pq.e;
+      has_patch = has_patch && (unsigned)pe < (unsigned)p.n_images;
+      if (lane == 0 && s == 0) p.valid_len_out[b] = p.patch_start + p.n_patch + pq.n_text;
+    }
     if constexpr (PK) {
       const PackedPos pp = packed_pos(p, row, s);
       pj = pp.pj; pe = pp.e; ps = min(pp.local, p.pos_rows - 1);
@@ -101,7 +139,8 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const EmbedParams p) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) { const float d = v[j][i] - mean; q += d * d; }
     const float rstd = rsqrtf(wave_sum(q) * invH + p.eps);
-    if (lane == 0) { p.mean_out[row] = mean; p.rstd_out[row] = rstd; }
+    if constexpr (!PAIR)
+      if (lane == 0) { p.mean_out[row] = mean; p.rstd_out[row] = rstd; }
 #pragma unroll
     for (int j = 0; j < NCH; ++j) {
       const int c = lane + 64 * j;
@@ -420,6 +459,37 @@ int mmt_embed_fwd_packed(const mmt_embed_desc* d, const int32_t* word_ids, const
   if (d && d->n_patch > 0 && (!patch_slots || n_examples <= 0)) return mmt::fail(MMT_E_INVALID, "mmt_embed_fwd_packed: n_patch > 0 needs patch_slots and n_examples > 0");
   return embed_fwd_any(d, word_ids, seg_ids, word_table, seg_table, pos_table, gamma, beta, patch_proj, patch_bias, out, mean,
                        rstd, example_starts, patch_slots, n_examples, pos_rows, stream);
+}
+
+int mmt_embed_fwd_pairs(const mmt_embed_desc* d, const int32_t* image_entry, const int32_t* text_entry,
+                        const int32_t* prefix_ids, const int32_t* text_ids, const int32_t* text_len, int32_t n_images,
+                        int32_t n_texts, const float* word_table, const float* seg_table, const float* pos_table,
+                        const float* gamma, const float* beta, const void* patch_proj, const float* patch_bias,
+                        void* out, int32_t* valid_len_out, void* stream) {
+  if (int rc = check_embed(d)) return rc;
+  if (d->dropout_p != 0.f) return mmt::fail(MMT_E_UNSUPPORTED, "mmt_embed_fwd_pairs: forward for prediction only, dropout_p must be 0");
+  if (!image_entry || !text_entry || !prefix_ids || !text_ids || !text_len || !word_table || !seg_table || !gamma || !beta ||
+      !out || !valid_len_out)
+    return mmt::fail(MMT_E_INVALID, "mmt_embed_fwd_pairs: NULL argument");
+  if ((long)d->patch_start + d->n_patch >= d->S)
+    return mmt::fail(MMT_E_INVALID, "mmt_embed_fwd_pairs: the image part [0, %d) leaves no room for text in S=%d",
+                     d->patch_start + d->n_patch, d->S);
+  if (d->n_patch > 0 && !patch_proj) return mmt::fail(MMT_E_INVALID, "mmt_embed_fwd_pairs: n_patch > 0 but patch_proj is NULL");
+  mmt::EmbedParams p; fill_embed(p, d);
+  p.word_table = word_table; p.seg_table = seg_table; p.pos_table = pos_table; p.gamma = gamma; p.beta = beta;
+  p.patch = d->n_patch > 0 ? patch_proj : nullptr; p.patch_bias = patch_bias; p.out = out;
+  p.image_entry = image_entry; p.text_entry = text_entry; p.prefix_ids = prefix_ids; p.text_ids = text_ids;
+  p.text_len = text_len; p.n_images = n_images > 0 ? n_images : 0; p.n_texts = n_texts > 0 ? n_texts : 0;
+  p.valid_len_out = valid_len_out;
+  const int blocks = embed_blocks(d), nchl = ((d->H >> 3) + 63) / 64;
+  hipStream_t st = (hipStream_t)stream;
+#define MMT_EP(T, N) hipLaunchKernelGGL((mmt::embed_fwd_kernel<T, N, false, true>), dim3(blocks), dim3(256), 0, st, p)
+#define MMT_EPN(T) do { if (nchl <= 1) MMT_EP(T, 1); else if (nchl <= 2) MMT_EP(T, 2); else MMT_EP(T, 4); } while (0)
+  if (d->dtype == MMT_BF16) MMT_EPN(__bf16); else MMT_EPN(float);
+#undef MMT_EPN
+#undef MMT_EP
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? MMT_OK : mmt::fail(MMT_E_LAUNCH, "mmt_embed_fwd_pairs: %s", hipGetErrorString(e));
 }
 
 size_t mmt_embed_workspace_bytes(const mmt_embed_desc* d) {

@@ -11,10 +11,10 @@ from .input_utils import example_ids_from_breakpoints, example_ids_from_lengths,
 from .encoder import MmtEncoder
 from .models import MmtClassificationModel, MmtPretrainingModel
 from .benchmarks import make_train_step_bench
-from . import configs, distribute, fused, input_utils, layers, optimization, registry_imports, tasks
+from . import configs, distribute, fused, input_utils, layers, optimization, registry_imports, retrieval, tasks
 
 __all__ = ['MmtEncoder', 'MmtPretrainingModel', 'MmtClassificationModel', 'make_train_step_bench',
-           'configs', 'tasks', 'distribute', 'optimization', 'layers', 'input_utils',
+           'configs', 'tasks', 'distribute', 'optimization', 'layers', 'input_utils', 'retrieval',
            'AttentionPattern', 'relative_attention', 'relative_attention_forward',
            'relative_attention_backward', 'side_inputs', 'example_ids_from_breakpoints', 'example_ids_from_lengths', 'packed_example_layout',
            '_lib']

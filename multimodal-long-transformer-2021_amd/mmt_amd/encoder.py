@@ -169,16 +169,99 @@ class MmtEncoder(nn.Module):
       emb = emb + torch.where(has[..., None], rows, torch.zeros_like(rows[:1, :1]))
     return emb
 
-  def forward(self, word_ids, segment_ids=None, att_mask=None, relative_att_ids=None,
+  _PROJECTION_CHUNK = 64      # images per projection GEMM of an image table: M = 64 * P^2 rows at the most
+
+  def project_image_table(self, sets, out=None):
+    """Projected patches [I, P^2, H] (bias included, compute dtype) of `sets.patch_embeddings` with the projection's
+    CURRENT weight and bias, in chunks of `_PROJECTION_CHUNK` images through `layers._linear`.  Nothing is cached here:
+    the fused optimizer and a replayed train step write the parameters without touching torch's version counters, so
+    no key on the host can tell a stale projection from a fresh one.  Whoever scores many batches of one set owns the
+    result and says when it is recomputed (`retrieval.PairScorer`: at the start of every scoring call).  `out`: a
+    buffer of that shape and dtype to write in place (its address may be baked into a recorded graph)."""
+    w, b = self._patch_projection_weight, self._patch_projection_bias
+    pe = sets.patch_embeddings
+    I, C = pe.shape[0], self._PROJECTION_CHUNK
+    with torch.no_grad():
+      if out is None:
+        out = torch.empty((I, pe.shape[1], w.shape[0]), dtype=self.compute_dtype, device=pe.device)
+      elif out.shape != (I, pe.shape[1], w.shape[0]) or out.dtype != self.compute_dtype or out.device != pe.device:
+        raise ValueError('out must be [I, P^2, H] in the compute dtype on the sets\' device')
+      for i in range(0, I, C):
+        out[i:i + C].copy_(layers._linear(pe[i:i + C].to(self.compute_dtype), w, b))
+    return out
+
+  def embed_pairs(self, sets, image_entry, text_entry, patch_proj=None):
+    """Embedding assembly of all pairs from separate sets (`retrieval.RetrievalSets`): row b is image `image_entry[b]`
+    followed by text `text_entry[b]` (int32 [B]), i.e. `embed` on `sets.materialize(image_entry, text_entry)` without
+    that batch -- returns (emb [B,S,H], valid_len int32 [B]).  Prediction only (no dropout, no gradient).  An entry
+    outside its table means "no image" / "empty text" (the padded tail of a batch).  `patch_proj`: the projected image
+    table (`project_image_table`) of a caller that scores many batches and keeps it; None projects the table in this
+    call, with the weights as they are now.  On the GPU one HIP kernel gathers from the resident tables
+    (`fused.embed_assemble_pairs`, `mmt_embed_fwd_pairs`); the torch branch below states the same rule and is the CPU
+    yardstick."""
+    ln = self._embedding_norm_layer
+    proj = self.project_image_table(sets) if patch_proj is None else patch_proj
+    image_entry, text_entry = image_entry.to(torch.int32), text_entry.to(torch.int32)
+    I, n_patch = proj.shape[0], proj.shape[1]
+    n_img = 2 + n_patch
+    T, Lt = sets.text_token_ids.shape
+    S = n_img + Lt
+    if self._fused_embed_ok(sets.text_token_ids):
+      return fused.embed_assemble_pairs(image_entry, text_entry, sets.prefix_ids, sets.text_token_ids,
+                                        sets.num_text_wordpieces, self._word_embedding_layer.embedding_table,
+                                        self._segment_embedding_layer.embedding_table, ln.weight, ln.bias,
+                                        pos_table=self._position_embeddings, patch_proj=proj, eps=ln.eps, patch_start=2,
+                                        out_dtype=self.compute_dtype)
+    with torch.no_grad():
+      dev = sets.text_token_ids.device
+      i_ok = (image_entry >= 0) & (image_entry < I)
+      t_ok = (text_entry >= 0) & (text_entry < T)
+      ti = text_entry.long().clamp(0, T - 1)
+      text = torch.where(t_ok[:, None], sets.text_token_ids[ti], torch.zeros_like(sets.text_token_ids[:1]))
+      n_text = torch.where(t_ok, sets.num_text_wordpieces[ti].clamp(0, Lt), torch.zeros_like(text_entry))
+      B = image_entry.shape[0]
+      word_ids = torch.cat([sets.prefix_ids[None].expand(B, n_img), text], 1)
+      pos = torch.arange(S, device=dev)[None]
+      segment_ids = ((pos < n_img).to(torch.int32)
+                     + 2 * ((pos > n_img) & (pos < n_img + n_text[:, None])).to(torch.int32))
+      word = self._word_embedding_layer(word_ids)
+      seg = self._segment_embedding_layer(segment_ids)
+      word = F.layer_norm(word, ln.normalized_shape, ln.weight, ln.bias, ln.eps)
+      emb = word + seg
+      if self._position_embeddings is not None:
+        emb = emb + self._position_embeddings[:S]
+      rows = proj[image_entry.long().clamp(0, max(I - 1, 0))].to(emb.dtype)
+      rows = torch.where(i_ok[:, None, None], rows, torch.zeros_like(rows[:1, :1]))
+      emb = emb + F.pad(rows, (0, 0, 2, S - 2 - n_patch))
+      return emb, (n_img + n_text).to(torch.int32)
+
+  def forward(self, word_ids=None, segment_ids=None, att_mask=None, relative_att_ids=None,
               patch_embeddings=None, training: Optional[bool] = None,
               attention_pattern: Optional[AttentionPattern] = None, valid_len=None, example_ids=None,
-              example_starts=None, patch_slots=None, first_positions=None):
+              example_starts=None, patch_slots=None, first_positions=None, pairs=None):
     """`example_starts` / `patch_slots` (with `example_ids`): packed multimodal rows (`embed`, ops.py).  `first_positions`
-    int64 [E_all, 2] = (row, first position) of every example: `pooled_output` is then [E_all, H], gathered there."""
+    int64 [E_all, 2] = (row, first position) of every example: `pooled_output` is then [E_all, H], gathered there.
+    `pairs=(sets, image_entry, text_entry[, patch_proj])`: the batch is all the named pairs of a
+    `retrieval.RetrievalSets` (`embed_pairs`; the optional fourth item is a projected image table the caller keeps); `word_ids`, `segment_ids`, `patch_embeddings` and `valid_len` must then be None -- they follow from
+    the sets -- and `attention_pattern` is the structured pattern of the data config as for any structured call."""
     training = bool(training)
+    if pairs is not None:
+      if any(x is not None for x in (word_ids, segment_ids, patch_embeddings, valid_len)):
+        raise ValueError('with pairs=, word_ids, segment_ids, patch_embeddings and valid_len must be None')
+      if training:
+        raise ValueError('pairs= is for prediction only')
+      if any(x is not None for x in (example_ids, example_starts, patch_slots, first_positions)):
+        raise ValueError('pairs= does not combine with packed rows')
+      emb, valid_len = self.embed_pairs(*pairs)
+      emb = emb.to(self.compute_dtype)
+    else:
+      if word_ids is None:
+        raise TypeError('forward() needs word_ids or pairs=')
+      emb = None
     if example_starts is not None and example_ids is None:
       raise ValueError('example_starts needs example_ids')
-    emb = self.embed(word_ids, segment_ids, patch_embeddings, training, example_starts, patch_slots).to(self.compute_dtype)
+    if emb is None:
+      emb = self.embed(word_ids, segment_ids, patch_embeddings, training, example_starts, patch_slots).to(self.compute_dtype)
     out = self._transformer_layers(inputs=emb, att_mask=att_mask, relative_att_ids=relative_att_ids,
                                    training=training, pattern=attention_pattern, valid_len=valid_len,
                                    example_ids=example_ids, example_starts=example_starts,

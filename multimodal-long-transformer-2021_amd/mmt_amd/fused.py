@@ -746,6 +746,78 @@ def embed_assemble(word_ids, seg_ids, word_table, seg_table, gamma, beta, pos_ta
                                 (eps, p, seed, patch_start, out_dtype, example_starts, patch_slots))
 
 
+def _i32_vector(name, t, n=None, device=None):
+  if t.dtype != torch.int32 or t.dim() != 1 or (n is not None and t.shape[0] != n) or not t.is_contiguous():
+    raise ValueError(f'{name} must be a contiguous int32 vector' + ('' if n is None else f' of {n} elements'))
+  if device is not None and t.device != device:
+    raise ValueError(f'{name} is on {t.device}, the tables are on {device}')
+  return t
+
+
+def embed_assemble_pairs(image_entry, text_entry, prefix_ids, text_ids, text_len, word_table, seg_table, gamma, beta,
+                         pos_table=None, patch_proj=None, eps=1e-12, patch_start=2, seq_len=None,
+                         out_dtype=torch.bfloat16, out=None, valid_len=None):
+  """All pairs from separate sets (`mmt_embed_fwd_pairs`): row b of the result is what `embed_assemble` gives for image
+  `image_entry[b]` followed by text `text_entry[b]`, gathered straight from the resident tables -- `prefix_ids` int32
+  [n_img] (n_img = patch_start + n_patch), `text_ids` int32 [T, Lt], `text_len` int32 [T], `patch_proj` [I, n_patch, H]
+  in `out_dtype` (projection bias included).  S = n_img + Lt (`seq_len` checks it).  Returns (out [B,S,H], valid_len
+  int32 [B]); `out` / `valid_len` may be given (a caller's fixed buffers).  Forward only: call it under
+  `torch.no_grad()`.  Everything is validated from shapes and dtypes on the host; no device value is read back, so the
+  call can be recorded into a graph.  Entries outside the tables and lengths outside [0, Lt] follow the rule of
+  include/mmt_layer.h (no image / empty text / clamped)."""
+  tables = (word_table, seg_table, gamma, beta, pos_table, patch_proj)
+  if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tables):
+    raise RuntimeError('embed_assemble_pairs is forward only (prediction): call it under torch.no_grad()')
+  _check(image_entry, text_entry, prefix_ids, text_ids, text_len, *tables)
+  dev = word_table.device
+  if word_table.dim() != 2 or seg_table.dim() != 2 or seg_table.shape[1] != word_table.shape[1]:
+    raise ValueError('word_table and seg_table must be [rows, H] with the same H')
+  V, H = word_table.shape
+  B = image_entry.shape[0] if image_entry.dim() == 1 else -1
+  _i32_vector('image_entry', image_entry, None, dev)
+  _i32_vector('text_entry', text_entry, B, dev)
+  if B <= 0:
+    raise ValueError('image_entry / text_entry must hold at least one pair')
+  n_patch = 0
+  if patch_proj is not None:
+    if patch_proj.dim() != 3 or patch_proj.shape[2] != H or patch_proj.dtype != out_dtype or patch_proj.device != dev:
+      raise ValueError('patch_proj must be [I, n_patch, H] in the output dtype, on the tables\' device')
+    patch_proj = patch_proj.contiguous()
+    n_patch = patch_proj.shape[1]
+  n_img = int(patch_start) + n_patch
+  _i32_vector('prefix_ids', prefix_ids, n_img, dev)
+  if text_ids.dtype != torch.int32 or text_ids.dim() != 2 or text_ids.shape[1] < 1 or not text_ids.is_contiguous() or text_ids.device != dev:
+    raise ValueError('text_ids must be a contiguous int32 [T, Lt] tensor with Lt >= 1, on the tables\' device')
+  T, Lt = text_ids.shape
+  _i32_vector('text_len', text_len, T, dev)
+  S = n_img + Lt
+  if seq_len is not None and int(seq_len) != S:
+    raise ValueError(f'sequence length {seq_len} is not patch_start + n_patch + Lt = {S}')
+  wt, st = _f32(word_table.detach()), _f32(seg_table.detach())
+  pt = None if pos_table is None else _f32(pos_table.detach())
+  if pt is not None and (pt.dim() != 2 or pt.shape[1] != H or pt.shape[0] < S):
+    raise ValueError(f'position table must be [>= {S}, {H}]')
+  g32, b32 = _f32(gamma.detach()), _f32(beta.detach())
+  d = _lib.EmbedDesc()
+  d.rows, d.S, d.H, d.dtype = B * S, S, H, _dtype_code(out_dtype)
+  d.vocab, d.seg_vocab, d.patch_start, d.n_patch = V, st.shape[0], int(patch_start), n_patch
+  d.eps, d.dropout_p, d.dropout_seed, d.dropout_epoch = float(eps), 0.0, 0, None
+  if out is None:
+    out = torch.empty((B, S, H), dtype=out_dtype, device=dev)
+  elif out.shape != (B, S, H) or out.dtype != out_dtype or out.device != dev or not out.is_contiguous():
+    raise ValueError(f'out must be a contiguous [{B}, {S}, {H}] tensor in the output dtype')
+  if valid_len is None:
+    valid_len = torch.empty(B, dtype=torch.int32, device=dev)
+  else:
+    _i32_vector('valid_len', valid_len, B, dev)
+  n_images = 0 if patch_proj is None else patch_proj.shape[0]
+  with torch.cuda.device(dev):
+    _lib.check(_lib.lib().mmt_embed_fwd_pairs(d, _p(image_entry), _p(text_entry), _p(prefix_ids), _p(text_ids), _p(text_len),
+                                              n_images, T, _p(wt), _p(st), _p(pt), _p(g32), _p(b32), _p(patch_proj), None,
+                                              _p(out), _p(valid_len), _stream(out)))
+  return out, valid_len
+
+
 # ---- softmax cross-entropy over wide rows (MLM / MPP heads) ---------------------------------------
 class _SoftmaxXentFn(torch.autograd.Function):
   """loss[row] = logsumexp(logits[row]) - logits[row, label[row]] (fp32), one pass over the logits in

@@ -113,6 +113,39 @@ def packed_example_layout(lengths, has_image, S: int, device=None):
   return ids, starts, slots, first
 
 
+def synthetic_retrieval_sets(data_cfg, n_images: int, n_texts: int, device, generator: Optional[torch.Generator] = None,
+                             vocab_size: int = 30522):
+  """A synthetic image set and text set (`retrieval.RetrievalSets`) with the layout and id ranges of `synthetic_batch`:
+  the shared prefix `[CLS][PATCH] patch_1..patch_{P^2}`, every text `[ATT] text ... [SEP]` zero-padded to
+  Lt = max_seq_len - 2 - P^2, ragged lengths in [2, Lt], ids 0 .. n - 1 for both sets and every text's ground-truth
+  image drawn from the image set."""
+  from .retrieval import RetrievalSets
+  S = data_cfg.max_seq_len
+  P = data_cfg.image_size // data_cfg.patch_size
+  n_patch = P * P
+  n_img = 2 + n_patch
+  Lt = S - n_img
+  if Lt < 2:
+    raise ValueError('max_seq_len leaves no room for text')
+  g = generator
+  ri = lambda lo, hi, shape: torch.randint(lo, hi, shape, device=device, generator=g, dtype=torch.int32)
+  prefix = torch.empty(n_img, device=device, dtype=torch.int32)
+  prefix[0], prefix[1] = CLS_ID, PATCH_ID
+  prefix[2:] = PATCH_START_UNUSED_INDEX + torch.arange(n_patch, device=device, dtype=torch.int32)
+  n_text = ri(2, Lt + 1, (n_texts,))
+  text = ri(1000, vocab_size, (n_texts, Lt))
+  text[:, 0] = ATT_ID
+  text[torch.arange(n_texts, device=device), (n_text - 1).long()] = SEP_ID
+  text = torch.where(torch.arange(Lt, device=device)[None] < n_text[:, None], text, torch.zeros_like(text))
+  image_index = torch.arange(n_images, device=device, dtype=torch.int64)
+  return RetrievalSets(
+      data_cfg=data_cfg,
+      patch_embeddings=torch.randn(n_images, n_patch, data_cfg.patch_size ** 2 * 3, device=device, generator=g),
+      image_index=image_index, prefix_ids=prefix, text_token_ids=text, num_text_wordpieces=n_text,
+      text_index=torch.arange(n_texts, device=device, dtype=torch.int64),
+      gt_image_index=image_index[torch.randint(0, n_images, (n_texts,), device=device, generator=g)])
+
+
 def synthetic_batch(data_cfg, batch_size: int, device, generator: Optional[torch.Generator] = None,
                     vocab_size: int = 30522, dense_side_inputs: bool = False,
                     ragged: bool = False, task: str = 'pretrain'):

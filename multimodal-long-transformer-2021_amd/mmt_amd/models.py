@@ -107,16 +107,22 @@ class MmtClassificationModel(nn.Module):
     self.classification_heads = nn.ModuleList(classification_heads)
     _check_unique(self.classification_heads)
 
-  def forward(self, word_ids, segment_ids=None, att_mask=None, relative_att_ids=None,
+  def forward(self, word_ids=None, segment_ids=None, att_mask=None, relative_att_ids=None,
               patch_embeddings=None, training=None, attention_pattern=None, valid_len=None, example_ids=None,
-              example_starts=None, patch_slots=None, first_positions=None):
-    """Packed multimodal rows: as `MmtPretrainingModel.forward` -- head logits are [E_all, classes]."""
+              example_starts=None, patch_slots=None, first_positions=None, pairs=None):
+    """Packed multimodal rows: as `MmtPretrainingModel.forward` -- head logits are [E_all, classes].
+    `pairs=(sets, image_entry, text_entry)`: score the named pairs of a `retrieval.RetrievalSets` (`MmtEncoder.forward`);
+    `word_ids`, `segment_ids`, `patch_embeddings` and `valid_len` must then be None."""
+    if pairs is not None and any(x is not None for x in (word_ids, segment_ids, patch_embeddings, valid_len)):
+      raise ValueError('with pairs=, word_ids, segment_ids, patch_embeddings and valid_len must be None')
+    if pairs is None and word_ids is None:
+      raise TypeError('forward() needs word_ids or pairs=')
     outputs = dict(self.encoder(word_ids=word_ids, segment_ids=segment_ids, att_mask=att_mask,
                                 relative_att_ids=relative_att_ids,
                                 patch_embeddings=patch_embeddings, training=training,
                                 attention_pattern=attention_pattern, valid_len=valid_len,
                                 example_ids=example_ids, example_starts=example_starts, patch_slots=patch_slots,
-                                first_positions=first_positions))
+                                first_positions=first_positions, pairs=pairs))
     if example_starts is not None:
       return _packed_heads(self, outputs, outputs['sequence_output'], first_positions, training)
     for head in self.classification_heads:

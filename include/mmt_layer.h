@@ -293,6 +293,9 @@ int mmt_embed_fwd_pairs(const mmt_embed_desc* desc, const int32_t* image_entry, 
  * the weighting and divide_no_nan reduction over a few hundred rows stay with the caller.
  * logits are read once in their storage dtype (MMT_F32 | MMT_BF16), row stride `ld` elements.
  * A label outside [0, C) means "no target": loss 0, zero gradient.
+ * A logit of -inf (a masked class) contributes exp(-inf) = 0 to its row's sum (softmax 0 there); a label on such a
+ * column gives loss +inf and a finite gradient.  A row that is -inf everywhere is unspecified (NaN, as in torch).  A NaN logit makes the
+ * loss of its own row NaN and of no other row.
  * Backward: dlogits[row, i] = (softmax(logits[row])[i] - [i == label]) * coef[row], written in `dtype`. */
 int mmt_xent_fwd(int64_t rows, int32_t C, int32_t dtype, const void* logits, int64_t ld,
                  const int32_t* labels, float* loss, float* lse, void* stream);

@@ -19,8 +19,8 @@ struct OnlineLse {
   int am = 0x7fffffff;          // index of the FIRST element equal to m (tf.argmax / SparseCategoricalAccuracy's tie rule)
   __device__ __forceinline__ void add(float x, int i) {
     if (x > m) { s = s * __expf(m - x) + 1.f; m = x; am = i; }       // a thread meets its indices in ascending order
-    else s += __expf(x - m);
-  }
+    else if (x != -INFINITY) s += __expf(x - m);     // a -inf logit adds exp(-inf) = 0 -- also while m is still -inf, where
+  }                                                  // x - m would be NaN; a NaN logit takes this branch and poisons s
   __device__ __forceinline__ void merge(float m2, float s2, int am2) {
     const float mm = fmaxf(m, m2);
     if (mm == -INFINITY) return;
@@ -39,14 +39,19 @@ __global__ __launch_bounds__(256) void xent_fwd_kernel(const T* logits, long ld,
   const long row = blockIdx.x;
   const T* x = logits + row * ld;
   OnlineLse acc;
-  const bool pairs = sizeof(T) == 2 && ((ld & 1) == 0) && ((reinterpret_cast<uintptr_t>(logits) & 3) == 0);
-  if (pairs) {                                    // two bf16 per 4-byte load
+  if constexpr (sizeof(T) == 2) {
+    // bf16: a thread takes element PAIRS (2i, 2i + 1), i = thread, thread + 256, ... -- one 4-byte load per pair when every
+    // row starts 4-byte aligned (even ld, aligned base), two 2-byte loads otherwise.  Both forms visit the same elements
+    // in the same order, so the loss does not depend on the stride or alignment the logits arrive with.
+    const bool pairs = ((ld & 1) == 0) && ((reinterpret_cast<uintptr_t>(logits) & 3) == 0);
     const int np = C >> 1;
     const uint32_t* xp = reinterpret_cast<const uint32_t*>(x);
     for (int i = threadIdx.x; i < np; i += 256) {
-      const uint32_t w = xp[i];
-      acc.add(__uint_as_float(w << 16), 2 * i);
-      acc.add(__uint_as_float(w & 0xFFFF0000u), 2 * i + 1);
+      float a, b;
+      if (pairs) { const uint32_t w = xp[i]; a = __uint_as_float(w << 16); b = __uint_as_float(w & 0xFFFF0000u); }
+      else { a = ldval(x, 2 * i); b = ldval(x, 2 * i + 1); }
+      acc.add(a, 2 * i);
+      acc.add(b, 2 * i + 1);
     }
     if (C & 1) {                      // the odd last element: folded in by thread 0 through a merge (its own indices
       OnlineLse tail;                 // would no longer be ascending)

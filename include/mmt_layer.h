@@ -373,6 +373,31 @@ int mmt_image_patches(const mmt_image_desc* desc, const uint8_t* pixels, int64_t
                       const int32_t* heights, const int32_t* widths, const uint8_t* flip, void* normalised_out,
                       float* unnormalised_out, int32_t* label_ids_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * RandAugment on the device (csrc/rand_augment.hip): the augmentation `decode_fn` applies to the decoded uint8 image
+ * before everything above (src/data/data_utils.py:125-145, 199-202; `RandAugment(num_layers=1)` with the reference's
+ * list of 14 operations).  One operation per image, uint8 in and uint8 out at the source resolution, on the packed
+ * layout of the front end: out_pixels has the size and the offsets of pixels, so the front end consumes it unchanged.
+ *   op  int32 [B]      0 AutoContrast, 1 Equalize, 2 Rotate, 3 Posterize, 4 Solarize, 5 Color, 6 Contrast, 7 Brightness,
+ *                      8 Sharpness, 9 ShearX, 10 ShearY, 11 TranslateX, 12 TranslateY, 13 SolarizeAdd; -1 and every
+ *                      other value: the image is copied
+ *   arg float [B, 8]   [0]: bits (3), threshold (4), addend (13), all truncated to int; blend factor (5, 6, 7, 8);
+ *                      [0..5]: a0 a1 a2 b0 b1 b2 of the affine ops (2, 9..12): output (x, y) takes the source pixel
+ *                      nearest to ((a0 x + a1 y) + a2, (b0 x + b1 y) + b2), or 128 when that lies outside the image
+ * The definitions are in DESIGN.md section 4: integer arithmetic, and fp32 with every product and sum rounded on its
+ * own where a blend or a coordinate needs it, so results are exact and bitwise reproducible (the histograms of ops 0,
+ * 1 and 6 are summed with integer atomics).  pixels, offsets, heights, widths, op, arg, out_pixels and the workspace
+ * are DEVICE memory and are read by the kernels, nothing is allocated and the host does not wait: a recorded graph
+ * follows new values.  The workspace (mmt_rand_augment_workspace_bytes(B) bytes, 4-byte aligned) needs no
+ * initialisation; the call clears what it uses.  Bytes of out_pixels outside every image are not written.
+ * out_pixels must not overlap pixels (MMT_E_INVALID).  The front end's safety rule holds for reads and writes: sizes
+ * below 1 count as 1, offsets and byte addresses are clamped into [0, pixels_bytes) -- wrong metadata gives wrong
+ * pixels, not a fault.  h * w * 3 < 2^31 per image. */
+size_t mmt_rand_augment_workspace_bytes(int32_t B);            /* host only; 0 for B < 1 */
+int mmt_rand_augment(int32_t B, const uint8_t* pixels, int64_t pixels_bytes, const int64_t* offsets,
+                     const int32_t* heights, const int32_t* widths, const int32_t* op, const float* arg /* [B,8] */,
+                     uint8_t* out_pixels, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

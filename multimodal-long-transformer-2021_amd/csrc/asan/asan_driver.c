@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "../../../include/mmt_attn.h"
+#include "../../../include/mmt_layer.h"
 
 extern const unsigned char* g_ws_lo;
 extern const unsigned char* g_ws_hi;
@@ -324,6 +325,51 @@ int main(void) {
     CHECK(mmt_attn_bwd(&da, dummy, dummy, dummy, dummy, NULL, NULL, NULL, dummy, dummy, (const float*)dummy, dummy, dummy, dummy,
                        (float*)dummy, NULL, ws, mmt_workspace_bytes(&da), NULL) == MMT_OK && g_last_handover == 1);
     free(ws);
+  }
+  /* ---- RandAugment (mmt_rand_augment): every refusal, then one accepted call on an exact-size workspace ---- */
+  {
+    enum { NB = 5, NBYTES = 1000 };
+    uint8_t* in = (uint8_t*)malloc(NBYTES);
+    uint8_t* out = (uint8_t*)malloc(NBYTES);
+    uint8_t* both = (uint8_t*)malloc(2 * NBYTES - 1);
+    const size_t need = mmt_rand_augment_workspace_bytes(NB);
+    unsigned char* ws = (unsigned char*)malloc(need);
+    CHECK(in && out && both && ws);
+    CHECK(mmt_rand_augment_workspace_bytes(0) == 0 && mmt_rand_augment_workspace_bytes(-1) == 0);
+    CHECK(need == (size_t)NB * 4 * 256 * 4);
+    const int64_t* offs = (const int64_t*)dummy;
+    const int32_t* i32 = (const int32_t*)dummy;
+    const float* f32 = (const float*)dummy;
+    g_ws_lo = ws; g_ws_hi = ws + need;
+    const int before = g_launches;
+    CHECK(mmt_rand_augment(0, in, NBYTES, offs, i32, i32, i32, f32, out, ws, need, NULL) == MMT_E_INVALID);
+    CHECK(strstr(mmt_last_error(), "must be positive") != NULL);
+    CHECK(mmt_rand_augment(-4, in, NBYTES, offs, i32, i32, i32, f32, out, ws, need, NULL) == MMT_E_INVALID);
+    CHECK(mmt_rand_augment(NB, NULL, NBYTES, offs, i32, i32, i32, f32, out, ws, need, NULL) == MMT_E_INVALID);
+    CHECK(strstr(mmt_last_error(), "NULL argument") != NULL);
+    CHECK(mmt_rand_augment(NB, in, NBYTES, NULL, i32, i32, i32, f32, out, ws, need, NULL) == MMT_E_INVALID);
+    CHECK(mmt_rand_augment(NB, in, NBYTES, offs, NULL, i32, i32, f32, out, ws, need, NULL) == MMT_E_INVALID);
+    CHECK(mmt_rand_augment(NB, in, NBYTES, offs, i32, NULL, i32, f32, out, ws, need, NULL) == MMT_E_INVALID);
+    CHECK(mmt_rand_augment(NB, in, NBYTES, offs, i32, i32, NULL, f32, out, ws, need, NULL) == MMT_E_INVALID);
+    CHECK(mmt_rand_augment(NB, in, NBYTES, offs, i32, i32, i32, NULL, out, ws, need, NULL) == MMT_E_INVALID);
+    CHECK(mmt_rand_augment(NB, in, NBYTES, offs, i32, i32, i32, f32, NULL, ws, need, NULL) == MMT_E_INVALID);
+    CHECK(mmt_rand_augment(NB, in, 0, offs, i32, i32, i32, f32, out, ws, need, NULL) == MMT_E_INVALID);
+    CHECK(strstr(mmt_last_error(), "pixels_bytes") != NULL);
+    CHECK(mmt_rand_augment(NB, in, -1, offs, i32, i32, i32, f32, out, ws, need, NULL) == MMT_E_INVALID);
+    CHECK(mmt_rand_augment(NB, in, (int64_t)1 << 60, offs, i32, i32, i32, f32, out, ws, need, NULL) == MMT_E_INVALID);
+    CHECK(mmt_rand_augment(NB, in, NBYTES, offs, i32, i32, i32, f32, in, ws, need, NULL) == MMT_E_INVALID);          /* in place */
+    CHECK(strstr(mmt_last_error(), "overlaps") != NULL);
+    CHECK(mmt_rand_augment(NB, both, NBYTES, offs, i32, i32, i32, f32, both + NBYTES - 1, ws, need, NULL) == MMT_E_INVALID);   /* one byte shared */
+    CHECK(mmt_rand_augment(NB, both + NBYTES - 1, NBYTES, offs, i32, i32, i32, f32, both, ws, need, NULL) == MMT_E_INVALID);
+    CHECK(mmt_rand_augment(NB, in, NBYTES, offs, i32, i32, i32, f32, out, NULL, need, NULL) == MMT_E_WORKSPACE);
+    CHECK(mmt_rand_augment(NB, in, NBYTES, offs, i32, i32, i32, f32, out, ws, need - 1, NULL) == MMT_E_WORKSPACE);
+    CHECK(strstr(mmt_last_error(), "bytes needed") != NULL);
+    CHECK(mmt_rand_augment(NB, in, NBYTES, offs, i32, i32, i32, f32, out, ws, 0, NULL) == MMT_E_WORKSPACE);
+    CHECK(g_launches == before);
+    CHECK(mmt_rand_augment(NB, in, NBYTES, offs, i32, i32, i32, f32, out, ws, need, NULL) == MMT_OK);
+    CHECK(g_launches == before + 1 && g_last_kind == 10);
+    CHECK(mmt_rand_augment(NB, both, NBYTES - 1, offs, i32, i32, i32, f32, both + NBYTES - 1, ws, need, NULL) == MMT_OK);      /* adjacent, not overlapping */
+    free(in); free(out); free(both); free(ws);
   }
   printf("asan driver ok: %d stand-in launches, no sanitizer report\n", g_launches);
   return 0;

@@ -8,12 +8,13 @@
 #include <cstdlib>
 
 #include "../attn_plan.h"
+#include "../rand_augment.h"
 
 extern "C" {
 const unsigned char* g_ws_lo = nullptr;
 const unsigned char* g_ws_hi = nullptr;
 int g_launches = 0;
-int g_last_kind = 0;   // 1 fwd general, 2 fwd band, 3 fwd window, 4 rows combine, 5 bwd, 6 side inputs, 7 step scalars, 8 fwd plane walk, 9 fwd sliding window
+int g_last_kind = 0;   // 1 fwd general, 2 fwd band, 3 fwd window, 4 rows combine, 5 bwd, 6 side inputs, 7 step scalars, 8 fwd plane walk, 9 fwd sliding window, 10 rand augment
 int g_last_handover = 0;   // the last backward asked for the P hand-over
 const void* g_last_epoch = nullptr;   // the device epoch word the last attention launch was given
 int g_last_pack = 0;       // the last general forward / backward launch was asked for the PACK (example ids) instantiations
@@ -162,5 +163,12 @@ hipError_t launch_attn_bwd_image(const BwdParams& p, int mode, bool bf16, int pa
 hipError_t launch_attn_bwd_globals(const BwdParams& p, int mode, bool bf16, int pack, hipStream_t) { return bwd_general(p, mode, bf16, pack, 3); }
 hipError_t launch_attn_bwd_band_bf16(const BwdParams& p, hipStream_t) { g_last_family = 1; return bwd_any(p, "bwd_lean", 0); }
 hipError_t launch_side_inputs(const SideParams&, hipStream_t) { ++g_launches; g_last_kind = 6; return hipSuccess; }
+hipError_t launch_rand_augment(const RandAugParams& p, hipStream_t) {     // rand_augment.hip built with MMT_RAND_AUGMENT_HOST_ONLY
+  ++g_launches; g_last_kind = 10;
+  trace(" | rand_augment B=%d parts=%d", p.B, p.parts);
+  if (p.B < 1 || p.parts < 8 || p.parts > 256) { std::fprintf(stderr, "asan driver: rand augment grid %d x %d\n", p.B, p.parts); std::abort(); }
+  inside(p.hist, (size_t)p.B * kRandAugHistBytes, "rand augment histograms");
+  return hipSuccess;
+}
 hipError_t launch_write_step_scalars(unsigned long long*, float*, unsigned long long, float, float, float, hipStream_t) { ++g_launches; g_last_kind = 7; return hipSuccess; }
 }  // namespace mmt

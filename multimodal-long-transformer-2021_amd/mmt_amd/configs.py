@@ -135,7 +135,7 @@ class MmtDataConfig(Config):        # data/configs.py:20-55 (+ TFM DataConfig ba
   logits_field: Optional[str] = None
   pos_weights_field: Optional[str] = None
   min_shift: int = 5
-  use_rand_aug: bool = False
+  use_rand_aug: bool = False                # read by feature_pipeline.decode_image_features: RandAugment on the device when training
   cycle_length: int = 8
   deterministic: bool = True
   drop_remainder: bool = True

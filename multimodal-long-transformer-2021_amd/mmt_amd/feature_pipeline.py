@@ -2,15 +2,20 @@
 tensor transforms the reference runs inside tf.data on the host, as batched torch ops on the GPU
 (integer / byte work: gathers, reshapes, bucketize -- nothing here is a GEMM).
 
+  decode_image_features      src/data/data_utils.py:195-222  (the tensor half of `decode_fn` driven by the data config:
+                                                              RandAugment and the flip coin when training, then the line below)
+  rand_augment(_plan)        src/data/data_utils.py:125-145, 199-202  (`RandAugment(num_layers=1)`, the reference's 14 operations,
+                                                              on the decoded uint8 images -- HIP)
   images_to_patch_features   src/data/data_utils.py:195-222  (decoded uint8 images of mixed sizes: /255, bilinear resize,
                                                               (im - MEAN) / MEAN, flip, patches, MPP colour ids -- one HIP kernel)
   convert_image_to_patches   src/data/data_utils.py:147-180  (tf.image.extract_patches 16x16 VALID + raster order)
   make_mpp_label_ids         src/data/data_utils.py:448-481  (mean colour per channel -> 2^bits bins -> base-2^bits id)
   make_matching_features     src/data/data_utils.py:642-712  (in-batch negatives for ITM: tile images, roll texts)
 
-File formats, JPEG decode, WordPiece and RandAugment stay out of scope."""
+File formats, JPEG decode and WordPiece stay out of scope."""
 from __future__ import annotations
 
+import math
 from typing import Dict
 
 import torch
@@ -185,6 +190,205 @@ def images_to_patch_features(images, image_size: int, patch_size: int, *, flip: 
   if bits:
     out['mpp_label_ids'] = ids
   return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# RandAugment (`rand_aug.distort`, src/data/data_utils.py:125-145, 199-202): one of 14 operations per decoded uint8
+# image, before the front end above.  The definitions are DESIGN.md section 4; csrc/rand_augment.hip runs them on the
+# device, the torch ops below are the same arithmetic for CPU tensors (integers, and float32 with every product and
+# sum a separate op), bit for bit.
+# ---------------------------------------------------------------------------------------------------
+RAND_AUGMENT_OPS = ('AutoContrast', 'Equalize', 'Rotate', 'Posterize', 'Solarize', 'Color', 'Contrast', 'Brightness',
+                    'Sharpness', 'ShearX', 'ShearY', 'TranslateX', 'TranslateY', 'SolarizeAdd')
+
+
+def rand_augment_plan(heights: torch.Tensor, widths: torch.Tensor, *, magnitude: float = 10.0,
+                      translate_const: float = 100.0, generator: torch.Generator = None, ops: torch.Tensor = None,
+                      signs: torch.Tensor = None):
+  """The per-example operation and its arguments: (op int32 [B], arg float32 [B, 8]) on the device of `heights`.
+
+  `ops` (ids into RAND_AUGMENT_OPS; -1 = none) and `signs` (+1 / -1, any non-negative value counts as +1) are drawn
+  with `generator` -- first the ids, uniform over the 14, then one fair coin per example -- unless given.  With
+  L = magnitude / 10 (10 is the Model Garden's default, which `RandAugment(num_layers=1)` takes):
+    Color, Contrast, Brightness, Sharpness   arg[0] = 1.8 L + 0.1
+    Posterize  arg[0] = int(4 L) bits;   Solarize  arg[0] = int(256 L);   SolarizeAdd  arg[0] = int(110 L)
+    arg[0..5] = a0 a1 a2 b0 b1 b2 of the affine operations, with t = +-30 degrees * L, c = cos t, s = sin t:
+      Rotate      a = [c, -s, ((w-1) - (c (w-1) - s (h-1))) / 2],   b = [s, c, ((h-1) - (s (w-1) + c (h-1))) / 2]
+      ShearX      a = [1, +-0.3 L, 0],  b = [0, 1, 0];      ShearY      a = [1, 0, 0],  b = [+-0.3 L, 1, 0]
+      TranslateX  a = [1, 0, +-translate_const L],  b = [0, 1, 0];   TranslateY  a = [1, 0, 0],  b = [0, 1, +-translate_const L]
+  Coefficients are computed in float64 and rounded once to float32.  Everything is torch ops on the tensors' device:
+  no value is read back to the host."""
+  if heights.dim() != 1 or heights.shape != widths.shape or heights.device != widths.device:
+    raise ValueError('heights and widths must be [B] tensors on one device')
+  B, dev = heights.shape[0], heights.device
+  if ops is None:
+    ops = torch.randint(0, len(RAND_AUGMENT_OPS), (B,), generator=generator, device=dev)
+  elif ops.shape != (B,) or ops.device != dev:
+    raise ValueError('ops must be a [B] tensor on the device of heights')
+  if signs is None:
+    signs = torch.rand(B, generator=generator, device=dev) < 0.5
+    signs = torch.where(signs, -1.0, 1.0)
+  elif signs.shape != (B,) or signs.device != dev:
+    raise ValueError('signs must be a [B] tensor on the device of heights')
+  op = ops.to(torch.int32)
+  sg = torch.where(signs.to(torch.float64) < 0, -1.0, 1.0).to(torch.float64)
+  L = float(magnitude) / 10.0
+  f64 = lambda v: torch.full((B,), float(v), dtype=torch.float64, device=dev)
+  zero, one = f64(0.0), f64(1.0)
+  w1, h1 = widths.to(torch.float64) - 1.0, heights.to(torch.float64) - 1.0
+  theta = sg * math.radians(30.0 * L)
+  c, s = torch.cos(theta), torch.sin(theta)
+  shear, shift = sg * (0.3 * L), sg * (float(translate_const) * L)
+  rows = {           # op id -> the six (or one) leading arguments
+      2: (c, -s, (w1 - (c * w1 - s * h1)) / 2.0, s, c, (h1 - (s * w1 + c * h1)) / 2.0),
+      3: (f64(int(4 * L)),), 4: (f64(int(256 * L)),), 13: (f64(int(110 * L)),),
+      5: (f64(1.8 * L + 0.1),), 6: (f64(1.8 * L + 0.1),), 7: (f64(1.8 * L + 0.1),), 8: (f64(1.8 * L + 0.1),),
+      9: (one, shear, zero, zero, one, zero), 10: (one, zero, zero, shear, one, zero),
+      11: (one, zero, shift, zero, one, zero), 12: (one, zero, zero, zero, one, shift),
+  }
+  arg = torch.zeros(B, 8, dtype=torch.float64, device=dev)
+  for k, vals in rows.items():
+    row = torch.stack(list(vals) + [zero] * (8 - len(vals)), dim=1)
+    arg = torch.where((op == k)[:, None], row, arg)
+  return op, arg.to(torch.float32)
+
+
+def _blend_u8(a: torch.Tensor, b: torch.Tensor, f: torch.Tensor) -> torch.Tensor:
+  """blend(a, b, f) = trunc(clip(a + f * (b - a), 0, 255)) on integer tensors, f a float32 scalar tensor: the difference
+  is exact, the product and the sum are separate float32 ops."""
+  d = (b - a).to(torch.float32)
+  t = a.to(torch.float32) + f * d
+  return t.clamp(0.0, 255.0).to(torch.int32)
+
+
+def _grey(im: torch.Tensor) -> torch.Tensor:
+  """Pillow's 'L' of an int32 [h, w, 3] image."""
+  return (19595 * im[..., 0] + 38470 * im[..., 1] + 7471 * im[..., 2] + 32768) >> 16
+
+
+def _rand_augment_image(u8: torch.Tensor, op: int, arg: torch.Tensor) -> torch.Tensor:
+  """One operation on one uint8 [h, w, 3] CPU tensor; arg float32 [8]."""
+  if not 0 <= op <= 13:
+    return u8.clone()
+  h, w = u8.shape[0], u8.shape[1]
+  im = u8.to(torch.int32)
+  f = arg[0]
+  if op == 0:
+    out = im.clone()
+    for c in range(3):
+      lo, hi = int(im[..., c].min()), int(im[..., c].max())
+      if hi > lo:
+        scale = torch.tensor(255.0, dtype=torch.float32) / torch.tensor(float(hi - lo), dtype=torch.float32)
+        off = torch.tensor(-float(lo), dtype=torch.float32) * scale
+        out[..., c] = (im[..., c].to(torch.float32) * scale + off).clamp(0.0, 255.0).to(torch.int32)
+  elif op == 1:
+    out = im.clone()
+    for c in range(3):
+      hist = torch.bincount(im[..., c].reshape(-1).to(torch.int64), minlength=256)
+      last = int(hist[int(torch.nonzero(hist)[-1])])
+      step = (int(hist.sum()) - last) // 255
+      if step > 0:
+        lut = ((torch.cumsum(hist, 0) - hist + step // 2) // step).clamp(max=255)
+        lut[0] = 0
+        out[..., c] = lut[im[..., c].to(torch.int64)].to(torch.int32)
+  elif op == 3:
+    shift = 8 - min(max(int(f), 0), 8)
+    out = (im >> shift) << shift
+  elif op == 4:
+    out = torch.where(im < int(f), im, 255 - im)
+  elif op == 13:
+    add = min(max(int(f), -255), 255)
+    out = torch.where(im < 128, (im + add).clamp(0, 255), im)
+  elif op == 5:
+    out = _blend_u8(_grey(im)[..., None], im, f)
+  elif op == 6:
+    g = _grey(im).to(torch.int64)
+    n = g.numel()
+    m = (int(g.sum()) + n // 2) // n
+    out = _blend_u8(torch.full_like(im, m), im, f)
+  elif op == 7:
+    out = _blend_u8(torch.zeros_like(im), im, f)
+  elif op == 8:
+    out = im.clone()
+    if h >= 3 and w >= 3:
+      acc = 5 * im[1:-1, 1:-1]
+      for dy in (0, 1, 2):
+        for dx in (0, 1, 2):
+          if (dy, dx) != (1, 1):
+            acc = acc + im[dy:dy + h - 2, dx:dx + w - 2]
+      out[1:-1, 1:-1] = _blend_u8(acc // 13, im[1:-1, 1:-1], f)
+  else:                                                    # the affine gather: Rotate, ShearX / Y, TranslateX / Y
+    x = torch.arange(w, dtype=torch.float32)[None, :]
+    y = torch.arange(h, dtype=torch.float32)[:, None]
+    sx = (arg[0] * x + arg[1] * y) + arg[2]
+    sy = (arg[3] * x + arg[4] * y) + arg[5]
+    rx, ry = torch.floor(sx + 0.5), torch.floor(sy + 0.5)
+    ok = (rx.abs() < 2.0 ** 30) & (ry.abs() < 2.0 ** 30)   # false for NaN and infinity as well
+    ix = torch.where(ok, rx, torch.full_like(rx, -1.0)).to(torch.int64)
+    iy = torch.where(ok, ry, torch.full_like(ry, -1.0)).to(torch.int64)
+    ok = ok & (ix >= 0) & (ix < w) & (iy >= 0) & (iy < h)
+    src = im[iy.clamp(0, h - 1), ix.clamp(0, w - 1)]
+    out = torch.where(ok[..., None], src, torch.full_like(src, 128))
+  return out.to(torch.uint8)
+
+
+def rand_augment(images, op: torch.Tensor, arg: torch.Tensor, out: torch.Tensor = None):
+  """One RandAugment operation per image.  images: list of uint8 [h, w, 3] tensors or a packed (pixels, offsets, heights,
+  widths) tuple, as `images_to_patch_features` takes; op int32 [B] (ids into RAND_AUGMENT_OPS, any other value copies
+  the image) and arg float32 [B, 8] as `rand_augment_plan` makes them; out: a uint8 tensor of the size of pixels that
+  does not overlap it (allocated when None).  Returns the packed tuple with the new pixels (offsets, heights and widths
+  are the inputs'), which `images_to_patch_features` consumes unchanged.  Bytes of `out` between the images are not
+  written (zero when it is allocated here).  On the GPU it is one mmt_rand_augment call; CPU tensors go through the
+  same arithmetic in torch ops, bit-identical to the kernels."""
+  pixels, offsets, heights, widths = _check_packed(images) if isinstance(images, tuple) else _pack_images(list(images))
+  B, dev = offsets.shape[0], pixels.device
+  if op.shape != (B,) or op.dtype != torch.int32 or op.device != dev:
+    raise ValueError('op must be an int32 [B] tensor on the images\' device')
+  if arg.shape != (B, 8) or arg.dtype != torch.float32 or arg.device != dev:
+    raise ValueError('arg must be a float32 [B, 8] tensor on the images\' device')
+  if out is None:
+    out = torch.zeros_like(pixels)
+  elif out.dtype != torch.uint8 or out.shape != pixels.shape or out.device != dev or not out.is_contiguous():
+    raise ValueError('out must be a contiguous uint8 tensor of the size of pixels on the images\' device')
+  elif out.data_ptr() < pixels.data_ptr() + pixels.numel() and pixels.data_ptr() < out.data_ptr() + out.numel():
+    raise ValueError('out must not overlap pixels')
+  op, arg = op.contiguous(), arg.contiguous()
+  if pixels.is_cuda:
+    from . import _lib
+    L = _lib.lib()
+    need = L.mmt_rand_augment_workspace_bytes(B)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    _lib.check(L.mmt_rand_augment(B, pixels.data_ptr(), pixels.numel(), offsets.data_ptr(), heights.data_ptr(),
+                                  widths.data_ptr(), op.data_ptr(), arg.data_ptr(), out.data_ptr(), ws.data_ptr(), need,
+                                  torch.cuda.current_stream(dev).cuda_stream))
+  else:
+    for b in range(B):
+      h, w, o = int(heights[b]), int(widths[b]), int(offsets[b])
+      im = pixels[o:o + h * w * 3].reshape(h, w, 3)
+      out[o:o + h * w * 3] = _rand_augment_image(im, int(op[b]), arg[b]).reshape(-1)
+  return out, offsets, heights, widths
+
+
+def decode_image_features(data_config, images, *, generator: torch.Generator = None,
+                          out_dtype: torch.dtype = torch.float32, keep_unnormalized: bool = False) -> Dict[str, torch.Tensor]:
+  """The tensor half of `decode_fn` (src/data/data_utils.py:195-222) as the data config drives it:
+    is_training and use_rand_aug   `rand_augment` with a `rand_augment_plan` drawn from `generator`      (:199-202)
+    is_training                    one flip coin per example, flipped when u > 0.5                        (:209-211)
+    then `images_to_patch_features` with the config's image_size, patch_size and, where the config has the field,
+    output_channel_bits (the pretraining loader's MPP ids).
+  Draws come from `generator` in this order: operation ids, signs, flip coins.  With is_training false the result is
+  `images_to_patch_features(images, image_size, patch_size, ...)` bit for bit."""
+  packed = _check_packed(images) if isinstance(images, tuple) else _pack_images(list(images))
+  pixels, offsets, heights, widths = packed
+  flip = None
+  if bool(data_config.is_training):
+    if bool(getattr(data_config, 'use_rand_aug', False)):
+      op, arg = rand_augment_plan(heights, widths, generator=generator)
+      packed = rand_augment(packed, op, arg)
+    flip = torch.rand(offsets.shape[0], generator=generator, device=pixels.device) > 0.5
+  return images_to_patch_features(packed, int(data_config.image_size), int(data_config.patch_size), flip=flip,
+                                  out_dtype=out_dtype, keep_unnormalized=keep_unnormalized,
+                                  output_channel_bits=int(getattr(data_config, 'output_channel_bits', 0)))
 
 
 def make_matching_features(features: Dict[str, torch.Tensor], image_keys: torch.Tensor,

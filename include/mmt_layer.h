@@ -398,6 +398,52 @@ int mmt_rand_augment(int32_t B, const uint8_t* pixels, int64_t pixels_bytes, con
                      const int32_t* heights, const int32_t* widths, const int32_t* op, const float* arg /* [B,8] */,
                      uint8_t* out_pixels, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Text front end of the data layer (csrc/text_tokens.hip): the text half of `decode_fn` (src/data/data_utils.py:241-278).
+ * Each of the F UTF-8 fields of an example is tokenised as original BERT does with do_lower_case (DESIGN.md section 4
+ * states the definition per code point), the fields share `budget` wordpieces round-robin, and the row
+ *   tok_0 pieces_0 tok_1 pieces_1 ... [SEP]   padded with 0 to T
+ * is written with its length (F + sum a_f + 1) and the word starts: 1 on each field token, on [SEP] and on the first
+ * piece of every word, 0 elsewhere and in the padding.  Field (b, f) is lengths[b*F + f] bytes from bytes +
+ * offsets[b*F + f]; offsets are clamped into [0, bytes_len] and lengths into what is left, so wrong metadata gives wrong
+ * ids, not a fault.  A field's work ends once it has produced `budget` pieces, however long it is.
+ *
+ * Vocabulary image (built on the host by mmt_wordpiece_vocab_build, uploaded by the caller; 32-bit words):
+ *   words 0..7   magic "MWPV" (0x5650574d), tokens, slots (a power of two >= 2 * tokens), first word of the token bytes
+ *                (8 + 4 * slots), token bytes stored, three reserved words
+ *   slots        4 words each, open addressing with linear probing from mix(key) & (slots - 1):
+ *                  [0] id + 1 (0: empty)   [1] key   [2] first byte, from the start of the token bytes
+ *                  [3] bytes of the piece | bit 31: a `##` piece
+ *                key = (sum_t c_t * 0x01000193^t mod 2^32) over the piece's code points c_t, xor 0x9e3779b9 for a `##`
+ *                piece; mix(x): x ^= x >> 16, x *= 0x7feb352d, x ^= x >> 15, x *= 0x846ca68b, x ^= x >> 16
+ *   token bytes  the pieces' UTF-8 bytes back to back, without the `##` prefix, padded to a whole word
+ * A token that starts with `##` and is longer is a continuation piece; ids are the positions in the token list.  Empty,
+ * duplicated and ill-formed (not UTF-8) tokens are refused.  A hash hit is confirmed byte by byte on the device.
+ *
+ * Code-point table (uint32, made by the caller: mmt_amd.text_frontend builds it from unicodedata): entries
+ * [0, 0x110000) by source code point, then the side table.  Entry: bits 0..20 value, bit 21 "a word of its own",
+ * bits 22..23 mapped characters n (0..3), bit 24 "separates words" (space).  n = 0 without bit 24: dropped.  n = 1: the
+ * value is the mapped character.  n = 2, 3: the value indexes the side table, whose n consecutive entries hold a
+ * character in bits 0..20 and bit 21 each.  codepoint_entries counts both parts; side indices are clamped into it.
+ *
+ * bytes, offsets (int64 [B*F]), lengths (int32 [B*F]), both tables, the outputs and the workspace are DEVICE memory;
+ * field_token_ids (F ids, F <= 16) is HOST memory and is read during the call.  Nothing is allocated and the host does
+ * not wait, so the call can be recorded into a graph.  Every element of token_ids_out [B,T], num_wordpieces_out [B] and
+ * word_start_out [B,T] is written, nothing else.  The workspace (mmt_text_tokens_workspace_bytes, 4-byte aligned)
+ * needs no initialisation.  No atomics: the same bytes give the same ids.  Refused: NULL arguments, B / F / T below 1,
+ * budget < 0, F + budget + 1 > T, a table too small to be one, misalignment (MMT_E_INVALID), F > 16 (MMT_E_UNSUPPORTED),
+ * a workspace that is too small (MMT_E_WORKSPACE). */
+size_t mmt_wordpiece_vocab_bytes(int64_t n_tokens, int64_t token_bytes);   /* host only; 0 when out of range */
+int mmt_wordpiece_vocab_build(int64_t n_tokens, const uint8_t* token_bytes, const int64_t* token_offsets /* [n_tokens + 1], from 0 */,
+                              void* image /* host, 4-byte aligned */, size_t image_bytes);
+size_t mmt_text_tokens_workspace_bytes(int32_t B, int32_t F, int32_t budget);   /* host only; 0 for B, F < 1 or budget < 0 */
+int mmt_text_tokens(int32_t B, int32_t F, const uint8_t* bytes, int64_t bytes_len, const int64_t* offsets,
+                    const int32_t* lengths, const void* vocab_image, size_t vocab_image_bytes,
+                    const uint32_t* codepoint_table, int64_t codepoint_entries, const int32_t* field_token_ids /* host [F] */,
+                    int32_t sep_id, int32_t unk_id, int32_t T, int32_t budget, int32_t* token_ids_out /* [B,T] */,
+                    int32_t* num_wordpieces_out /* [B] */, uint8_t* word_start_out /* [B,T] */, void* workspace,
+                    size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -371,6 +371,105 @@ int main(void) {
     CHECK(mmt_rand_augment(NB, both, NBYTES - 1, offs, i32, i32, i32, f32, both + NBYTES - 1, ws, need, NULL) == MMT_OK);      /* adjacent, not overlapping */
     free(in); free(out); free(both); free(ws);
   }
+  /* ---- text front end: the vocabulary builder on exact-size buffers (every slot and byte it writes is inside what
+   *      mmt_wordpiece_vocab_bytes asked for), its refusals, then every refusal of mmt_text_tokens and one accepted call ---- */
+  {
+    static const char* toks[] = {"[PAD]", "[UNK]", "[SEP]", "a", "ab", "abc", "##b", "##bc", "##", "#", "\xc3\xa9t\xc3\xa9", "##\xe4\xb8\xad", "\xf0\x9f\x98\x80"};
+    enum { NT = sizeof(toks) / sizeof(toks[0]) };
+    int64_t offs[NT + 1];
+    size_t nb = 0;
+    for (int i = 0; i < NT; ++i) { offs[i] = (int64_t)nb; nb += strlen(toks[i]); }
+    offs[NT] = (int64_t)nb;
+    uint8_t* tb = (uint8_t*)malloc(nb);
+    CHECK(tb != NULL);
+    for (int i = 0; i < NT; ++i) memcpy(tb + offs[i], toks[i], strlen(toks[i]));
+    const size_t vbytes = mmt_wordpiece_vocab_bytes(NT, (int64_t)nb);
+    CHECK(vbytes == 32 + 32 * 16 + ((nb + 3) & ~(size_t)3));
+    CHECK(mmt_wordpiece_vocab_bytes(0, 0) == 0 && mmt_wordpiece_vocab_bytes(-1, 5) == 0 && mmt_wordpiece_vocab_bytes(4, 3) == 0);
+    uint32_t* image = (uint32_t*)malloc(vbytes);
+    CHECK(image != NULL);
+    CHECK(mmt_wordpiece_vocab_build(NT, tb, offs, image, vbytes) == MMT_OK);
+    CHECK(image[1] == NT && image[2] == 32 && image[3] == 8 + 4 * 32);
+    { unsigned used = 0; for (unsigned s = 0; s < 32; ++s) used += image[8 + 4 * s] != 0; CHECK(used == NT); }
+    CHECK(mmt_wordpiece_vocab_build(NT, tb, offs, image, vbytes - 1) == MMT_E_WORKSPACE);
+    CHECK(strstr(mmt_last_error(), "bytes needed") != NULL);
+    CHECK(mmt_wordpiece_vocab_build(NT, NULL, offs, image, vbytes) == MMT_E_INVALID);
+    CHECK(mmt_wordpiece_vocab_build(NT, tb, NULL, image, vbytes) == MMT_E_INVALID);
+    CHECK(mmt_wordpiece_vocab_build(NT, tb, offs, NULL, vbytes) == MMT_E_INVALID);
+    CHECK(mmt_wordpiece_vocab_build(0, tb, offs, image, vbytes) == MMT_E_INVALID);
+    {
+      int64_t bad[4] = {0, 1, 1, 2};                           /* "a", "", "b" */
+      CHECK(mmt_wordpiece_vocab_build(3, tb + offs[3], bad, image, vbytes) == MMT_E_INVALID);
+      CHECK(strstr(mmt_last_error(), "is empty") != NULL);
+      int64_t dec[3] = {0, 2, 1};
+      CHECK(mmt_wordpiece_vocab_build(2, tb, dec, image, vbytes) == MMT_E_INVALID);
+      const uint8_t dup[] = "ab##bab";                         /* "ab", "##b", "ab" */
+      int64_t d3[4] = {0, 2, 5, 7};
+      CHECK(mmt_wordpiece_vocab_build(3, dup, d3, image, vbytes) == MMT_E_INVALID);
+      CHECK(strstr(mmt_last_error(), "token 2 duplicates token 0") != NULL);
+      const uint8_t ill[] = {'a', 0xc0, 0x80};                 /* an overlong form */
+      int64_t i2[3] = {0, 1, 3};
+      CHECK(mmt_wordpiece_vocab_build(2, ill, i2, image, vbytes) == MMT_E_INVALID);
+      CHECK(strstr(mmt_last_error(), "well-formed") != NULL);
+    }
+    enum { TB = 3, TF = 2, TT = 16, TBUD = 13 };
+    const size_t need = mmt_text_tokens_workspace_bytes(TB, TF, TBUD);
+    CHECK(need == (size_t)TB * TF * (TBUD + 1) * 4);
+    CHECK(mmt_text_tokens_workspace_bytes(0, 1, 1) == 0 && mmt_text_tokens_workspace_bytes(1, 0, 1) == 0 && mmt_text_tokens_workspace_bytes(1, 1, -1) == 0);
+    unsigned char* ws = (unsigned char*)malloc(need);
+    CHECK(ws != NULL);
+    g_ws_lo = ws; g_ws_hi = ws + need;
+    int64_t aligned[8] = {0};                                /* the alignment checks want real alignment */
+    char* dm = (char*)aligned;
+    const uint8_t* by = (const uint8_t*)dm;
+    const int64_t* i64 = (const int64_t*)dm;
+    const int32_t* i32 = (const int32_t*)dm;
+    const uint32_t* cp = (const uint32_t*)dm;
+    int32_t* o32 = (int32_t*)dm;
+    uint8_t* o8 = (uint8_t*)dm;
+    const int32_t ftok[2] = {5, 6};
+    const int64_t CPN = 0x110000;
+    const int before = g_launches;
+#define TEXT(B, F, bytes, offsets, lengths, vocab, vb, table, tn, ft, sep, T, budget, ids, cnt, st, w, wb) \
+    mmt_text_tokens(B, F, bytes, 64, offsets, lengths, vocab, vb, table, tn, ft, sep, 1, T, budget, ids, cnt, st, w, wb, NULL)
+    CHECK(TEXT(0, TF, by, i64, i32, image, vbytes, cp, CPN, ftok, 2, TT, TBUD, o32, o32, o8, ws, need) == MMT_E_INVALID);
+    CHECK(strstr(mmt_last_error(), "must be positive") != NULL);
+    CHECK(TEXT(TB, 0, by, i64, i32, image, vbytes, cp, CPN, ftok, 2, TT, TBUD, o32, o32, o8, ws, need) == MMT_E_INVALID);
+    CHECK(TEXT(TB, TF, by, i64, i32, image, vbytes, cp, CPN, ftok, 2, 0, 0, o32, o32, o8, ws, need) == MMT_E_INVALID);
+    CHECK(TEXT(TB, 17, by, i64, i32, image, vbytes, cp, CPN, ftok, 2, 64, TBUD, o32, o32, o8, ws, need) == MMT_E_UNSUPPORTED);
+    CHECK(TEXT(TB, TF, by, i64, i32, image, vbytes, cp, CPN, ftok, 2, TT, TBUD + 1, o32, o32, o8, ws, need) == MMT_E_INVALID);
+    CHECK(strstr(mmt_last_error(), "must fit T") != NULL);
+    CHECK(TEXT(TB, TF, by, i64, i32, image, vbytes, cp, CPN, ftok, 2, TT, -1, o32, o32, o8, ws, need) == MMT_E_INVALID);
+    CHECK(TEXT(TB, TF, NULL, i64, i32, image, vbytes, cp, CPN, ftok, 2, TT, TBUD, o32, o32, o8, ws, need) == MMT_E_INVALID);
+    CHECK(strstr(mmt_last_error(), "NULL argument") != NULL);
+    CHECK(TEXT(TB, TF, by, NULL, i32, image, vbytes, cp, CPN, ftok, 2, TT, TBUD, o32, o32, o8, ws, need) == MMT_E_INVALID);
+    CHECK(TEXT(TB, TF, by, i64, NULL, image, vbytes, cp, CPN, ftok, 2, TT, TBUD, o32, o32, o8, ws, need) == MMT_E_INVALID);
+    CHECK(TEXT(TB, TF, by, i64, i32, NULL, vbytes, cp, CPN, ftok, 2, TT, TBUD, o32, o32, o8, ws, need) == MMT_E_INVALID);
+    CHECK(TEXT(TB, TF, by, i64, i32, image, vbytes, NULL, CPN, ftok, 2, TT, TBUD, o32, o32, o8, ws, need) == MMT_E_INVALID);
+    CHECK(TEXT(TB, TF, by, i64, i32, image, vbytes, cp, CPN, NULL, 2, TT, TBUD, o32, o32, o8, ws, need) == MMT_E_INVALID);
+    CHECK(TEXT(TB, TF, by, i64, i32, image, vbytes, cp, CPN, ftok, 2, TT, TBUD, NULL, o32, o8, ws, need) == MMT_E_INVALID);
+    CHECK(TEXT(TB, TF, by, i64, i32, image, vbytes, cp, CPN, ftok, 2, TT, TBUD, o32, NULL, o8, ws, need) == MMT_E_INVALID);
+    CHECK(TEXT(TB, TF, by, i64, i32, image, vbytes, cp, CPN, ftok, 2, TT, TBUD, o32, o32, NULL, ws, need) == MMT_E_INVALID);
+    CHECK(TEXT(TB, TF, by, i64, i32, image, 40, cp, CPN, ftok, 2, TT, TBUD, o32, o32, o8, ws, need) == MMT_E_INVALID);
+    CHECK(strstr(mmt_last_error(), "no vocabulary image") != NULL);
+    CHECK(TEXT(TB, TF, by, i64, i32, image, vbytes, cp, CPN - 1, ftok, 2, TT, TBUD, o32, o32, o8, ws, need) == MMT_E_INVALID);
+    CHECK(strstr(mmt_last_error(), "codepoint_entries") != NULL);
+    CHECK(TEXT(TB, TF, by, i64, i32, image, vbytes, cp, CPN, ftok, -2, TT, TBUD, o32, o32, o8, ws, need) == MMT_E_INVALID);
+    CHECK(TEXT(TB, TF, by, (const int64_t*)(dm + 4), i32, image, vbytes, cp, CPN, ftok, 2, TT, TBUD, o32, o32, o8, ws, need) == MMT_E_INVALID);
+    CHECK(strstr(mmt_last_error(), "aligned") != NULL);
+    CHECK(TEXT(TB, TF, by, i64, (const int32_t*)(dm + 2), image, vbytes, cp, CPN, ftok, 2, TT, TBUD, o32, o32, o8, ws, need) == MMT_E_INVALID);
+    CHECK(TEXT(TB, TF, by, i64, i32, image, vbytes, cp, CPN, ftok, 2, TT, TBUD, (int32_t*)(dm + 1), o32, o8, ws, need) == MMT_E_INVALID);
+    CHECK(TEXT(TB, TF, by, i64, i32, image, vbytes, cp, CPN, ftok, 2, TT, TBUD, o32, o32, o8, ws + 2, need) == MMT_E_INVALID);
+    CHECK(TEXT(TB, TF, by, i64, i32, image, vbytes, cp, CPN, ftok, 2, TT, TBUD, o32, o32, o8, NULL, need) == MMT_E_WORKSPACE);
+    CHECK(TEXT(TB, TF, by, i64, i32, image, vbytes, cp, CPN, ftok, 2, TT, TBUD, o32, o32, o8, ws, need - 1) == MMT_E_WORKSPACE);
+    CHECK(strstr(mmt_last_error(), "bytes needed") != NULL);
+    CHECK(g_launches == before);
+    CHECK(TEXT(TB, TF, by, i64, i32, image, vbytes, cp, CPN, ftok, 2, TT, TBUD, o32, o32, o8, ws, need) == MMT_OK);
+    CHECK(g_launches == before + 1 && g_last_kind == 11);
+    CHECK(TEXT(1, 1, by, i64, i32, image, vbytes, cp, CPN, ftok, 2, 2, 0, o32, o32, o8, ws, 4) == MMT_OK);      /* budget 0: counts only */
+#undef TEXT
+    free(tb); free(image); free(ws);
+  }
   printf("asan driver ok: %d stand-in launches, no sanitizer report\n", g_launches);
   return 0;
 }

@@ -9,12 +9,13 @@
 
 #include "../attn_plan.h"
 #include "../rand_augment.h"
+#include "../text_tokens.h"
 
 extern "C" {
 const unsigned char* g_ws_lo = nullptr;
 const unsigned char* g_ws_hi = nullptr;
 int g_launches = 0;
-int g_last_kind = 0;   // 1 fwd general, 2 fwd band, 3 fwd window, 4 rows combine, 5 bwd, 6 side inputs, 7 step scalars, 8 fwd plane walk, 9 fwd sliding window, 10 rand augment
+int g_last_kind = 0;   // 1 fwd general, 2 fwd band, 3 fwd window, 4 rows combine, 5 bwd, 6 side inputs, 7 step scalars, 8 fwd plane walk, 9 fwd sliding window, 10 rand augment, 11 text tokens
 int g_last_handover = 0;   // the last backward asked for the P hand-over
 const void* g_last_epoch = nullptr;   // the device epoch word the last attention launch was given
 int g_last_pack = 0;       // the last general forward / backward launch was asked for the PACK (example ids) instantiations
@@ -168,6 +169,14 @@ hipError_t launch_rand_augment(const RandAugParams& p, hipStream_t) {     // ran
   trace(" | rand_augment B=%d parts=%d", p.B, p.parts);
   if (p.B < 1 || p.parts < 8 || p.parts > 256) { std::fprintf(stderr, "asan driver: rand augment grid %d x %d\n", p.B, p.parts); std::abort(); }
   inside(p.hist, (size_t)p.B * kRandAugHistBytes, "rand augment histograms");
+  return hipSuccess;
+}
+hipError_t launch_text_tokens(const TextParams& p, hipStream_t) {       // text_tokens.hip built with MMT_TEXT_TOKENS_HOST_ONLY
+  ++g_launches; g_last_kind = 11;
+  trace(" | text_tokens B=%d F=%d T=%d budget=%d", p.B, p.F, p.T, p.budget);
+  if (p.B < 1 || p.F < 1 || p.F > kTextMaxFields || p.budget < 0 || p.F + p.budget + 1 > p.T) { std::fprintf(stderr, "asan driver: text tokens shape %d %d %d %d\n", p.B, p.F, p.T, p.budget); std::abort(); }
+  inside(p.pieces, (size_t)p.B * p.F * p.budget * 4, "text piece records");
+  inside(p.npieces, (size_t)p.B * p.F * 4, "text piece counts");
   return hipSuccess;
 }
 hipError_t launch_write_step_scalars(unsigned long long*, float*, unsigned long long, float, float, float, hipStream_t) { ++g_launches; g_last_kind = 7; return hipSuccess; }

@@ -47,7 +47,8 @@ EXPORTS = ('mmt_abi_version', 'mmt_last_error', 'mmt_write_step_scalars', 'mmt_w
            'mmt_residual_block_bwd', 'mmt_bias_gelu_fwd', 'mmt_bias_gelu_bwd', 'mmt_colsum_reduce', 'mmt_colsum_reduce_batch', 'mmt_accumulate_grad', 'mmt_grad_clip_scale', 'mmt_adamw_step', 'mmt_wgrad_accumulate',
            'mmt_wgrad_bias_accumulate', 'mmt_wgrad_grouped', 'mmt_wgrad_group_workspace_bytes', 'mmt_wgrad_workspace_bytes', 'mmt_wgrad_set_cu_budget', 'mmt_embed_fwd', 'mmt_embed_bwd', 'mmt_embed_fwd_packed', 'mmt_embed_bwd_packed', 'mmt_embed_fwd_pairs',
            'mmt_embed_workspace_bytes', 'mmt_xent_fwd', 'mmt_xent_fwd_argmax', 'mmt_xent_bwd', 'mmt_xent_bwd_scaled', 'mmt_weighted_loss', 'mmt_colsum', 'mmt_colsum_workspace_bytes', 'mmt_ln_bwd_add', 'mmt_ffn_gelu_gemm', 'mmt_ffn_dgelu_gemm', 'mmt_ffn_set_cu_budget',
-           'mmt_image_patches', 'mmt_rand_augment_workspace_bytes', 'mmt_rand_augment')
+           'mmt_image_patches', 'mmt_rand_augment_workspace_bytes', 'mmt_rand_augment',
+           'mmt_wordpiece_vocab_bytes', 'mmt_wordpiece_vocab_build', 'mmt_text_tokens_workspace_bytes', 'mmt_text_tokens')
 
 
 class EmbedDesc(ctypes.Structure):
@@ -238,6 +239,15 @@ def lib() -> ctypes.CDLL:
   L.mmt_rand_augment_workspace_bytes.argtypes = [ctypes.c_int32]
   L.mmt_rand_augment.restype = ctypes.c_int
   L.mmt_rand_augment.argtypes = [ctypes.c_int32, vp, i64, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+  L.mmt_wordpiece_vocab_bytes.restype = ctypes.c_size_t
+  L.mmt_wordpiece_vocab_bytes.argtypes = [i64, i64]
+  L.mmt_wordpiece_vocab_build.restype = ctypes.c_int
+  L.mmt_wordpiece_vocab_build.argtypes = [i64, vp, vp, vp, ctypes.c_size_t]
+  L.mmt_text_tokens_workspace_bytes.restype = ctypes.c_size_t
+  L.mmt_text_tokens_workspace_bytes.argtypes = [ctypes.c_int32] * 3
+  L.mmt_text_tokens.restype = ctypes.c_int
+  L.mmt_text_tokens.argtypes = ([ctypes.c_int32] * 2 + [vp, i64, vp, vp, vp, ctypes.c_size_t, vp, i64, vp] + [ctypes.c_int32] * 4 +
+                                [vp, vp, vp, vp, ctypes.c_size_t, vp])
   L.mmt_write_step_scalars.restype = ctypes.c_int
   L.mmt_write_step_scalars.argtypes = [vp, vp, ctypes.c_uint64, ctypes.c_float, ctypes.c_float, ctypes.c_float, vp]
   if L.mmt_abi_version() != MMT_ABI_VERSION:

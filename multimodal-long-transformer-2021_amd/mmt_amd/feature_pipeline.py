@@ -12,7 +12,10 @@ tensor transforms the reference runs inside tf.data on the host, as batched torc
   make_mpp_label_ids         src/data/data_utils.py:448-481  (mean colour per channel -> 2^bits bins -> base-2^bits id)
   make_matching_features     src/data/data_utils.py:642-712  (in-batch negatives for ITM: tile images, roll texts)
 
-File formats, JPEG decode and WordPiece stay out of scope."""
+The text half of `decode_fn` (:241-278: WordPiece tokenisation, trim, field tokens, [SEP], padding, word starts) is
+mmt_amd/text_frontend.py (`decode_text_features`, HIP: csrc/text_tokens.hip); its outputs are the text_token_ids,
+num_text_wordpieces and text_word_start that `make_mlm_and_mpp_features` below takes.
+File formats and JPEG decode stay out of scope."""
 from __future__ import annotations
 
 import math

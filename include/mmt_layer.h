@@ -444,6 +444,63 @@ int mmt_text_tokens(int32_t B, int32_t F, const uint8_t* bytes, int64_t bytes_le
                     int32_t* num_wordpieces_out /* [B] */, uint8_t* word_start_out /* [B,T] */, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * JPEG decode in front of the image front end (csrc/jpeg_decode.hip): `tf.io.decode_image(example['image_data'])` of
+ * `decode_fn` (src/data/data_utils.py:195) for JPEG bytes, as libjpeg decodes by default (JDCT_ISLOW, fancy
+ * upsampling; the rules are DESIGN.md section 4, "JPEG decode").  The serial part -- markers and Huffman decoding --
+ * runs on the host and yields quantised coefficients; dequantisation, the 8x8 inverse DCT, chroma upsampling, YCbCr to
+ * RGB and range limiting run on the device and write the packed layout that the two entry points above read: image b
+ * is height x width x 3 bytes, row-major RGB, from pixels_out + pixel_offset.
+ *
+ * Accepted: SOF0 / SOF1 (baseline, extended sequential), Huffman coded, 8-bit samples, 1 component (grey: R = G = B)
+ * or 3 (YCbCr) with chroma 1x1 and luma 1x1, 2x1 or 2x2; any number of scans; DRI / RSTn; 8-bit DQT.  Refused with
+ * MMT_E_UNSUPPORTED: progressive, arithmetic, lossless and hierarchical files, 12-bit samples, 16-bit quantisation
+ * tables, 4 components, other sampling patterns, RGB stored directly (Adobe transform 0), and whatever is not a JPEG.
+ * A truncated or corrupt stream is MMT_E_INVALID.
+ *
+ * One struct describes an image to every call.  The info call fills it with the offsets of a stand-alone image
+ * (coef_offset from 0, pixel_offset 0); a caller that batches adds each image's base to coef_offset[] and sets
+ * pixel_offset.  blocks_w / blocks_h are the component's grid of 8x8 blocks, padded to whole MCUs; component c owns
+ * blocks_w[c] * blocks_h[c] * 64 int16 coefficients from coef + coef_offset[c]: quantised, DC prediction resolved,
+ * natural (de-zigzagged) order, [block_y][block_x][64]; blocks no scan covers are zero.  coef_offset[] must be
+ * multiples of 8.  qtables holds one table of 64 uint16 per component in natural order: [3][64] per image, image b of
+ * a batch at qtables + b * 192. */
+typedef struct mmt_jpeg_image {
+  int32_t width, height;     /* pixels                                                        */
+  int32_t components;        /* 1 | 3                                                         */
+  int32_t h_samp[3];         /* sampling factors per component (1 | 2)                        */
+  int32_t v_samp[3];
+  int32_t blocks_w[3];       /* block grid per component, whole MCUs                          */
+  int32_t blocks_h[3];
+  int64_t coef_offset[3];    /* first coefficient of the component's plane, in int16 elements */
+  int64_t coef_elems;        /* int16 elements of the whole image                             */
+  int64_t pixel_offset;      /* first byte of the image in pixels_out                         */
+} mmt_jpeg_image;
+
+/* Host only, no device call, re-entrant, nothing allocated that outlives the call; never reads past len.
+ * The info call parses the headers up to the first SOS.  The coefficients call entropy-decodes every scan into the
+ * caller's HOST memory (pinned, if it is to be uploaded): `image` must describe this stream (as the info call
+ * reported it, offsets rebased at will) and every plane must lie inside [0, coef_elems).  qtables_out: [3][64]. */
+int mmt_jpeg_info(const uint8_t* bytes, int64_t len, mmt_jpeg_image* out);
+int mmt_jpeg_coefficients(const uint8_t* bytes, int64_t len, const mmt_jpeg_image* image, int16_t* coef,
+                          int64_t coef_elems, uint16_t* qtables_out /* [3][64] */);
+
+/* Stage 2.  The device call takes DEVICE memory throughout (images [B], coef, qtables [B][3][64], pixels_out and the
+ * workspace), allocates nothing and does not wait, so it can be recorded into a graph; two launches whatever B is
+ * (dequantisation + IDCT into uint8 component planes in the workspace, then upsampling + colour), no atomics, bitwise
+ * reproducible.  The workspace (mmt_jpeg_workspace_bytes(coef_elems) bytes) needs no initialisation.  coef and qtables
+ * must be 16-byte aligned, coef_elems in [64, 2^60), pixels_bytes in [1, 2^60).  Bytes of pixels_out outside every
+ * image are not written.  The front end's safety rule holds for every read and write: sizes, grids and offsets from
+ * `images` are clamped into the buffers -- wrong metadata gives wrong pixels, not a fault.  The host variant is the
+ * same arithmetic as a plain loop over HOST memory (CPU tensors, host tests, the sanitizer program). */
+size_t mmt_jpeg_workspace_bytes(int64_t coef_elems);           /* host only; 0 for coef_elems < 64 */
+int mmt_jpeg_pixels(int32_t B, const mmt_jpeg_image* images, const int16_t* coef, int64_t coef_elems,
+                    const uint16_t* qtables, uint8_t* pixels_out, int64_t pixels_bytes, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int mmt_jpeg_pixels_host(int32_t B, const mmt_jpeg_image* images, const int16_t* coef, int64_t coef_elems,
+                         const uint16_t* qtables, uint8_t* pixels_out, int64_t pixels_bytes, void* workspace,
+                         size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

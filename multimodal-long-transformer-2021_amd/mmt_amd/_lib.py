@@ -48,7 +48,8 @@ EXPORTS = ('mmt_abi_version', 'mmt_last_error', 'mmt_write_step_scalars', 'mmt_w
            'mmt_wgrad_bias_accumulate', 'mmt_wgrad_grouped', 'mmt_wgrad_group_workspace_bytes', 'mmt_wgrad_workspace_bytes', 'mmt_wgrad_set_cu_budget', 'mmt_embed_fwd', 'mmt_embed_bwd', 'mmt_embed_fwd_packed', 'mmt_embed_bwd_packed', 'mmt_embed_fwd_pairs',
            'mmt_embed_workspace_bytes', 'mmt_xent_fwd', 'mmt_xent_fwd_argmax', 'mmt_xent_bwd', 'mmt_xent_bwd_scaled', 'mmt_weighted_loss', 'mmt_colsum', 'mmt_colsum_workspace_bytes', 'mmt_ln_bwd_add', 'mmt_ffn_gelu_gemm', 'mmt_ffn_dgelu_gemm', 'mmt_ffn_set_cu_budget',
            'mmt_image_patches', 'mmt_rand_augment_workspace_bytes', 'mmt_rand_augment',
-           'mmt_wordpiece_vocab_bytes', 'mmt_wordpiece_vocab_build', 'mmt_text_tokens_workspace_bytes', 'mmt_text_tokens')
+           'mmt_wordpiece_vocab_bytes', 'mmt_wordpiece_vocab_build', 'mmt_text_tokens_workspace_bytes', 'mmt_text_tokens',
+           'mmt_jpeg_info', 'mmt_jpeg_coefficients', 'mmt_jpeg_workspace_bytes', 'mmt_jpeg_pixels', 'mmt_jpeg_pixels_host')
 
 
 class EmbedDesc(ctypes.Structure):
@@ -95,6 +96,13 @@ class AdamwDesc(ctypes.Structure):
 class ImageDesc(ctypes.Structure):
   _fields_ = [('B', ctypes.c_int32), ('image_size', ctypes.c_int32), ('patch_size', ctypes.c_int32),
               ('out_dtype', ctypes.c_int32), ('channel_bits', ctypes.c_int32), ('mean', ctypes.c_float * 3)]
+
+
+class JpegImage(ctypes.Structure):
+  _fields_ = [('width', ctypes.c_int32), ('height', ctypes.c_int32), ('components', ctypes.c_int32),
+              ('h_samp', ctypes.c_int32 * 3), ('v_samp', ctypes.c_int32 * 3), ('blocks_w', ctypes.c_int32 * 3),
+              ('blocks_h', ctypes.c_int32 * 3), ('coef_offset', ctypes.c_int64 * 3), ('coef_elems', ctypes.c_int64),
+              ('pixel_offset', ctypes.c_int64)]
 
 
 class WgradProblem(ctypes.Structure):
@@ -248,6 +256,17 @@ def lib() -> ctypes.CDLL:
   L.mmt_text_tokens.restype = ctypes.c_int
   L.mmt_text_tokens.argtypes = ([ctypes.c_int32] * 2 + [vp, i64, vp, vp, vp, ctypes.c_size_t, vp, i64, vp] + [ctypes.c_int32] * 4 +
                                 [vp, vp, vp, vp, ctypes.c_size_t, vp])
+  jp = ctypes.POINTER(JpegImage)
+  L.mmt_jpeg_info.restype = ctypes.c_int
+  L.mmt_jpeg_info.argtypes = [vp, i64, jp]
+  L.mmt_jpeg_coefficients.restype = ctypes.c_int
+  L.mmt_jpeg_coefficients.argtypes = [vp, i64, jp, vp, i64, vp]
+  L.mmt_jpeg_workspace_bytes.restype = ctypes.c_size_t
+  L.mmt_jpeg_workspace_bytes.argtypes = [i64]
+  L.mmt_jpeg_pixels.restype = ctypes.c_int
+  L.mmt_jpeg_pixels.argtypes = [ctypes.c_int32, vp, vp, i64, vp, vp, i64, vp, ctypes.c_size_t, vp]
+  L.mmt_jpeg_pixels_host.restype = ctypes.c_int
+  L.mmt_jpeg_pixels_host.argtypes = [ctypes.c_int32, vp, vp, i64, vp, vp, i64, vp, ctypes.c_size_t]
   L.mmt_write_step_scalars.restype = ctypes.c_int
   L.mmt_write_step_scalars.argtypes = [vp, vp, ctypes.c_uint64, ctypes.c_float, ctypes.c_float, ctypes.c_float, vp]
   if L.mmt_abi_version() != MMT_ABI_VERSION:

@@ -2,8 +2,10 @@
 tensor transforms the reference runs inside tf.data on the host, as batched torch ops on the GPU
 (integer / byte work: gathers, reshapes, bucketize -- nothing here is a GEMM).
 
-  decode_image_features      src/data/data_utils.py:195-222  (the tensor half of `decode_fn` driven by the data config:
-                                                              RandAugment and the flip coin when training, then the line below)
+  decode_jpeg_images         src/data/data_utils.py:195      (`tf.io.decode_image(example['image_data'])` for JPEG bytes: markers and
+                                                              Huffman decoding on the host, IDCT, upsampling and colour in HIP)
+  decode_image_features      src/data/data_utils.py:195-222  (`decode_fn` from the encoded bytes or the decoded pixels on, driven by the
+                                                              data config: RandAugment and the flip coin when training, then the line below)
   rand_augment(_plan)        src/data/data_utils.py:125-145, 199-202  (`RandAugment(num_layers=1)`, the reference's 14 operations,
                                                               on the decoded uint8 images -- HIP)
   images_to_patch_features   src/data/data_utils.py:195-222  (decoded uint8 images of mixed sizes: /255, bilinear resize,
@@ -15,11 +17,16 @@ tensor transforms the reference runs inside tf.data on the host, as batched torc
 The text half of `decode_fn` (:241-278: WordPiece tokenisation, trim, field tokens, [SEP], padding, word starts) is
 mmt_amd/text_frontend.py (`decode_text_features`, HIP: csrc/text_tokens.hip); its outputs are the text_token_ids,
 num_text_wordpieces and text_word_start that `make_mlm_and_mpp_features` below takes.
-File formats and JPEG decode stay out of scope."""
+JPEG decode (baseline and extended sequential files; DESIGN.md section 4 lists what is accepted) is `decode_jpeg_images`;
+other file formats and the TFRecord container stay out of scope."""
 from __future__ import annotations
 
+import ctypes
 import math
+from concurrent.futures import ThreadPoolExecutor
 from typing import Dict
+
+import numpy as np
 
 import torch
 
@@ -127,13 +134,117 @@ def _check_packed(packed):
   return pixels.contiguous(), offsets.contiguous(), heights.contiguous(), widths.contiguous()
 
 
+# ---------------------------------------------------------------------------------------------------
+# JPEG decode (`tf.io.decode_image`, src/data/data_utils.py:195): encoded bytes -> the packed layout.  The host parses
+# and Huffman-decodes (csrc/jpeg_decode.hip, plain C++; ctypes releases the GIL, so a thread pool spreads the files),
+# the device dequantises, transforms, upsamples and converts.  DESIGN.md section 4 "JPEG decode" has the rules.
+# ---------------------------------------------------------------------------------------------------
+def _default_device(device):
+  return torch.device(device) if device is not None else torch.device('cuda' if torch.cuda.is_available() else 'cpu')
+
+
+def _is_encoded(item) -> bool:
+  return isinstance(item, (bytes, bytearray, memoryview, np.ndarray))
+
+
+def _maybe_decode(images, device):
+  """A list whose items are encoded bytes is decoded first; a list of tensors or a packed tuple passes unchanged."""
+  if isinstance(images, tuple):
+    return images
+  images = list(images)
+  if images and all(_is_encoded(im) for im in images):
+    return decode_jpeg_images(images, device)
+  return images
+
+
+def decode_jpeg_images(data, device, *, workers: int = 8, out: torch.Tensor = None):
+  """JPEG files -> the packed (pixels uint8 [n], offsets int64 [B], heights int32 [B], widths int32 [B]) tuple on
+  `device` that `rand_augment` and `images_to_patch_features` take; image b is RGB, row-major, back to back.
+
+  data: a list of bytes, bytearray, memoryview or uint8 numpy arrays, one file each.  libjpeg's default decode
+  (JDCT_ISLOW, fancy upsampling), bit for bit; a greyscale file gives R = G = B.  Per item mmt_jpeg_info; one
+  coefficient buffer for the batch (pinned when the device is a GPU); mmt_jpeg_coefficients spread over `workers` threads
+  (clamped to 1..16); one asynchronous upload; one mmt_jpeg_pixels.  With device 'cpu' the same buffers go through
+  mmt_jpeg_pixels_host.  out: a contiguous uint8 tensor on `device` of at least the needed size (allocated when None;
+  bytes behind the last image are not written).  A file the library refuses raises ValueError naming the example."""
+  from . import _lib
+  L = _lib.lib()
+  device = torch.device(device)
+  items = list(data)
+  B = len(items)
+  if B == 0:
+    raise ValueError('data is empty')
+  bufs = []
+  for i, item in enumerate(items):
+    if not _is_encoded(item):
+      raise ValueError(f'data[{i}] must be bytes, bytearray, memoryview or a uint8 numpy array, got {type(item).__name__}')
+    arr = np.ascontiguousarray(item) if isinstance(item, np.ndarray) else np.frombuffer(item, dtype=np.uint8)
+    if arr.dtype != np.uint8 or arr.ndim != 1:
+      raise ValueError(f'data[{i}] must be a 1-D uint8 array of encoded bytes')
+    bufs.append(arr)
+  workers = min(max(int(workers), 1), 16)
+  images = (_lib.JpegImage * B)()
+  n_coef, n_pix = 0, 0
+  hs, ws, offs = [], [], []
+  for i, arr in enumerate(bufs):
+    rc = L.mmt_jpeg_info(arr.ctypes.data, arr.size, ctypes.byref(images[i]))
+    if rc != 0:
+      raise ValueError(f'data[{i}] cannot be decoded: {L.mmt_last_error().decode()}')
+    im = images[i]
+    for c in range(3):
+      im.coef_offset[c] += n_coef
+    im.pixel_offset = n_pix
+    n_coef += im.coef_elems
+    hs.append(im.height); ws.append(im.width); offs.append(n_pix)
+    n_pix += im.height * im.width * 3
+  on_gpu = device.type == 'cuda'
+  coef = torch.empty(n_coef, dtype=torch.int16, pin_memory=on_gpu)
+  qtab = torch.empty(B * 192, dtype=torch.int16, pin_memory=on_gpu)       # uint16 values; torch has no such dtype everywhere
+  coef_ptr, qtab_ptr = coef.data_ptr(), qtab.data_ptr()
+
+  def entropy(i):                                               # the message is thread-local: read it on the worker
+    rc = L.mmt_jpeg_coefficients(bufs[i].ctypes.data, bufs[i].size, ctypes.byref(images[i]), coef_ptr, n_coef, qtab_ptr + i * 384)
+    return None if rc == 0 else L.mmt_last_error().decode()
+
+  if workers == 1 or B == 1:
+    errors = [entropy(i) for i in range(B)]
+  else:
+    with ThreadPoolExecutor(max_workers=min(workers, B)) as pool:
+      errors = list(pool.map(entropy, range(B)))
+  for i, msg in enumerate(errors):
+    if msg is not None:
+      raise ValueError(f'data[{i}] cannot be decoded: {msg}')
+  if out is None:
+    out = torch.zeros(n_pix, dtype=torch.uint8, device=device)
+  elif out.dtype != torch.uint8 or out.dim() != 1 or out.numel() < n_pix or out.device != device or not out.is_contiguous():
+    raise ValueError(f'out must be a contiguous 1-D uint8 tensor of at least {n_pix} bytes on {device}')
+  need = L.mmt_jpeg_workspace_bytes(n_coef)
+  meta = torch.frombuffer(bytearray(bytes(images)), dtype=torch.uint8)
+  if on_gpu:
+    with torch.cuda.device(device):
+      stream = torch.cuda.current_stream(device).cuda_stream
+      coef_d, qtab_d = coef.to(device, non_blocking=True), qtab.to(device, non_blocking=True)
+      meta_d = meta.pin_memory().to(device, non_blocking=True)
+      work = torch.empty(need, dtype=torch.uint8, device=device)
+      _lib.check(L.mmt_jpeg_pixels(B, meta_d.data_ptr(), coef_d.data_ptr(), n_coef, qtab_d.data_ptr(), out.data_ptr(),
+                                   out.numel(), work.data_ptr(), need, stream))
+  else:
+    work = torch.empty(need, dtype=torch.uint8)
+    _lib.check(L.mmt_jpeg_pixels_host(B, ctypes.addressof(images), coef_ptr, n_coef, qtab_ptr, out.data_ptr(), out.numel(),
+                                      work.data_ptr(), need))
+  t = lambda v, dt: torch.tensor(v, dtype=dt).to(device)
+  return out, t(offs, torch.int64), t(hs, torch.int32), t(ws, torch.int32)
+
+
 def images_to_patch_features(images, image_size: int, patch_size: int, *, flip: torch.Tensor = None,
                              out_dtype: torch.dtype = torch.float32, keep_unnormalized: bool = False,
-                             output_channel_bits: int = 0, mean=IMAGENET_DEFAULT_MEAN) -> Dict[str, torch.Tensor]:
+                             output_channel_bits: int = 0, mean=IMAGENET_DEFAULT_MEAN, device=None) -> Dict[str, torch.Tensor]:
   """The tensor half of `decode_fn` (src/data/data_utils.py:195-222) for a batch of decoded RGB images of any sizes.
 
   images: list of uint8 [h, w, 3] tensors, or an already packed (pixels uint8 [n], offsets int64 [B], heights int32
-  [B], widths int32 [B]) tuple (example b is heights[b] x widths[b] x 3 bytes, row-major, from pixels[offsets[b]]).
+  [B], widths int32 [B]) tuple (example b is heights[b] x widths[b] x 3 bytes, row-major, from pixels[offsets[b]]), or a
+  list of encoded JPEG files (bytes, bytearray, memoryview, uint8 numpy arrays), which `decode_jpeg_images` decodes first
+  onto `device` (default: the GPU when there is one).
   Per example: x = u8 / 255; bilinear resize to image_size x image_size (tf.image.resize, TF2 defaults);
   patch_embeddings from (r - mean) / mean -- the reference's line 204 divides by the MEAN -- and
   unnormalized_patch_embeddings from r; flip [B] (bool / uint8; the reference's training-time coin, :209-211, as an
@@ -154,6 +265,7 @@ def images_to_patch_features(images, image_size: int, patch_size: int, *, flip: 
     raise ValueError('output_channel_bits must be in [0, 8]')
   if len(mean) != 3 or any(float(m) == 0.0 for m in mean):
     raise ValueError('mean must be three non-zero numbers')
+  images = _maybe_decode(images, _default_device(device))
   pixels, offsets, heights, widths = _check_packed(images) if isinstance(images, tuple) else _pack_images(list(images))
   B, dev = offsets.shape[0], pixels.device
   if flip is not None:
@@ -373,14 +485,18 @@ def rand_augment(images, op: torch.Tensor, arg: torch.Tensor, out: torch.Tensor 
 
 
 def decode_image_features(data_config, images, *, generator: torch.Generator = None,
-                          out_dtype: torch.dtype = torch.float32, keep_unnormalized: bool = False) -> Dict[str, torch.Tensor]:
-  """The tensor half of `decode_fn` (src/data/data_utils.py:195-222) as the data config drives it:
+                          out_dtype: torch.dtype = torch.float32, keep_unnormalized: bool = False,
+                          device=None) -> Dict[str, torch.Tensor]:
+  """`decode_fn` (src/data/data_utils.py:195-222) as the data config drives it.  images: a list of uint8 [h, w, 3] tensors,
+  a packed tuple, or a list of encoded JPEG files, which `decode_jpeg_images` decodes first onto `device` (default: the
+  GPU when there is one):
     is_training and use_rand_aug   `rand_augment` with a `rand_augment_plan` drawn from `generator`      (:199-202)
     is_training                    one flip coin per example, flipped when u > 0.5                        (:209-211)
     then `images_to_patch_features` with the config's image_size, patch_size and, where the config has the field,
     output_channel_bits (the pretraining loader's MPP ids).
   Draws come from `generator` in this order: operation ids, signs, flip coins.  With is_training false the result is
   `images_to_patch_features(images, image_size, patch_size, ...)` bit for bit."""
+  images = _maybe_decode(images, _default_device(device))
   packed = _check_packed(images) if isinstance(images, tuple) else _pack_images(list(images))
   pixels, offsets, heights, widths = packed
   flip = None

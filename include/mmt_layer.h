@@ -501,6 +501,94 @@ int mmt_jpeg_pixels_host(int32_t B, const mmt_jpeg_image* images, const int16_t*
                          const uint16_t* qtables, uint8_t* pixels_out, int64_t pixels_bytes, void* workspace,
                          size_t workspace_bytes);
 
+/* ------------------------------------------------------------------------------------------------
+ * JPEG entropy decode on the device (csrc/jpeg_entropy.hip; DESIGN.md section 4, "JPEG entropy decode on the device"):
+ * the Huffman decode of the scan as kernels, so that the encoded bytes are uploaded in place of the coefficients.  Its
+ * output is the coefficient layout described above, the one mmt_jpeg_coefficients writes and mmt_jpeg_pixels reads.
+ * Served: files with ONE scan that carries every component (interleaved 4:4:4 / 4:2:2 / 4:2:0, or one grey component),
+ * which is what libjpeg, Pillow and tf.io.encode_jpeg write.  The plan call refuses a file with more than one scan with
+ * MMT_E_UNSUPPORTED; such a file goes through mmt_jpeg_coefficients.
+ *
+ * The scan is cut into restart segments (the bytes between RSTn markers; one segment without DRI) and every segment
+ * into subsequences of subseq_bytes raw bytes (a power of two in [8, 1024]); a subsequence never straddles a segment.
+ * One thread owns a subsequence.  Its state at a boundary is (bit position in the scan, block inside the MCU, zigzag
+ * index); where all components share their tables the block inside the MCU is left out (uniform_tables).  Round 0 decodes every subsequence from an assumed state, round r from the exit state its left neighbour
+ * reached in round r - 1; after r rounds the first r + 1 subsequences of every segment are exact, so max_rounds >=
+ * max_segment_subseq is exact by construction and Huffman streams synchronise themselves long before.  A final pass
+ * checks the chain of states, decodes once more and writes.
+ *
+ * Plan, per image (host memory, filled by mmt_jpeg_scan_plan; a caller that batches concatenates them and rebases
+ * byte_offset, segment_offset and subseq_offset, as it rebases coef_offset):
+ *   scan      mmt_jpeg_scan below
+ *   huff      uint32 [6][MMT_JPEG_HUFF_WORDS]: the DC then the AC table of scan component 0, 1, 2 (unused: zero).
+ *             Table: words 0..255 hold 512 uint16 entries indexed by the next 9 bits, (length << 8) | symbol, 0 when
+ *             the code is longer; words 256..262 the largest code of lengths 10..16 (int32, -1: none); words 264..270
+ *             (index of the first symbol of that length) - (its code); words 272..335 the 256 symbols as bytes
+ *   qtables   uint16 [3][64], exactly what mmt_jpeg_coefficients writes
+ *   segments  int32 [n_segments][4]: first byte and end byte (from the scan's first byte), first MCU, first
+ *             subsequence (from the image's first)
+ *   subseqs   int32 [n_subseq]: the segment of each subsequence (from the image's first)
+ * With segments_out and subseqs_out both NULL the call only reports: it fills scan_out (n_segments and n_subseq are the
+ * capacities to allocate) and, where given, huff_out and qtables_out.  Host only, re-entrant, never reads past len,
+ * allocates nothing that outlives the call.  Malformed data is MMT_E_INVALID as in mmt_jpeg_coefficients. */
+#define MMT_JPEG_HUFF_WORDS 336
+#define MMT_JPEG_ST_OK 0            /* status[b] of the entropy calls                                        */
+#define MMT_JPEG_ST_BAD_CODE 1      /* corrupt: a code that is not in the table                              */
+#define MMT_JPEG_ST_RUN 2           /* corrupt: a zero run past coefficient 63                               */
+#define MMT_JPEG_ST_OVERRUN 3       /* corrupt: a segment ends inside a block                                */
+#define MMT_JPEG_ST_BLOCKS 4        /* corrupt: a segment holds the wrong number of blocks                   */
+#define MMT_JPEG_ST_NOT_CONVERGED 16 /* no error: max_rounds did not suffice, decode the file on the host    */
+typedef struct mmt_jpeg_scan {
+  int64_t byte_offset;        /* first entropy-coded byte of the scan in `bytes`                             */
+  int64_t byte_count;         /* bytes of the scan, restart markers included, below 2^28                     */
+  int64_t segment_offset;     /* the image's first entry in `segments`                                       */
+  int64_t subseq_offset;      /* the image's first entry in `subseqs`                                        */
+  int32_t n_segments;
+  int32_t n_subseq;
+  int32_t max_segment_subseq; /* subsequences of the longest segment                                         */
+  int32_t components;         /* of the MCU: 1 | 3                                                           */
+  int32_t dc_table[3];        /* the scan header's table selectors (huff is laid out per component)          */
+  int32_t ac_table[3];
+  int32_t restart_interval;   /* MCUs per segment, 0: one segment                                            */
+  int32_t mcus;               /* MCUs of the scan                                                            */
+  int32_t subseq_bytes;
+  int32_t uniform_tables;     /* 1: every component names the same DC and the same AC table, so the block inside the
+                                 MCU decides nothing and is no part of a decoder's state (it stays 0)               */
+} mmt_jpeg_scan;
+
+int mmt_jpeg_scan_plan(const uint8_t* bytes, int64_t len, const mmt_jpeg_image* image, int32_t subseq_bytes,
+                       mmt_jpeg_scan* scan_out, uint32_t* huff_out /* [6][336] | NULL */,
+                       uint16_t* qtables_out /* [3][64] | NULL */, int32_t* segments_out, int64_t segment_capacity,
+                       int32_t* subseqs_out, int64_t subseq_capacity);
+
+/* The device call takes DEVICE memory throughout: bytes (the files back to back, 16-byte aligned, bytes_len of them),
+ * images [B], scans [B], huff [B][6][336], segments [n_segments][4], subseqs [n_subseq], coef (16-byte aligned), status
+ * (int32 [B]) and the workspace (mmt_jpeg_entropy_workspace_bytes, 16-byte aligned).  max_subseq is the largest
+ * n_subseq of an image (an image that has more gets an error status), max_rounds >= 1 the number of rounds.  Nothing
+ * is allocated and the host does not wait; the launches -- clear, max_rounds rounds, two for the offsets, write, DC
+ * prediction: max_rounds + 5, their grids sized by B, max_subseq and subseq_bytes -- depend on the arguments alone, so
+ * the call can be recorded into a graph.  Neither the workspace nor coef need be initialised: every plane of every
+ * image is written whole, nothing of coef outside the planes is touched, and the result is bitwise reproducible.
+ * status[b]: MMT_JPEG_ST_OK; MMT_JPEG_ST_NOT_CONVERGED (no error; the planes of that image are unspecified, inside their
+ * bounds); or the largest error code met (corrupt stream).  One image's failure does not disturb another image.  After
+ * the call the first max_rounds * B int32 of the workspace hold, [round][image], whether the round changed a state.
+ * The front end's safety rule holds: every offset, count and index read from device memory is clamped into its buffer
+ * and every loop is bounded by a buffer size, 64 slots per block or max_rounds -- wrong plans give wrong coefficients or
+ * a status, not a fault.  No workgroup waits for another inside a launch.  The host variant runs the same functions as
+ * plain loops over HOST memory, round for round and group for group: the same coefficients and the same status. */
+size_t mmt_jpeg_entropy_workspace_bytes(int32_t B, int64_t n_subseq, int32_t max_subseq, int32_t subseq_bytes,
+                                        int32_t max_rounds);     /* host only; 0 when an argument is out of range */
+int mmt_jpeg_entropy(int32_t B, const uint8_t* bytes, int64_t bytes_len, const mmt_jpeg_image* images,
+                     const mmt_jpeg_scan* scans, const uint32_t* huff, const int32_t* segments, int64_t n_segments,
+                     const int32_t* subseqs, int64_t n_subseq, int32_t max_subseq, int32_t subseq_bytes,
+                     int32_t max_rounds, int16_t* coef, int64_t coef_elems, int32_t* status, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int mmt_jpeg_entropy_host(int32_t B, const uint8_t* bytes, int64_t bytes_len, const mmt_jpeg_image* images,
+                          const mmt_jpeg_scan* scans, const uint32_t* huff, const int32_t* segments, int64_t n_segments,
+                          const int32_t* subseqs, int64_t n_subseq, int32_t max_subseq, int32_t subseq_bytes,
+                          int32_t max_rounds, int16_t* coef, int64_t coef_elems, int32_t* status, void* workspace,
+                          size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

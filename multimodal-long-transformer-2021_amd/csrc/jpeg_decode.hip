@@ -5,6 +5,9 @@
 //   host    mmt_jpeg_info, mmt_jpeg_coefficients: markers and Huffman decoding -- serial by nature, plain C++ that a
 //           sanitizer checks; a corrupt file can do no harm there.  Output: quantised coefficients in natural order,
 //           [component][block_y][block_x][64], and one quantisation table per component.
+//           mmt_jpeg_scan_plan: the same header parser in front of the device entropy decode (jpeg_entropy.hip), which
+//           writes those coefficients from the uploaded bytes: tables in the kernels' form, restart segments,
+//           subsequences.
 //   device  two kernels, grid (images, parts), whatever B is:
 //           1. dequantise + 8x8 inverse DCT into uint8 component planes in the workspace.  8 threads per block, 32
 //              blocks per workgroup step: thread t loads row t (one 16-byte load), dequantises into LDS, runs column t,
@@ -298,17 +301,17 @@ int decode_block(Bits& b, const Huff& dc, const Huff& ac, int& pred, short* out 
 
 struct ScanComp { int c, td, ta; };
 
-// One scan: p stands behind the SOS marker.  Planes are given per component (NULL: the caller has refused already).
-int read_scan(Stream& s, const mmt_jpeg_image& im, short* coef, unsigned short* qout, bool* seen) {
+// The header of a scan: p stands behind the SOS marker and moves to the first entropy-coded byte.  Fills the scan's
+// components and, per component met for the first time, its quantisation table.
+int read_scan_header(Stream& s, ScanComp* sc, int& ns, unsigned short* qout, bool* seen) {
   const Frame& f = s.f;
   if (s.end - s.p < 2) return fail(MMT_E_INVALID, "jpeg: truncated in the scan header");
   const int len = (s.p[0] << 8) | s.p[1];
   if (len < 6 || len > s.end - s.p) return fail(MMT_E_INVALID, "jpeg: scan header of %d bytes leaves the data", len);
   const unsigned char* d = s.p + 2;
   s.p += len;
-  const int ns = d[0];
+  ns = d[0];
   if (ns < 1 || ns > f.nc || len != 6 + 2 * ns) return fail(MMT_E_INVALID, "jpeg: malformed scan header");
-  ScanComp sc[3];
   for (int i = 0; i < ns; ++i) {
     int c = 0;
     while (c < f.nc && f.id[c] != d[1 + 2 * i]) ++c;
@@ -324,6 +327,16 @@ int read_scan(Stream& s, const mmt_jpeg_image& im, short* coef, unsigned short* 
   }
   const unsigned char* t = d + 1 + 2 * ns;
   if (t[0] != 0 || t[1] != 63 || t[2] != 0) return fail(MMT_E_INVALID, "jpeg: spectral selection or successive approximation in a sequential scan");
+  return MMT_OK;
+}
+
+// One scan: p stands behind the SOS marker.  Planes are given per component (NULL: the caller has refused already).
+int read_scan(Stream& s, const mmt_jpeg_image& im, short* coef, unsigned short* qout, bool* seen) {
+  const Frame& f = s.f;
+  ScanComp sc[3];
+  int ns = 0;
+  const int hrc = read_scan_header(s, sc, ns, qout, seen);
+  if (hrc) return hrc;
 
   // a scan of one component walks that component's own blocks; an interleaved one walks MCUs of h x v blocks each
   int mx = f.mcus_x, my = f.mcus_y;
@@ -364,6 +377,39 @@ int read_scan(Stream& s, const mmt_jpeg_image& im, short* coef, unsigned short* 
   }
   s.p = b.p;
   return MMT_OK;
+}
+
+// A table in the form the entropy kernels read (include/mmt_layer.h, MMT_JPEG_HUFF_WORDS words).
+void device_huff(const Huff& h, uint32_t* w) {
+  std::memset(w, 0, MMT_JPEG_HUFF_WORDS * sizeof(uint32_t));
+  std::memcpy(w, h.look, sizeof(h.look));
+  for (int len = 10; len <= 16; ++len) {
+    w[256 + len - 10] = (uint32_t)h.maxcode[len];
+    w[264 + len - 10] = (uint32_t)h.valoff[len];
+  }
+  std::memcpy(w + 272, h.vals, 256);
+}
+
+// The entropy-coded bytes from `at` on, cut at RSTn markers: calls seg(begin, end) per restart segment, at most
+// `expected` of them, and returns the end of the scan (the first marker that is no expected RSTn, or the end of the
+// data).  A 0xff followed by 0x00 is data; any other 0xff ends the segment, as it does for read_scan's bit reader.
+template <class F>
+const unsigned char* walk_segments(const unsigned char* at, const unsigned char* end, int64_t expected, F seg) {
+  const unsigned char* begin = at;
+  int64_t k = 0;
+  for (;;) {
+    const unsigned char* ff = at < end ? (const unsigned char*)std::memchr(at, 0xff, (size_t)(end - at)) : nullptr;
+    if (!ff) { seg(begin, end); return end; }
+    if (ff + 1 < end && ff[1] == 0x00) { at = ff + 2; continue; }
+    const unsigned char* m = ff + 1;                            // the marker's code: read_scan takes no fill bytes either
+    seg(begin, ff);
+    if (m < end && *m == 0xd0 + (k & 7) && k + 1 < expected) {
+      ++k;
+      begin = at = m + 1;
+      continue;
+    }
+    return ff;
+  }
 }
 
 int check_bytes(const char* who, const uint8_t* bytes, int64_t len) {
@@ -568,6 +614,108 @@ int mmt_jpeg_coefficients(const uint8_t* bytes, int64_t len, const mmt_jpeg_imag
   if (rc == MMT_OK)
     for (int c = 0; c < s->f.nc; ++c)
       if (!seen[c]) { rc = mmt::fail(MMT_E_INVALID, "jpeg: truncated: no scan holds component %d", c); break; }
+  delete s;
+  return rc;
+}
+
+int mmt_jpeg_scan_plan(const uint8_t* bytes, int64_t len, const mmt_jpeg_image* image, int32_t subseq_bytes, mmt_jpeg_scan* scan_out,
+                       uint32_t* huff_out, uint16_t* qtables_out, int32_t* segments_out, int64_t segment_capacity, int32_t* subseqs_out,
+                       int64_t subseq_capacity) {
+  int rc = mmt::check_bytes("mmt_jpeg_scan_plan", bytes, len);
+  if (rc) return rc;
+  if (!image || !scan_out) return mmt::fail(MMT_E_INVALID, "mmt_jpeg_scan_plan: NULL argument (image and scan_out are required)");
+  if (subseq_bytes < 8 || subseq_bytes > 1024 || (subseq_bytes & (subseq_bytes - 1)))
+    return mmt::fail(MMT_E_INVALID, "mmt_jpeg_scan_plan: subseq_bytes (%d) must be a power of two in [8, 1024]", subseq_bytes);
+  const bool report = !segments_out && !subseqs_out;
+  if (!report && (!segments_out || !subseqs_out || segment_capacity < 0 || subseq_capacity < 0))
+    return mmt::fail(MMT_E_INVALID, "mmt_jpeg_scan_plan: segments_out and subseqs_out go together, with capacities >= 0");
+  mmt::Stream* s = new mmt::Stream();
+  s->p = bytes; s->end = bytes + len;
+  rc = mmt::read_headers(*s);
+  mmt::ScanComp sc[3];
+  int ns = 0;
+  unsigned short q[3 * 64];
+  bool seen[3] = {false, false, false};
+  if (rc == MMT_OK) {
+    mmt_jpeg_image own;
+    mmt::fill_image(s->f, &own);
+    bool same = image->width == own.width && image->height == own.height && image->components == own.components;
+    for (int c = 0; same && c < own.components; ++c)
+      same = image->h_samp[c] == own.h_samp[c] && image->v_samp[c] == own.v_samp[c] && image->blocks_w[c] == own.blocks_w[c] &&
+             image->blocks_h[c] == own.blocks_h[c];
+    if (!same) rc = mmt::fail(MMT_E_INVALID, "mmt_jpeg_scan_plan: image does not describe this stream (take it from mmt_jpeg_info)");
+    else if (own.coef_elems >= ((int64_t)1 << 31))
+      rc = mmt::fail(MMT_E_UNSUPPORTED, "jpeg: %lld coefficients are too many for the device entropy decode: the host decode takes it",
+                     (long long)own.coef_elems);
+  }
+  if (rc == MMT_OK) {
+    std::memset(q, 0, sizeof(q));
+    rc = mmt::read_scan_header(*s, sc, ns, q, seen);
+  }
+  if (rc == MMT_OK && ns != s->f.nc)
+    rc = mmt::fail(MMT_E_UNSUPPORTED, "jpeg: more than one scan (the first holds %d of %d components): the host decode takes it", ns, s->f.nc);
+  if (rc == MMT_OK && ns == 3 && (sc[0].c != 0 || sc[1].c != 1 || sc[2].c != 2))
+    rc = mmt::fail(MMT_E_UNSUPPORTED, "jpeg: a scan whose components are not in frame order: the host decode takes it");
+  if (rc == MMT_OK) {
+    const mmt::Frame& f = s->f;
+    const int64_t mcus = (int64_t)f.mcus_x * f.mcus_y;          // a lone component has h = v = 1: its blocks are the MCUs
+    const int64_t expected = s->restart ? (mcus + s->restart - 1) / s->restart : 1;
+    const unsigned char* first = s->p;
+    int64_t nseg = 0, nsub = 0, longest = 0;
+    bool fits = true;
+    const unsigned char* scan_end = mmt::walk_segments(first, s->end, expected, [&](const unsigned char* b, const unsigned char* e) {
+      const int64_t subs = e - b > subseq_bytes ? (e - b + subseq_bytes - 1) / subseq_bytes : 1;      // an empty segment has one too
+      if (!report) {
+        if (nseg < segment_capacity && nsub + subs <= subseq_capacity && e - first < ((int64_t)1 << 28)) {
+          int32_t* g = segments_out + nseg * 4;
+          g[0] = (int32_t)(b - first); g[1] = (int32_t)(e - first);
+          g[2] = (int32_t)(nseg * s->restart); g[3] = (int32_t)nsub;
+          for (int64_t i = 0; i < subs; ++i) subseqs_out[nsub + i] = (int32_t)nseg;
+        } else {
+          fits = false;
+        }
+      }
+      ++nseg; nsub += subs;
+      if (subs > longest) longest = subs;
+    });
+    if (scan_end - first >= ((int64_t)1 << 28) || nsub >= ((int64_t)1 << 30))
+      rc = mmt::fail(MMT_E_UNSUPPORTED, "jpeg: a scan of %lld bytes is too long for the device entropy decode: the host decode takes it",
+                     (long long)(scan_end - first));
+    else if (!fits)
+      rc = mmt::fail(MMT_E_INVALID, "mmt_jpeg_scan_plan: %lld segments and %lld subsequences needed, room for %lld and %lld given",
+                     (long long)nseg, (long long)nsub, (long long)segment_capacity, (long long)subseq_capacity);
+    if (rc == MMT_OK) {
+      std::memset(scan_out, 0, sizeof(*scan_out));
+      scan_out->byte_offset = first - bytes; scan_out->byte_count = scan_end - first;
+      scan_out->n_segments = (int32_t)nseg; scan_out->n_subseq = (int32_t)nsub; scan_out->max_segment_subseq = (int32_t)longest;
+      scan_out->components = ns; scan_out->restart_interval = s->restart; scan_out->mcus = (int32_t)mcus;
+      scan_out->subseq_bytes = subseq_bytes;
+      scan_out->uniform_tables = 1;
+      for (int i = 0; i < ns; ++i) {
+        scan_out->dc_table[i] = sc[i].td; scan_out->ac_table[i] = sc[i].ta;
+        if (sc[i].td != sc[0].td || sc[i].ta != sc[0].ta) scan_out->uniform_tables = 0;
+      }
+      if (huff_out) {
+        std::memset(huff_out, 0, 6 * MMT_JPEG_HUFF_WORDS * sizeof(uint32_t));
+        for (int i = 0; i < ns; ++i) {
+          mmt::device_huff(s->dc[sc[i].td], huff_out + (2 * i) * MMT_JPEG_HUFF_WORDS);
+          mmt::device_huff(s->ac[sc[i].ta], huff_out + (2 * i + 1) * MMT_JPEG_HUFF_WORDS);
+        }
+      }
+      if (qtables_out) std::memcpy(qtables_out, q, sizeof(q));
+      s->p = scan_end;
+    }
+  }
+  while (rc == MMT_OK) {                                        // behind the scan, as mmt_jpeg_coefficients goes on: up to EOI
+    const int m = mmt::next_marker(*s);
+    if (m < 0) { rc = mmt::fail(MMT_E_INVALID, "jpeg: truncated: the data ends without an EOI marker"); break; }
+    if (m == 0xd9) break;
+    if (m == 0xda) { rc = mmt::fail(MMT_E_UNSUPPORTED, "jpeg: more than one scan: the host decode takes it"); break; }
+    if (m >= 0xd0 && m <= 0xd7) { rc = mmt::fail(MMT_E_INVALID, "jpeg: corrupt: a restart marker outside a scan"); break; }
+    if (mmt::bare_marker(m)) continue;
+    if (m >= 0xc0 && m <= 0xcf && m != 0xc4) { rc = mmt::fail(MMT_E_INVALID, "jpeg: a second frame header"); break; }
+    rc = mmt::read_segment(*s, m);
+  }
   delete s;
   return rc;
 }

@@ -49,7 +49,8 @@ EXPORTS = ('mmt_abi_version', 'mmt_last_error', 'mmt_write_step_scalars', 'mmt_w
            'mmt_embed_workspace_bytes', 'mmt_xent_fwd', 'mmt_xent_fwd_argmax', 'mmt_xent_bwd', 'mmt_xent_bwd_scaled', 'mmt_weighted_loss', 'mmt_colsum', 'mmt_colsum_workspace_bytes', 'mmt_ln_bwd_add', 'mmt_ffn_gelu_gemm', 'mmt_ffn_dgelu_gemm', 'mmt_ffn_set_cu_budget',
            'mmt_image_patches', 'mmt_rand_augment_workspace_bytes', 'mmt_rand_augment',
            'mmt_wordpiece_vocab_bytes', 'mmt_wordpiece_vocab_build', 'mmt_text_tokens_workspace_bytes', 'mmt_text_tokens',
-           'mmt_jpeg_info', 'mmt_jpeg_coefficients', 'mmt_jpeg_workspace_bytes', 'mmt_jpeg_pixels', 'mmt_jpeg_pixels_host')
+           'mmt_jpeg_info', 'mmt_jpeg_coefficients', 'mmt_jpeg_workspace_bytes', 'mmt_jpeg_pixels', 'mmt_jpeg_pixels_host',
+           'mmt_jpeg_scan_plan', 'mmt_jpeg_entropy_workspace_bytes', 'mmt_jpeg_entropy', 'mmt_jpeg_entropy_host')
 
 
 class EmbedDesc(ctypes.Structure):
@@ -103,6 +104,19 @@ class JpegImage(ctypes.Structure):
               ('h_samp', ctypes.c_int32 * 3), ('v_samp', ctypes.c_int32 * 3), ('blocks_w', ctypes.c_int32 * 3),
               ('blocks_h', ctypes.c_int32 * 3), ('coef_offset', ctypes.c_int64 * 3), ('coef_elems', ctypes.c_int64),
               ('pixel_offset', ctypes.c_int64)]
+
+
+MMT_JPEG_HUFF_WORDS = 336      # uint32 words of one Huffman table in the device form; 6 tables per image
+MMT_JPEG_ST_OK, MMT_JPEG_ST_BAD_CODE, MMT_JPEG_ST_RUN, MMT_JPEG_ST_OVERRUN, MMT_JPEG_ST_BLOCKS = 0, 1, 2, 3, 4
+MMT_JPEG_ST_NOT_CONVERGED = 16
+
+
+class JpegScan(ctypes.Structure):
+  _fields_ = [('byte_offset', ctypes.c_int64), ('byte_count', ctypes.c_int64), ('segment_offset', ctypes.c_int64),
+              ('subseq_offset', ctypes.c_int64), ('n_segments', ctypes.c_int32), ('n_subseq', ctypes.c_int32),
+              ('max_segment_subseq', ctypes.c_int32), ('components', ctypes.c_int32), ('dc_table', ctypes.c_int32 * 3),
+              ('ac_table', ctypes.c_int32 * 3), ('restart_interval', ctypes.c_int32), ('mcus', ctypes.c_int32),
+              ('subseq_bytes', ctypes.c_int32), ('uniform_tables', ctypes.c_int32)]
 
 
 class WgradProblem(ctypes.Structure):
@@ -267,6 +281,15 @@ def lib() -> ctypes.CDLL:
   L.mmt_jpeg_pixels.argtypes = [ctypes.c_int32, vp, vp, i64, vp, vp, i64, vp, ctypes.c_size_t, vp]
   L.mmt_jpeg_pixels_host.restype = ctypes.c_int
   L.mmt_jpeg_pixels_host.argtypes = [ctypes.c_int32, vp, vp, i64, vp, vp, i64, vp, ctypes.c_size_t]
+  L.mmt_jpeg_scan_plan.restype = ctypes.c_int
+  L.mmt_jpeg_scan_plan.argtypes = [vp, i64, jp, ctypes.c_int32, ctypes.POINTER(JpegScan), vp, vp, vp, i64, vp, i64]
+  L.mmt_jpeg_entropy_workspace_bytes.restype = ctypes.c_size_t
+  L.mmt_jpeg_entropy_workspace_bytes.argtypes = [ctypes.c_int32, i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
+  entropy_args = ([ctypes.c_int32, vp, i64, vp, vp, vp, vp, i64, vp, i64] + [ctypes.c_int32] * 3 + [vp, i64, vp, vp, ctypes.c_size_t])
+  L.mmt_jpeg_entropy.restype = ctypes.c_int
+  L.mmt_jpeg_entropy.argtypes = entropy_args + [vp]
+  L.mmt_jpeg_entropy_host.restype = ctypes.c_int
+  L.mmt_jpeg_entropy_host.argtypes = entropy_args
   L.mmt_write_step_scalars.restype = ctypes.c_int
   L.mmt_write_step_scalars.argtypes = [vp, vp, ctypes.c_uint64, ctypes.c_float, ctypes.c_float, ctypes.c_float, vp]
   if L.mmt_abi_version() != MMT_ABI_VERSION:

@@ -2,8 +2,9 @@
 tensor transforms the reference runs inside tf.data on the host, as batched torch ops on the GPU
 (integer / byte work: gathers, reshapes, bucketize -- nothing here is a GEMM).
 
-  decode_jpeg_images         src/data/data_utils.py:195      (`tf.io.decode_image(example['image_data'])` for JPEG bytes: markers and
-                                                              Huffman decoding on the host, IDCT, upsampling and colour in HIP)
+  decode_jpeg_images         src/data/data_utils.py:195      (`tf.io.decode_image(example['image_data'])` for JPEG bytes: markers on
+                                                              the host, Huffman decoding on the host or, with entropy='device', in
+                                                              HIP; IDCT, upsampling and colour in HIP)
   decode_image_features      src/data/data_utils.py:195-222  (`decode_fn` from the encoded bytes or the decoded pixels on, driven by the
                                                               data config: RandAugment and the flip coin when training, then the line below)
   rand_augment(_plan)        src/data/data_utils.py:125-145, 199-202  (`RandAugment(num_layers=1)`, the reference's 14 operations,
@@ -147,17 +148,133 @@ def _is_encoded(item) -> bool:
   return isinstance(item, (bytes, bytearray, memoryview, np.ndarray))
 
 
-def _maybe_decode(images, device):
+def _maybe_decode(images, device, entropy='host'):
   """A list whose items are encoded bytes is decoded first; a list of tensors or a packed tuple passes unchanged."""
   if isinstance(images, tuple):
     return images
   images = list(images)
   if images and all(_is_encoded(im) for im in images):
-    return decode_jpeg_images(images, device)
+    return decode_jpeg_images(images, device, entropy=entropy)
   return images
 
 
-def decode_jpeg_images(data, device, *, workers: int = 8, out: torch.Tensor = None):
+# Defaults of the device entropy decode, from profiles/jpeg_decode_timing.json (DESIGN.md section 4, "JPEG entropy decode
+# on the device"): the fastest of 64 / 128 / 256 / 512 bytes, and the most rounds a file of the set needed (2) plus two.
+JPEG_ENTROPY_SUBSEQ_BYTES = 128
+JPEG_ENTROPY_MAX_ROUNDS = 4
+
+
+def _up16(n: int) -> int:
+  return (n + 15) & ~15
+
+
+def _jpeg_entropy_stage(L, _lib, bufs, images, n_coef, device, workers, subseq_bytes, max_rounds):
+  """The `entropy='device'` stage of decode_jpeg_images: (coef int16 [n_coef], qtab int16 [B * 192]) on `device`.
+  mmt_jpeg_scan_plan per file over the thread pool; file bytes and plans in one buffer (pinned for a GPU) and one upload;
+  mmt_jpeg_entropy (mmt_jpeg_entropy_host for 'cpu'); one read-back of the status words.  A file whose plan was refused
+  or whose status is not 0 goes through mmt_jpeg_coefficients and its planes are copied into the same coef buffer, so the
+  result does not depend on the path a file took; what the host decode refuses raises ValueError as the host path does."""
+  B = len(bufs)
+  on_gpu = device.type == 'cuda'
+  sb, rounds = int(subseq_bytes), int(max_rounds)
+
+  def plan(i):
+    scan = _lib.JpegScan()
+    a = bufs[i]
+    rc = L.mmt_jpeg_scan_plan(a.ctypes.data, a.size, ctypes.byref(images[i]), sb, ctypes.byref(scan), None, None, None, 0, None, 0)
+    if rc != 0:
+      return None
+    huff = np.empty(6 * _lib.MMT_JPEG_HUFF_WORDS, dtype=np.uint32)
+    qt = np.empty(192, dtype=np.uint16)
+    seg = np.empty(scan.n_segments * 4, dtype=np.int32)
+    sub = np.empty(scan.n_subseq, dtype=np.int32)
+    rc = L.mmt_jpeg_scan_plan(a.ctypes.data, a.size, ctypes.byref(images[i]), sb, ctypes.byref(scan), huff.ctypes.data, qt.ctypes.data,
+                              seg.ctypes.data, scan.n_segments, sub.ctypes.data, scan.n_subseq)
+    return None if rc != 0 else (scan, huff, qt, seg, sub)
+
+  if workers == 1 or B == 1:
+    plans = [plan(i) for i in range(B)]
+  else:
+    with ThreadPoolExecutor(max_workers=min(workers, B)) as pool:
+      plans = list(pool.map(plan, range(B)))
+
+  # one buffer: bytes of the planned files | huff | segments | subseqs | scans | images | qtables | (status, device side)
+  scans = (_lib.JpegScan * B)()
+  at_bytes, at_seg, at_sub = 0, 0, 0
+  for i, pl in enumerate(plans):
+    if pl is None:
+      continue                                                  # a zeroed scan: no subsequence, the status word says so
+    scan = pl[0]
+    scan.byte_offset += at_bytes
+    scan.segment_offset, scan.subseq_offset = at_seg, at_sub
+    scans[i] = scan
+    at_bytes += bufs[i].size
+    at_seg += scan.n_segments
+    at_sub += scan.n_subseq
+  planned = [i for i, pl in enumerate(plans) if pl is not None]
+  max_sub = max([plans[i][0].n_subseq for i in planned], default=0)
+  o_huff = _up16(max(at_bytes, 1))
+  o_seg = o_huff + B * 6 * _lib.MMT_JPEG_HUFF_WORDS * 4
+  o_sub = _up16(o_seg + max(at_seg, 1) * 16)
+  o_scan = _up16(o_sub + max(at_sub, 1) * 4)
+  o_img = _up16(o_scan + ctypes.sizeof(scans))
+  o_qt = _up16(o_img + ctypes.sizeof(images))
+  total = _up16(o_qt + B * 384)
+  stage = torch.zeros(total, dtype=torch.uint8, pin_memory=on_gpu)
+  view = stage.numpy()
+  at = 0
+  for i in planned:
+    _, huff, qt, seg, sub = plans[i]
+    view[at:at + bufs[i].size] = bufs[i]
+    at += bufs[i].size
+    view[o_huff + i * huff.nbytes:o_huff + (i + 1) * huff.nbytes] = huff.view(np.uint8)
+    view[o_seg + scans[i].segment_offset * 16:o_seg + scans[i].segment_offset * 16 + seg.nbytes] = seg.view(np.uint8)
+    view[o_sub + scans[i].subseq_offset * 4:o_sub + scans[i].subseq_offset * 4 + sub.nbytes] = sub.view(np.uint8)
+    view[o_qt + i * 384:o_qt + (i + 1) * 384] = qt.view(np.uint8)
+  view[o_scan:o_scan + ctypes.sizeof(scans)] = np.frombuffer(bytes(scans), dtype=np.uint8)
+  view[o_img:o_img + ctypes.sizeof(images)] = np.frombuffer(bytes(images), dtype=np.uint8)
+
+  def host_decode(i):                                           # the host path for one file, into buffers of its own
+    im = _lib.JpegImage.from_buffer_copy(images[i])
+    base = im.coef_offset[0]
+    for c in range(3):
+      im.coef_offset[c] -= base
+    coef = torch.empty(im.coef_elems, dtype=torch.int16, pin_memory=on_gpu)
+    qt = torch.empty(192, dtype=torch.int16, pin_memory=on_gpu)
+    rc = L.mmt_jpeg_coefficients(bufs[i].ctypes.data, bufs[i].size, ctypes.byref(im), coef.data_ptr(), im.coef_elems, qt.data_ptr())
+    if rc != 0:
+      raise ValueError(f'data[{i}] cannot be decoded: {L.mmt_last_error().decode()}')
+    return base, coef, qt
+
+  def run(stage_d, stream):
+    coef_d = torch.empty(n_coef, dtype=torch.int16, device=device)
+    status_d = torch.zeros(B, dtype=torch.int32, device=device)
+    base = stage_d.data_ptr()
+    if planned:
+      need = L.mmt_jpeg_entropy_workspace_bytes(B, at_sub, max_sub, sb, rounds)
+      work = torch.empty(need, dtype=torch.uint8, device=device)
+      args = (B, base, max(at_bytes, 1), base + o_img, base + o_scan, base + o_huff, base + o_seg, max(at_seg, 1), base + o_sub, at_sub,
+              max_sub, sb, rounds, coef_d.data_ptr(), n_coef, status_d.data_ptr(), work.data_ptr(), need)
+      _lib.check(L.mmt_jpeg_entropy(*args, stream) if on_gpu else L.mmt_jpeg_entropy_host(*args))
+      status = status_d.cpu().tolist()                          # the one read-back; waits for the kernels
+    else:
+      status = [0] * B
+    qtab_d = stage_d[o_qt:o_qt + B * 384].view(torch.int16)
+    for i in range(B):
+      if plans[i] is None or status[i] != 0:
+        off, coef, qt = host_decode(i)
+        coef_d[off:off + coef.numel()].copy_(coef, non_blocking=True)
+        qtab_d[i * 192:(i + 1) * 192].copy_(qt, non_blocking=True)
+    return coef_d, qtab_d
+
+  if on_gpu:
+    with torch.cuda.device(device):
+      return run(stage.to(device, non_blocking=True), torch.cuda.current_stream(device).cuda_stream)
+  return run(stage, None)
+
+
+def decode_jpeg_images(data, device, *, workers: int = 8, out: torch.Tensor = None, entropy: str = 'host',
+                       subseq_bytes: int = None, max_rounds: int = None):
   """JPEG files -> the packed (pixels uint8 [n], offsets int64 [B], heights int32 [B], widths int32 [B]) tuple on
   `device` that `rand_augment` and `images_to_patch_features` take; image b is RGB, row-major, back to back.
 
@@ -166,10 +283,27 @@ def decode_jpeg_images(data, device, *, workers: int = 8, out: torch.Tensor = No
   coefficient buffer for the batch (pinned when the device is a GPU); mmt_jpeg_coefficients spread over `workers` threads
   (clamped to 1..16); one asynchronous upload; one mmt_jpeg_pixels.  With device 'cpu' the same buffers go through
   mmt_jpeg_pixels_host.  out: a contiguous uint8 tensor on `device` of at least the needed size (allocated when None;
-  bytes behind the last image are not written).  A file the library refuses raises ValueError naming the example."""
+  bytes behind the last image are not written).  A file the library refuses raises ValueError naming the example.
+
+  entropy: 'host' (the default) is the path above.  'device' uploads the encoded bytes instead of the coefficients and
+  runs the Huffman decode as kernels (mmt_jpeg_scan_plan per file on the thread pool, then mmt_jpeg_entropy in front of
+  mmt_jpeg_pixels on the same stream; with device 'cpu' mmt_jpeg_entropy_host); files it does not serve (more than one
+  scan), files that need more than max_rounds rounds and corrupt files go through the host decode, so pixels and errors
+  are those of 'host'.  'auto' is 'device' on a GPU and 'host' otherwise.  subseq_bytes (a power of two in [8, 1024]) and
+  max_rounds (>= 1) default to JPEG_ENTROPY_SUBSEQ_BYTES and JPEG_ENTROPY_MAX_ROUNDS."""
   from . import _lib
   L = _lib.lib()
   device = torch.device(device)
+  if entropy not in ('host', 'device', 'auto'):
+    raise ValueError(f"entropy must be 'host', 'device' or 'auto', got {entropy!r}")
+  if entropy == 'auto':
+    entropy = 'device' if device.type == 'cuda' else 'host'
+  subseq_bytes = JPEG_ENTROPY_SUBSEQ_BYTES if subseq_bytes is None else int(subseq_bytes)
+  max_rounds = JPEG_ENTROPY_MAX_ROUNDS if max_rounds is None else int(max_rounds)
+  if subseq_bytes < 8 or subseq_bytes > 1024 or subseq_bytes & (subseq_bytes - 1):
+    raise ValueError(f'subseq_bytes must be a power of two in [8, 1024], got {subseq_bytes}')
+  if max_rounds < 1:
+    raise ValueError(f'max_rounds must be at least 1, got {max_rounds}')
   items = list(data)
   B = len(items)
   if B == 0:
@@ -198,6 +332,24 @@ def decode_jpeg_images(data, device, *, workers: int = 8, out: torch.Tensor = No
     hs.append(im.height); ws.append(im.width); offs.append(n_pix)
     n_pix += im.height * im.width * 3
   on_gpu = device.type == 'cuda'
+  if entropy == 'device':
+    coef_t, qtab_t = _jpeg_entropy_stage(L, _lib, bufs, images, n_coef, device, workers, subseq_bytes, max_rounds)
+    if out is None:
+      out = torch.zeros(n_pix, dtype=torch.uint8, device=device)
+    elif out.dtype != torch.uint8 or out.dim() != 1 or out.numel() < n_pix or out.device != device or not out.is_contiguous():
+      raise ValueError(f'out must be a contiguous 1-D uint8 tensor of at least {n_pix} bytes on {device}')
+    need = L.mmt_jpeg_workspace_bytes(n_coef)
+    work = torch.empty(need, dtype=torch.uint8, device=device)
+    if on_gpu:
+      with torch.cuda.device(device):
+        meta_d = torch.frombuffer(bytearray(bytes(images)), dtype=torch.uint8).pin_memory().to(device, non_blocking=True)
+        _lib.check(L.mmt_jpeg_pixels(B, meta_d.data_ptr(), coef_t.data_ptr(), n_coef, qtab_t.data_ptr(), out.data_ptr(), out.numel(),
+                                     work.data_ptr(), need, torch.cuda.current_stream(device).cuda_stream))
+    else:
+      _lib.check(L.mmt_jpeg_pixels_host(B, ctypes.addressof(images), coef_t.data_ptr(), n_coef, qtab_t.data_ptr(), out.data_ptr(),
+                                        out.numel(), work.data_ptr(), need))
+    t = lambda v, dt: torch.tensor(v, dtype=dt).to(device)
+    return out, t(offs, torch.int64), t(hs, torch.int32), t(ws, torch.int32)
   coef = torch.empty(n_coef, dtype=torch.int16, pin_memory=on_gpu)
   qtab = torch.empty(B * 192, dtype=torch.int16, pin_memory=on_gpu)       # uint16 values; torch has no such dtype everywhere
   coef_ptr, qtab_ptr = coef.data_ptr(), qtab.data_ptr()
@@ -238,13 +390,14 @@ def decode_jpeg_images(data, device, *, workers: int = 8, out: torch.Tensor = No
 
 def images_to_patch_features(images, image_size: int, patch_size: int, *, flip: torch.Tensor = None,
                              out_dtype: torch.dtype = torch.float32, keep_unnormalized: bool = False,
-                             output_channel_bits: int = 0, mean=IMAGENET_DEFAULT_MEAN, device=None) -> Dict[str, torch.Tensor]:
+                             output_channel_bits: int = 0, mean=IMAGENET_DEFAULT_MEAN, device=None,
+                             entropy: str = 'host') -> Dict[str, torch.Tensor]:
   """The tensor half of `decode_fn` (src/data/data_utils.py:195-222) for a batch of decoded RGB images of any sizes.
 
   images: list of uint8 [h, w, 3] tensors, or an already packed (pixels uint8 [n], offsets int64 [B], heights int32
   [B], widths int32 [B]) tuple (example b is heights[b] x widths[b] x 3 bytes, row-major, from pixels[offsets[b]]), or a
   list of encoded JPEG files (bytes, bytearray, memoryview, uint8 numpy arrays), which `decode_jpeg_images` decodes first
-  onto `device` (default: the GPU when there is one).
+  onto `device` (default: the GPU when there is one) with its `entropy` mode.
   Per example: x = u8 / 255; bilinear resize to image_size x image_size (tf.image.resize, TF2 defaults);
   patch_embeddings from (r - mean) / mean -- the reference's line 204 divides by the MEAN -- and
   unnormalized_patch_embeddings from r; flip [B] (bool / uint8; the reference's training-time coin, :209-211, as an
@@ -265,7 +418,7 @@ def images_to_patch_features(images, image_size: int, patch_size: int, *, flip: 
     raise ValueError('output_channel_bits must be in [0, 8]')
   if len(mean) != 3 or any(float(m) == 0.0 for m in mean):
     raise ValueError('mean must be three non-zero numbers')
-  images = _maybe_decode(images, _default_device(device))
+  images = _maybe_decode(images, _default_device(device), entropy)
   pixels, offsets, heights, widths = _check_packed(images) if isinstance(images, tuple) else _pack_images(list(images))
   B, dev = offsets.shape[0], pixels.device
   if flip is not None:
@@ -486,17 +639,17 @@ def rand_augment(images, op: torch.Tensor, arg: torch.Tensor, out: torch.Tensor 
 
 def decode_image_features(data_config, images, *, generator: torch.Generator = None,
                           out_dtype: torch.dtype = torch.float32, keep_unnormalized: bool = False,
-                          device=None) -> Dict[str, torch.Tensor]:
+                          device=None, entropy: str = 'host') -> Dict[str, torch.Tensor]:
   """`decode_fn` (src/data/data_utils.py:195-222) as the data config drives it.  images: a list of uint8 [h, w, 3] tensors,
   a packed tuple, or a list of encoded JPEG files, which `decode_jpeg_images` decodes first onto `device` (default: the
-  GPU when there is one):
+  GPU when there is one; `entropy` is its mode):
     is_training and use_rand_aug   `rand_augment` with a `rand_augment_plan` drawn from `generator`      (:199-202)
     is_training                    one flip coin per example, flipped when u > 0.5                        (:209-211)
     then `images_to_patch_features` with the config's image_size, patch_size and, where the config has the field,
     output_channel_bits (the pretraining loader's MPP ids).
   Draws come from `generator` in this order: operation ids, signs, flip coins.  With is_training false the result is
   `images_to_patch_features(images, image_size, patch_size, ...)` bit for bit."""
-  images = _maybe_decode(images, _default_device(device))
+  images = _maybe_decode(images, _default_device(device), entropy)
   packed = _check_packed(images) if isinstance(images, tuple) else _pack_images(list(images))
   pixels, offsets, heights, widths = packed
   flip = None

@@ -9,6 +9,12 @@ Reported:
   upload   bytes of coefficients, tables and metadata the device stage takes, against the decoded pixels' bytes
   device   mmt_jpeg_pixels by HIP events: warm-up, then rounds of calls; median and range over the rounds
   pillow   where Pillow is installed: its decode of the same files in one thread plus the upload of the pixels
+  entropy  the device entropy decode (csrc/jpeg_entropy.hip) on the same files, for subseq_bytes 64, 128, 256 and 512:
+           mmt_jpeg_scan_plan over the batch at workers 1, 8 and 16; the upload of the file bytes and plans; the rounds
+           each file needed (a call with a generous max_rounds, then the per-round changed words), as a histogram;
+           mmt_jpeg_entropy by HIP events at max_rounds = the most any file needed + 2; and that sum against the host
+           decode at 16 workers plus its coefficient upload, from this same run.  The coefficients are checked against
+           mmt_jpeg_coefficients' before anything is timed.
 
 A record, not a gate: nothing is asserted on the times.  Writes one JSON record (--out)."""
 import argparse
@@ -154,6 +160,111 @@ def encode_jpeg(rgb, quality=90):
   return out + data.tobytes() + b'\xff\xd9'
 
 
+def entropy_leg(torch, _lib, L, bufs, images, n_coef, coef_d, dev, args):
+  """The device entropy decode of the batch; coef_d: the host decode's coefficients on the device, the yardstick."""
+  B = len(bufs)
+  img_d = torch.frombuffer(bytearray(bytes(images)), dtype=torch.uint8).to(dev)
+  e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+  stream = torch.cuda.current_stream(dev).cuda_stream
+  generous = 64
+  out = {}
+  for sb in (64, 128, 256, 512):
+    def plan(i):
+      a, scan = bufs[i], _lib.JpegScan()
+      _lib.check(L.mmt_jpeg_scan_plan(a.ctypes.data, a.size, ctypes.byref(images[i]), sb, ctypes.byref(scan), None, None, None, 0, None, 0))
+      huff, qt = np.empty(6 * _lib.MMT_JPEG_HUFF_WORDS, dtype=np.uint32), np.empty(192, dtype=np.uint16)
+      seg, sub = np.empty(scan.n_segments * 4, dtype=np.int32), np.empty(scan.n_subseq, dtype=np.int32)
+      _lib.check(L.mmt_jpeg_scan_plan(a.ctypes.data, a.size, ctypes.byref(images[i]), sb, ctypes.byref(scan), huff.ctypes.data, qt.ctypes.data,
+                                      seg.ctypes.data, scan.n_segments, sub.ctypes.data, scan.n_subseq))
+      return scan, huff, qt, seg, sub
+
+    plan_ms = {}
+    for workers in (1, 8, 16):
+      best = None
+      for _ in range(args.host_rounds):
+        t0 = time.perf_counter()
+        if workers == 1:
+          plans = [plan(i) for i in range(B)]
+        else:
+          with ThreadPoolExecutor(max_workers=workers) as pool:
+            plans = list(pool.map(plan, range(B)))
+        dt = time.perf_counter() - t0
+        best = dt if best is None else min(best, dt)
+      plan_ms[str(workers)] = round(best * 1e3, 2)
+    scans = (_lib.JpegScan * B)()
+    at_b = at_seg = at_sub = 0
+    for i, (scan, _, _, _, _) in enumerate(plans):
+      scan.byte_offset += at_b
+      scan.segment_offset, scan.subseq_offset = at_seg, at_sub
+      scans[i] = scan
+      at_b += bufs[i].size; at_seg += scan.n_segments; at_sub += scan.n_subseq
+    max_sub = max(sc.n_subseq for sc in scans)
+    pin = lambda a: torch.from_numpy(np.array(a, copy=True).view(np.uint8)).pin_memory()
+    host_parts = [pin(np.concatenate(bufs)), pin(np.concatenate([pl[1] for pl in plans])), pin(np.concatenate([pl[3] for pl in plans])),
+                  pin(np.concatenate([pl[4] for pl in plans])), pin(np.frombuffer(bytes(scans), dtype=np.uint8))]
+    dev_parts = [torch.empty(h.numel() + 16, dtype=torch.uint8, device=dev)[:h.numel()] for h in host_parts]
+    ups = []
+    for _ in range(5):
+      e0.record()
+      for d, h in zip(dev_parts, host_parts):
+        d.copy_(h, non_blocking=True)
+      e1.record()
+      torch.cuda.synchronize()
+      ups.append(e0.elapsed_time(e1) * 1e3)
+    bytes_d, huff_d, seg_d, sub_d, scan_d = dev_parts
+    coef_e = torch.empty(n_coef, dtype=torch.int16, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+
+    def call(rounds, ws):
+      _lib.check(L.mmt_jpeg_entropy(B, bytes_d.data_ptr(), at_b, img_d.data_ptr(), scan_d.data_ptr(), huff_d.data_ptr(), seg_d.data_ptr(),
+                                    at_seg, sub_d.data_ptr(), at_sub, max_sub, sb, rounds, coef_e.data_ptr(), n_coef, status.data_ptr(),
+                                    ws.data_ptr(), ws.numel(), stream))
+
+    ws = torch.empty(L.mmt_jpeg_entropy_workspace_bytes(B, at_sub, max_sub, sb, generous), dtype=torch.uint8, device=dev)
+    coef_e.fill_(0x5555)
+    call(generous, ws)
+    torch.cuda.synchronize()
+    assert int(status.abs().max()) == 0, status.tolist()
+    assert torch.equal(coef_e, coef_d), 'the device entropy decode differs from mmt_jpeg_coefficients'
+    changed = ws[:generous * B * 4].view(torch.int32).reshape(generous, B).cpu().numpy()
+    needed = [int(np.nonzero(changed[:, b])[0].max()) + 1 for b in range(B)]         # rounds that changed a state of the file
+    most = max(needed)
+    assert most < generous
+    call(most, ws)                                              # the smallest max_rounds at which no file falls back
+    torch.cuda.synchronize()
+    assert int(status.abs().max()) == 0, (most, status.tolist())
+    fallbacks_below = 0
+    if most > 1:
+      call(most - 1, ws)
+      torch.cuda.synchronize()
+      fallbacks_below = int((status != 0).sum())
+    rounds = most + 2
+    ws = torch.empty(L.mmt_jpeg_entropy_workspace_bytes(B, at_sub, max_sub, sb, rounds), dtype=torch.uint8, device=dev)
+    for _ in range(3):
+      call(rounds, ws)
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(args.rounds):
+      e0.record()
+      for _ in range(args.calls):
+        call(rounds, ws)
+      e1.record()
+      torch.cuda.synchronize()
+      ts.append(e0.elapsed_time(e1) / args.calls * 1e3)
+    assert int(status.abs().max()) == 0 and torch.equal(coef_e, coef_d)
+    med = statistics.median(ts)
+    out[str(sb)] = {
+        'plan_ms_by_workers': plan_ms, 'upload_bytes': sum(h.numel() for h in host_parts), 'upload_us_median': round(statistics.median(ups), 1),
+        'subsequences': at_sub, 'segments': at_seg, 'rounds_needed_histogram': {str(k): needed.count(k) for k in sorted(set(needed))},
+        'smallest_max_rounds_without_fallback': most, 'files_falling_back_one_round_below': fallbacks_below, 'max_rounds_timed': rounds,
+        'launches': rounds + 5, 'entropy_us_median': round(med, 1), 'entropy_us_min': round(min(ts), 1), 'entropy_us_max': round(max(ts), 1),
+        'workspace_bytes': ws.numel()}
+    print(f'  device entropy, subseq_bytes {sb:>3}: plan {plan_ms["1"]} / {plan_ms["8"]} / {plan_ms["16"]} ms at 1 / 8 / 16 workers, upload '
+          f'{out[str(sb)]["upload_us_median"]} us, rounds needed {out[str(sb)]["rounds_needed_histogram"]}, mmt_jpeg_entropy {round(med, 1)} us '
+          f'({round(min(ts), 1)}..{round(max(ts), 1)}) at max_rounds {rounds}')
+  return out
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--batch', type=int, default=64)
@@ -257,7 +368,19 @@ def main():
 
   record = {'device': torch.cuda.get_device_name(0), 'shape': dict(B=B, size=S, quality=args.quality, sampling='4:2:0', distinct=len(distinct)),
             'host_entropy_decode': host, 'upload': upload, 'device_stage': device, 'rounds': args.rounds, 'calls_per_round': args.calls}
+  record['device_entropy'] = entropy_leg(torch, _lib, L, bufs, images, n_coef, coef_d, dev, args)
+  fastest = min(record['device_entropy'], key=lambda k: record['device_entropy'][k]['entropy_us_median'])
+  best = record['device_entropy'][fastest]
+  record['device_entropy_summary'] = {
+      'fastest_subseq_bytes': int(fastest), 'max_rounds_default': best['smallest_max_rounds_without_fallback'] + 2,
+      'host_path_ms': round(host['16']['batch_ms'] + upload['us_median'] / 1e3, 2),
+      'device_path_ms': round(best['plan_ms_by_workers']['16'] + (best['upload_us_median'] + best['entropy_us_median']) / 1e3, 2),
+      'note': 'host_path: mmt_jpeg_coefficients at 16 workers + coefficient upload; device_path: mmt_jpeg_scan_plan at 16 workers + upload of '
+              'bytes and plans + mmt_jpeg_entropy; both in front of the same mmt_jpeg_pixels'}
+  print('  ', record['device_entropy_summary'])
   got = fp.decode_jpeg_images(files[:2], dev)[0].cpu().numpy()
+  got_device = fp.decode_jpeg_images(files[:2], dev, entropy='device')[0].cpu().numpy()
+  assert np.array_equal(got, got_device), "entropy='device' differs from entropy='host'"
   try:
     from PIL import Image
   except ImportError:

@@ -589,6 +589,69 @@ int mmt_jpeg_entropy_host(int32_t B, const uint8_t* bytes, int64_t bytes_len, co
                           int32_t max_rounds, int16_t* coef, int64_t coef_elems, int32_t* status, void* workspace,
                           size_t workspace_bytes);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Record container of the data layer (csrc/records.hip; DESIGN.md section 4, "Records"): the TFRecord frames and the
+ * tf.train.Example fields that src/data/pretrain_dataloader.py:62-72 reads.
+ *
+ * A frame is  uint64 length (little endian) | uint32 masked_crc32c(the 8 length bytes) | length payload bytes |
+ * uint32 masked_crc32c(payload), with CRC-32C (Castagnoli, reflected 0x82F63B78, init and final xor 0xFFFFFFFF) and
+ * mask(c) = ((c >> 15 | c << 17) + 0xa282ead8) mod 2^32.
+ *
+ * The two host calls are plain C++: re-entrant, they allocate nothing that outlives the call and never read past len;
+ * errors go through mmt_last_error with the byte offset.
+ *
+ * mmt_records_scan walks frames from offset 0 and writes one mmt_record per whole frame.  The length checksum is
+ * verified (wrong: MMT_E_INVALID -- there is no resynchronisation); the payload checksum is only copied out, it is
+ * verified by mmt_records_crc.  A frame that does not fit in the remaining bytes, or a full records_out, ends the walk:
+ * *consumed_out is that frame's first byte (len when every byte was consumed), so a chunked reader continues there.
+ * The fit test cannot wrap for a declared length near 2^64.
+ *
+ * mmt_example_fields looks n_names features (NUL-terminated names) up in one serialized tf.train.Example
+ * (Example.features = 1; Features.feature = 1, a map entry key = 1 / value = 2; Feature.bytes_list = 1, float_list = 2,
+ * int64_list = 3; value = 1 in each list; int64 and float lists packed or unpacked; varints of up to 10 bytes; unknown
+ * fields of wire types 0, 1, 2 and 5 skipped).  Groups, a length that leaves its enclosing message, a truncated or
+ * 11-byte varint and a packed float list whose length is no multiple of 4 are MMT_E_INVALID.  Repeated `features`
+ * merge, a repeated key keeps its last value, a Feature with no kind set counts as missing. */
+#define MMT_FIELD_MISSING 0
+#define MMT_FIELD_BYTES 1
+#define MMT_FIELD_INT64 2
+#define MMT_FIELD_FLOAT 3
+typedef struct mmt_record {
+  int64_t offset;          /* of the payload, from the start of the scanned bytes */
+  int64_t length;          /* of the payload */
+  uint32_t crc;            /* the stored (masked) payload checksum */
+  uint32_t reserved;
+} mmt_record;
+typedef struct mmt_example_field {
+  int32_t kind;            /* MMT_FIELD_* */
+  float float_value;       /* the first value of a float list */
+  int64_t count;           /* number of values */
+  int64_t offset, length;  /* the first value of a bytes list, inside payload */
+  int64_t int_value;       /* the first value of an int64 list */
+} mmt_example_field;
+int mmt_records_scan(const uint8_t* bytes, int64_t len, mmt_record* records_out, int64_t capacity, int64_t* n_out,
+                     int64_t* consumed_out);
+int mmt_example_fields(const uint8_t* payload, int64_t len, int32_t n_names, const char* const* names,
+                       mmt_example_field* fields_out /* [n_names] */);
+
+/* Payload checksums on the device: crc_out[i] = CRC-32C (unmasked) of records[i]'s payload inside bytes, bad_out[i] =
+ * (mask(crc_out[i]) != records[i].crc).  DEVICE memory throughout (records 8-byte, crc_out and bad_out 4-byte, the
+ * workspace of mmt_records_crc_workspace_bytes(n) 16-byte aligned; bytes at any alignment); nothing is allocated, the
+ * host does not wait, and the three launches (piece counts and their prefix sum, the pieces, the comparison) and their
+ * grids depend on bytes_len and n alone, so the call can be recorded into a graph.  Work is cut by bytes: every payload
+ * into pieces of MMT_RECORDS_PIECE bytes counted from its END (so only a record's first piece is short), a lane takes a
+ * piece, a workgroup MMT_RECORDS_PART bytes of pieces, which may belong to many records; pieces are joined with
+ * raw(a||b) = shift(raw(a), |b|) ^ raw(b).  The same bytes give the same words.  Offsets and lengths are clamped into
+ * [0, bytes_len] and nothing at or beyond bytes_len is read, also not by a wide load, whatever the records say; records
+ * may overlap.  n = 0 is allowed.  The host variant runs the same functions (csrc/records.h) over HOST memory. */
+#define MMT_RECORDS_PIECE 128
+#define MMT_RECORDS_PART (256 * MMT_RECORDS_PIECE)
+size_t mmt_records_crc_workspace_bytes(int64_t n);    /* host only; 0 for n outside [0, 2^31) */
+int mmt_records_crc(const uint8_t* bytes, int64_t bytes_len, int64_t n, const mmt_record* records, uint32_t* crc_out,
+                    int32_t* bad_out, void* workspace, size_t workspace_bytes, void* stream);
+int mmt_records_crc_host(const uint8_t* bytes, int64_t bytes_len, int64_t n, const mmt_record* records,
+                         uint32_t* crc_out, int32_t* bad_out, void* workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

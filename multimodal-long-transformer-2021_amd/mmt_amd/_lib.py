@@ -50,7 +50,8 @@ EXPORTS = ('mmt_abi_version', 'mmt_last_error', 'mmt_write_step_scalars', 'mmt_w
            'mmt_image_patches', 'mmt_rand_augment_workspace_bytes', 'mmt_rand_augment',
            'mmt_wordpiece_vocab_bytes', 'mmt_wordpiece_vocab_build', 'mmt_text_tokens_workspace_bytes', 'mmt_text_tokens',
            'mmt_jpeg_info', 'mmt_jpeg_coefficients', 'mmt_jpeg_workspace_bytes', 'mmt_jpeg_pixels', 'mmt_jpeg_pixels_host',
-           'mmt_jpeg_scan_plan', 'mmt_jpeg_entropy_workspace_bytes', 'mmt_jpeg_entropy', 'mmt_jpeg_entropy_host')
+           'mmt_jpeg_scan_plan', 'mmt_jpeg_entropy_workspace_bytes', 'mmt_jpeg_entropy', 'mmt_jpeg_entropy_host',
+           'mmt_records_scan', 'mmt_example_fields', 'mmt_records_crc_workspace_bytes', 'mmt_records_crc', 'mmt_records_crc_host')
 
 
 class EmbedDesc(ctypes.Structure):
@@ -117,6 +118,20 @@ class JpegScan(ctypes.Structure):
               ('max_segment_subseq', ctypes.c_int32), ('components', ctypes.c_int32), ('dc_table', ctypes.c_int32 * 3),
               ('ac_table', ctypes.c_int32 * 3), ('restart_interval', ctypes.c_int32), ('mcus', ctypes.c_int32),
               ('subseq_bytes', ctypes.c_int32), ('uniform_tables', ctypes.c_int32)]
+
+
+MMT_FIELD_MISSING, MMT_FIELD_BYTES, MMT_FIELD_INT64, MMT_FIELD_FLOAT = 0, 1, 2, 3
+MMT_RECORDS_PIECE = 128                  # bytes a lane of mmt_records_crc takes
+MMT_RECORDS_PART = 256 * MMT_RECORDS_PIECE   # bytes of pieces a workgroup takes
+
+
+class Record(ctypes.Structure):
+  _fields_ = [('offset', ctypes.c_int64), ('length', ctypes.c_int64), ('crc', ctypes.c_uint32), ('reserved', ctypes.c_uint32)]
+
+
+class ExampleField(ctypes.Structure):
+  _fields_ = [('kind', ctypes.c_int32), ('float_value', ctypes.c_float), ('count', ctypes.c_int64), ('offset', ctypes.c_int64),
+              ('length', ctypes.c_int64), ('int_value', ctypes.c_int64)]
 
 
 class WgradProblem(ctypes.Structure):
@@ -290,6 +305,16 @@ def lib() -> ctypes.CDLL:
   L.mmt_jpeg_entropy.argtypes = entropy_args + [vp]
   L.mmt_jpeg_entropy_host.restype = ctypes.c_int
   L.mmt_jpeg_entropy_host.argtypes = entropy_args
+  L.mmt_records_scan.restype = ctypes.c_int
+  L.mmt_records_scan.argtypes = [vp, i64, vp, i64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
+  L.mmt_example_fields.restype = ctypes.c_int
+  L.mmt_example_fields.argtypes = [vp, i64, ctypes.c_int32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ExampleField)]
+  L.mmt_records_crc_workspace_bytes.restype = ctypes.c_size_t
+  L.mmt_records_crc_workspace_bytes.argtypes = [i64]
+  L.mmt_records_crc.restype = ctypes.c_int
+  L.mmt_records_crc.argtypes = [vp, i64, i64, vp, vp, vp, vp, ctypes.c_size_t, vp]
+  L.mmt_records_crc_host.restype = ctypes.c_int
+  L.mmt_records_crc_host.argtypes = [vp, i64, i64, vp, vp, vp, vp, ctypes.c_size_t]
   L.mmt_write_step_scalars.restype = ctypes.c_int
   L.mmt_write_step_scalars.argtypes = [vp, vp, ctypes.c_uint64, ctypes.c_float, ctypes.c_float, ctypes.c_float, vp]
   if L.mmt_abi_version() != MMT_ABI_VERSION:

@@ -19,7 +19,8 @@ The text half of `decode_fn` (:241-278: WordPiece tokenisation, trim, field toke
 mmt_amd/text_frontend.py (`decode_text_features`, HIP: csrc/text_tokens.hip); its outputs are the text_token_ids,
 num_text_wordpieces and text_word_start that `make_mlm_and_mpp_features` below takes.
 JPEG decode (baseline and extended sequential files; DESIGN.md section 4 lists what is accepted) is `decode_jpeg_images`;
-other file formats and the TFRecord container stay out of scope."""
+other image file formats stay out of scope.  The TFRecord container in front of all of this, and
+the loader that strings these stages together, are mmt_amd/records.py and mmt_amd/pretrain_dataloader.py."""
 from __future__ import annotations
 
 import ctypes
@@ -148,13 +149,13 @@ def _is_encoded(item) -> bool:
   return isinstance(item, (bytes, bytearray, memoryview, np.ndarray))
 
 
-def _maybe_decode(images, device, entropy='host'):
+def _maybe_decode(images, device, entropy='host', uploaded=None):
   """A list whose items are encoded bytes is decoded first; a list of tensors or a packed tuple passes unchanged."""
   if isinstance(images, tuple):
     return images
   images = list(images)
   if images and all(_is_encoded(im) for im in images):
-    return decode_jpeg_images(images, device, entropy=entropy)
+    return decode_jpeg_images(images, device, entropy=entropy, uploaded=uploaded)
   return images
 
 
@@ -168,12 +169,14 @@ def _up16(n: int) -> int:
   return (n + 15) & ~15
 
 
-def _jpeg_entropy_stage(L, _lib, bufs, images, n_coef, device, workers, subseq_bytes, max_rounds):
+def _jpeg_entropy_stage(L, _lib, bufs, images, n_coef, device, workers, subseq_bytes, max_rounds, uploaded=None):
   """The `entropy='device'` stage of decode_jpeg_images: (coef int16 [n_coef], qtab int16 [B * 192]) on `device`.
   mmt_jpeg_scan_plan per file over the thread pool; file bytes and plans in one buffer (pinned for a GPU) and one upload;
   mmt_jpeg_entropy (mmt_jpeg_entropy_host for 'cpu'); one read-back of the status words.  A file whose plan was refused
   or whose status is not 0 goes through mmt_jpeg_coefficients and its planes are copied into the same coef buffer, so the
-  result does not depend on the path a file took; what the host decode refuses raises ValueError as the host path does."""
+  result does not depend on the path a file took; what the host decode refuses raises ValueError as the host path does.
+  uploaded: (bytes uint8 tensor on `device`, offsets): file i already lives at bytes[offsets[i]:] there (the record
+  loader's blob), so the kernels read it in place and only the plans are uploaded."""
   B = len(bufs)
   on_gpu = device.type == 'cuda'
   sb, rounds = int(subseq_bytes), int(max_rounds)
@@ -205,10 +208,11 @@ def _jpeg_entropy_stage(L, _lib, bufs, images, n_coef, device, workers, subseq_b
     if pl is None:
       continue                                                  # a zeroed scan: no subsequence, the status word says so
     scan = pl[0]
-    scan.byte_offset += at_bytes
+    scan.byte_offset += at_bytes if uploaded is None else int(uploaded[1][i])
     scan.segment_offset, scan.subseq_offset = at_seg, at_sub
     scans[i] = scan
-    at_bytes += bufs[i].size
+    if uploaded is None:
+      at_bytes += bufs[i].size
     at_seg += scan.n_segments
     at_sub += scan.n_subseq
   planned = [i for i, pl in enumerate(plans) if pl is not None]
@@ -225,8 +229,9 @@ def _jpeg_entropy_stage(L, _lib, bufs, images, n_coef, device, workers, subseq_b
   at = 0
   for i in planned:
     _, huff, qt, seg, sub = plans[i]
-    view[at:at + bufs[i].size] = bufs[i]
-    at += bufs[i].size
+    if uploaded is None:
+      view[at:at + bufs[i].size] = bufs[i]
+      at += bufs[i].size
     view[o_huff + i * huff.nbytes:o_huff + (i + 1) * huff.nbytes] = huff.view(np.uint8)
     view[o_seg + scans[i].segment_offset * 16:o_seg + scans[i].segment_offset * 16 + seg.nbytes] = seg.view(np.uint8)
     view[o_sub + scans[i].subseq_offset * 4:o_sub + scans[i].subseq_offset * 4 + sub.nbytes] = sub.view(np.uint8)
@@ -253,7 +258,8 @@ def _jpeg_entropy_stage(L, _lib, bufs, images, n_coef, device, workers, subseq_b
     if planned:
       need = L.mmt_jpeg_entropy_workspace_bytes(B, at_sub, max_sub, sb, rounds)
       work = torch.empty(need, dtype=torch.uint8, device=device)
-      args = (B, base, max(at_bytes, 1), base + o_img, base + o_scan, base + o_huff, base + o_seg, max(at_seg, 1), base + o_sub, at_sub,
+      src, src_len = (base, max(at_bytes, 1)) if uploaded is None else (uploaded[0].data_ptr(), uploaded[0].numel())
+      args = (B, src, src_len, base + o_img, base + o_scan, base + o_huff, base + o_seg, max(at_seg, 1), base + o_sub, at_sub,
               max_sub, sb, rounds, coef_d.data_ptr(), n_coef, status_d.data_ptr(), work.data_ptr(), need)
       _lib.check(L.mmt_jpeg_entropy(*args, stream) if on_gpu else L.mmt_jpeg_entropy_host(*args))
       status = status_d.cpu().tolist()                          # the one read-back; waits for the kernels
@@ -274,7 +280,7 @@ def _jpeg_entropy_stage(L, _lib, bufs, images, n_coef, device, workers, subseq_b
 
 
 def decode_jpeg_images(data, device, *, workers: int = 8, out: torch.Tensor = None, entropy: str = 'host',
-                       subseq_bytes: int = None, max_rounds: int = None):
+                       subseq_bytes: int = None, max_rounds: int = None, uploaded=None):
   """JPEG files -> the packed (pixels uint8 [n], offsets int64 [B], heights int32 [B], widths int32 [B]) tuple on
   `device` that `rand_augment` and `images_to_patch_features` take; image b is RGB, row-major, back to back.
 
@@ -290,7 +296,12 @@ def decode_jpeg_images(data, device, *, workers: int = 8, out: torch.Tensor = No
   mmt_jpeg_pixels on the same stream; with device 'cpu' mmt_jpeg_entropy_host); files it does not serve (more than one
   scan), files that need more than max_rounds rounds and corrupt files go through the host decode, so pixels and errors
   are those of 'host'.  'auto' is 'device' on a GPU and 'host' otherwise.  subseq_bytes (a power of two in [8, 1024]) and
-  max_rounds (>= 1) default to JPEG_ENTROPY_SUBSEQ_BYTES and JPEG_ENTROPY_MAX_ROUNDS."""
+  max_rounds (>= 1) default to JPEG_ENTROPY_SUBSEQ_BYTES and JPEG_ENTROPY_MAX_ROUNDS.
+
+  uploaded: None, or (bytes, offsets) -- a 1-D uint8 tensor on `device` (16-byte aligned) that already holds the files,
+  file i at bytes[offsets[i] : offsets[i] + len(data[i])] -- which the device entropy decode then reads in place instead
+  of uploading the files again (the record loader's blob).  `data` still names the host copies: the markers are parsed
+  there.  The host path ignores it."""
   from . import _lib
   L = _lib.lib()
   device = torch.device(device)
@@ -333,7 +344,14 @@ def decode_jpeg_images(data, device, *, workers: int = 8, out: torch.Tensor = No
     n_pix += im.height * im.width * 3
   on_gpu = device.type == 'cuda'
   if entropy == 'device':
-    coef_t, qtab_t = _jpeg_entropy_stage(L, _lib, bufs, images, n_coef, device, workers, subseq_bytes, max_rounds)
+    if uploaded is not None:
+      blob, at = uploaded
+      same = isinstance(blob, torch.Tensor) and blob.device.type == device.type and device.index in (None, blob.device.index)
+      if not same or blob.dtype != torch.uint8 or blob.dim() != 1 or not blob.is_contiguous() or blob.data_ptr() & 15 or len(at) != B:
+        raise ValueError(f'uploaded must be (a contiguous 16-byte aligned 1-D uint8 tensor on {device}, {B} offsets)')
+      if any(int(o) < 0 or int(o) + a.size > blob.numel() for o, a in zip(at, bufs)):
+        raise ValueError('an uploaded file leaves the uploaded bytes')
+    coef_t, qtab_t = _jpeg_entropy_stage(L, _lib, bufs, images, n_coef, device, workers, subseq_bytes, max_rounds, uploaded)
     if out is None:
       out = torch.zeros(n_pix, dtype=torch.uint8, device=device)
     elif out.dtype != torch.uint8 or out.dim() != 1 or out.numel() < n_pix or out.device != device or not out.is_contiguous():
@@ -639,7 +657,7 @@ def rand_augment(images, op: torch.Tensor, arg: torch.Tensor, out: torch.Tensor 
 
 def decode_image_features(data_config, images, *, generator: torch.Generator = None,
                           out_dtype: torch.dtype = torch.float32, keep_unnormalized: bool = False,
-                          device=None, entropy: str = 'host') -> Dict[str, torch.Tensor]:
+                          device=None, entropy: str = 'host', uploaded=None) -> Dict[str, torch.Tensor]:
   """`decode_fn` (src/data/data_utils.py:195-222) as the data config drives it.  images: a list of uint8 [h, w, 3] tensors,
   a packed tuple, or a list of encoded JPEG files, which `decode_jpeg_images` decodes first onto `device` (default: the
   GPU when there is one; `entropy` is its mode):
@@ -648,8 +666,8 @@ def decode_image_features(data_config, images, *, generator: torch.Generator = N
     then `images_to_patch_features` with the config's image_size, patch_size and, where the config has the field,
     output_channel_bits (the pretraining loader's MPP ids).
   Draws come from `generator` in this order: operation ids, signs, flip coins.  With is_training false the result is
-  `images_to_patch_features(images, image_size, patch_size, ...)` bit for bit."""
-  images = _maybe_decode(images, _default_device(device), entropy)
+  `images_to_patch_features(images, image_size, patch_size, ...)` bit for bit.  `uploaded` is `decode_jpeg_images`'s."""
+  images = _maybe_decode(images, _default_device(device), entropy, uploaded)
   packed = _check_packed(images) if isinstance(images, tuple) else _pack_images(list(images))
   pixels, offsets, heights, widths = packed
   flip = None

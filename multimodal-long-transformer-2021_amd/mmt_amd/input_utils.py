@@ -1,6 +1,7 @@
 """Input contract of the models (`src/input_utils.py:21-103`) and the synthetic feature
-generator used instead of the reference's tf.data pipeline (out of scope, SURVEY.md section 2
-row 15; its OUTPUT feature contract is what is kept here)."""
+generator that stands in for the reference's tf.data pipeline wherever no local records are named
+(its OUTPUT feature contract is what is kept here, SURVEY.md 8(d), and
+what `pretrain_dataloader.MmtPretrainDataLoader` produces from TFRecord shards)."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Tuple

@@ -67,11 +67,24 @@ class _TaskBase:
                                  patch_embedding_size=data_cfg.patch_size ** 2 * 3)
 
   def build_inputs(self, params, device='cuda', rank: int = 0, dense_side_inputs: bool = False,
-                   batch_size: Optional[int] = None, ragged: bool = False):
-    """Synthetic stand-in for the tf.data loaders: an endless iterator of (inputs, labels)
-    with the reference's feature contract; per-replica batch = global_batch_size / replicas
-    (`pretrain_dataloader.py:107-108`), seeded per rank."""
+                   batch_size: Optional[int] = None, ragged: bool = False, loader_args: Optional[Dict] = None):
+    """An iterator of (inputs, labels) with the reference's feature contract; per-replica batch =
+    global_batch_size / replicas (`pretrain_dataloader.py:107-108`), seeded per rank.  The pretraining task reads
+    TFRecord shards through `pretrain_dataloader.MmtPretrainDataLoader` when `params.input_path` is a local pattern (no
+    URL scheme) and `params.vocab_filename` names a file; everything else -- the empty path, the `gs://` placeholder of
+    the committed YAMLs, the classification task -- draws the endless synthetic stand-in.  `self.input_source` says
+    which ('records' | 'synthetic'); `loader_args` are keyword arguments of the loader (its shuffle buffer sizes)."""
     per_replica = batch_size or max(1, params.global_batch_size // self.num_replicas)
+    self.input_source = 'synthetic'
+    if isinstance(self, PretrainingTask):
+      from . import pretrain_dataloader
+      if pretrain_dataloader.wants_records(getattr(params, 'input_path', ''), getattr(params, 'vocab_filename', '')):
+        self.input_source = 'records'
+        loader = pretrain_dataloader.MmtPretrainDataLoader(params, device=device, dense_side_inputs=dense_side_inputs,
+                                                           **(loader_args or {}))
+        return loader.load(rank=rank, num_replicas=self.num_replicas, batch_size=per_replica)
+      if params.input_path and '://' not in params.input_path:
+        pretrain_dataloader.check_input_patterns(params.input_path.split(','))     # a local pattern must match, vocabulary or not
     gen = torch.Generator(device=device).manual_seed(1234 + rank)
     vocab = self.task_config.model.encoder.get().vocab_size
     task = 'pretrain' if isinstance(self, PretrainingTask) else 'classification'
@@ -211,7 +224,7 @@ class PretrainingTask(_TaskBase):
     if 'mpp_accuracy' in named:
       named['mpp_accuracy'].update_state(labels['mpp_label_ids'], model_outputs['mpp_logits'], mpp_w,
                                          argmax=model_outputs.get('mpp_argmax'))
-    if 'itm_accuracy' in named and 'itm_logits' in model_outputs:
+    if 'itm_accuracy' in named and 'itm_logits' in model_outputs and 'itm_label_ids' in labels:    # no ITM labels without 'itm' in tasks
       named['itm_accuracy'].update_state(labels['itm_label_ids'], model_outputs['itm_logits'],
                                          labels['itm_label_weights'], argmax=model_outputs.get('itm_argmax'))
 

@@ -1,8 +1,10 @@
 """Training driver with the reference's flag surface (`src/train.py:37-91`):
   python -m mmt_amd.train --experiment mmt/pretraining --mode train --model_dir /tmp/m \\
       --config_file a.yaml --params_override task.train_data.max_seq_len=1024
-Launch one process per GPU (torchrun / torch.distributed.run); data are synthetic
-(`input_utils.synthetic_batch`) -- real-data ingestion is out of scope.
+Launch one process per GPU (torchrun / torch.distributed.run).  The pretraining task trains from TFRecord shards when
+`task.train_data.input_path` is a local file pattern and `task.train_data.vocab_filename` names a vocabulary file
+(`pretrain_dataloader.MmtPretrainDataLoader`); otherwise -- the `gs://` placeholder of the committed YAMLs, an empty
+path, the classification task -- data are synthetic (`input_utils.synthetic_batch`).  One log line says which.
 """
 from __future__ import annotations
 
@@ -36,6 +38,9 @@ def run_experiment(params: configs.ExperimentConfig, mode: str, model_dir: str, 
   reducer = strategy.make_reducer(list(model.parameters()), reduce=tasks.gradient_reduce_mode(params.task))
   optimizer = optimization.create_optimizer(model, opt_cfg, reducer=reducer)
   data = task.build_inputs(params.task.train_data, device=device, rank=strategy.rank)
+  if strategy.rank == 0:
+    print(json.dumps({'input_source': getattr(task, 'input_source', 'synthetic'),
+                      'input_path': params.task.train_data.input_path if getattr(task, 'input_source', '') == 'records' else ''}), flush=True)
   steps = max_steps or params.trainer.train_steps
   logs = []
   start = 0

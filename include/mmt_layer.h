@@ -652,6 +652,69 @@ int mmt_records_crc(const uint8_t* bytes, int64_t bytes_len, int64_t n, const mm
 int mmt_records_crc_host(const uint8_t* bytes, int64_t bytes_len, int64_t n, const mmt_record* records,
                          uint32_t* crc_out, int32_t* bad_out, void* workspace, size_t workspace_bytes);
 
+/* ------------------------------------------------------------------------------------------------
+ * PNG decode in front of the image front end (csrc/png_decode.hip): `tf.io.decode_image(example['image_data'])` of
+ * `decode_fn` (src/data/data_utils.py:195) for PNG bytes, as libpng decodes with palette and low-bit grey expansion and
+ * nothing else (no gamma; ancillary chunks ignored; the rules are DESIGN.md section 4, "PNG decode").  The serial part
+ * -- the chunk walk and DEFLATE, by the library's own inflate -- runs on the host and yields the filtered scanlines;
+ * unfiltering, de-interlacing, bit-depth expansion and the palette lookup run on the device and write the packed
+ * layout of the JPEG calls: image b is height x width x 3 bytes, row-major RGB, from pixels_out + pixel_offset.
+ *
+ * Accepted: colour type 2 at depth 8; colour type 0 (grey: R = G = B, samples scaled by 255 / 85 / 17 / 1) and colour
+ * type 3 (palette; an index beyond the palette's entries gives (0, 0, 0)) at depths 1, 2, 4 and 8; interlace methods 0
+ * and 1 (Adam7); the five filter types; any number of IDAT chunks split anywhere; stored, fixed and dynamic DEFLATE
+ * blocks.  Refused with MMT_E_UNSUPPORTED: depth 16, colour types 4 and 6, a tRNS chunk, an unknown critical chunk, a
+ * compression or filter method other than 0, a width or height above 2^30 (a limit of this decode), and whatever does
+ * not start with the first byte of a PNG.  MMT_E_INVALID: a wrong signature
+ * behind a correct first byte, a CRC-32 mismatch on IHDR / PLTE / IDAT / IEND, truncation, a bad zlib header (preset
+ * dictionary, window above 32 KiB), an invalid DEFLATE stream, an Adler-32 mismatch, inflated data shorter or longer
+ * than IHDR requires, a filter-type byte above 4, a palette file without PLTE, a PLTE of more than 1 << depth entries
+ * or of a length not divisible by 3, a width or height of 0 or above 2^31 - 1.  CRC errors of ancillary chunks and
+ * bytes behind IEND are ignored.
+ *
+ * One struct describes an image to every call.  The info call fills it for a stand-alone image (raw_offset 0,
+ * pixel_offset 0); a caller that batches rebases the two offsets.  raw_bytes is the exact inflated size: per non-empty
+ * pass, rows x (1 + row bytes); the passes follow each other in Adam7 order (one pass without interlace). */
+typedef struct mmt_png_image {
+  int32_t width, height;     /* pixels                                                        */
+  int32_t bit_depth;         /* 1 | 2 | 4 | 8                                                 */
+  int32_t color_type;        /* 0 grey | 2 RGB | 3 palette                                    */
+  int32_t interlace;         /* 0 | 1 (Adam7)                                                 */
+  int32_t palette_entries;   /* entries of PLTE, 0 without one                                */
+  int64_t raw_offset;        /* first byte of the image's filtered scanlines in raw           */
+  int64_t raw_bytes;         /* their exact size                                              */
+  int64_t pixel_offset;      /* first byte of the image in pixels_out                         */
+} mmt_png_image;
+
+/* Host only, no device call, re-entrant, nothing allocated that outlives the call; never reads past len.
+ * The info call walks the chunks up to the first IDAT.  The inflate call concatenates the IDAT payloads logically (no
+ * copy of the file) and inflates them straight into the caller's HOST memory (pinned, if it is to be uploaded) at
+ * raw_out + image->raw_offset; it never writes outside [raw_offset, raw_offset + raw_bytes), which must lie inside
+ * [0, raw_capacity).  `image` must describe this stream (as the info call reported it, offsets rebased at will).  It
+ * checks the Adler-32, the length and every filter-type byte, and walks on to IEND.  palette_out: uint8 [256][3], the
+ * PLTE entries, zero-padded (all zero without a PLTE). */
+int mmt_png_info(const uint8_t* bytes, int64_t len, mmt_png_image* out);
+int mmt_png_inflate(const uint8_t* bytes, int64_t len, const mmt_png_image* image, uint8_t* raw_out,
+                    int64_t raw_capacity, uint8_t* palette_out /* [256][3] */);
+
+/* Stage 2.  The device call takes DEVICE memory throughout (images [B], raw, palettes [B][256][3], pixels_out and the
+ * workspace), allocates nothing and does not wait, so it can be recorded into a graph; one launch whatever B is, no
+ * atomics, no floating point, bitwise reproducible.  raw is only read: a replay without a new upload gives the same
+ * pixels.  The workspace (mmt_png_workspace_bytes(raw_bytes) bytes: the reconstructed last row of a band of 64 rows,
+ * per image and pass) needs no initialisation.  raw_bytes and pixels_bytes in [1, 2^60).  Bytes of pixels_out outside
+ * every image are not written.  The front end's safety rule holds for every read and write: sizes, offsets, the pass
+ * geometry and palette indices that come from `images` or from `raw` are clamped into the buffers, and a filter byte
+ * above 4 counts as None -- wrong metadata gives wrong pixels, not a fault -- and the work of a call is bounded by its
+ * buffer sizes.  The host variant is the same arithmetic as a plain loop over HOST memory (CPU tensors, host tests, the
+ * sanitizer program). */
+size_t mmt_png_workspace_bytes(int64_t raw_bytes);             /* host only; 0 for raw_bytes < 1 */
+int mmt_png_pixels(int32_t B, const mmt_png_image* images, const uint8_t* raw, int64_t raw_bytes,
+                   const uint8_t* palettes, uint8_t* pixels_out, int64_t pixels_bytes, void* workspace,
+                   size_t workspace_bytes, void* stream);
+int mmt_png_pixels_host(int32_t B, const mmt_png_image* images, const uint8_t* raw, int64_t raw_bytes,
+                        const uint8_t* palettes, uint8_t* pixels_out, int64_t pixels_bytes, void* workspace,
+                        size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,7 +51,8 @@ EXPORTS = ('mmt_abi_version', 'mmt_last_error', 'mmt_write_step_scalars', 'mmt_w
            'mmt_wordpiece_vocab_bytes', 'mmt_wordpiece_vocab_build', 'mmt_text_tokens_workspace_bytes', 'mmt_text_tokens',
            'mmt_jpeg_info', 'mmt_jpeg_coefficients', 'mmt_jpeg_workspace_bytes', 'mmt_jpeg_pixels', 'mmt_jpeg_pixels_host',
            'mmt_jpeg_scan_plan', 'mmt_jpeg_entropy_workspace_bytes', 'mmt_jpeg_entropy', 'mmt_jpeg_entropy_host',
-           'mmt_records_scan', 'mmt_example_fields', 'mmt_records_crc_workspace_bytes', 'mmt_records_crc', 'mmt_records_crc_host')
+           'mmt_records_scan', 'mmt_example_fields', 'mmt_records_crc_workspace_bytes', 'mmt_records_crc', 'mmt_records_crc_host',
+           'mmt_png_info', 'mmt_png_inflate', 'mmt_png_workspace_bytes', 'mmt_png_pixels', 'mmt_png_pixels_host')
 
 
 class EmbedDesc(ctypes.Structure):
@@ -118,6 +119,12 @@ class JpegScan(ctypes.Structure):
               ('max_segment_subseq', ctypes.c_int32), ('components', ctypes.c_int32), ('dc_table', ctypes.c_int32 * 3),
               ('ac_table', ctypes.c_int32 * 3), ('restart_interval', ctypes.c_int32), ('mcus', ctypes.c_int32),
               ('subseq_bytes', ctypes.c_int32), ('uniform_tables', ctypes.c_int32)]
+
+
+class PngImage(ctypes.Structure):
+  _fields_ = [('width', ctypes.c_int32), ('height', ctypes.c_int32), ('bit_depth', ctypes.c_int32), ('color_type', ctypes.c_int32),
+              ('interlace', ctypes.c_int32), ('palette_entries', ctypes.c_int32), ('raw_offset', ctypes.c_int64),
+              ('raw_bytes', ctypes.c_int64), ('pixel_offset', ctypes.c_int64)]
 
 
 MMT_FIELD_MISSING, MMT_FIELD_BYTES, MMT_FIELD_INT64, MMT_FIELD_FLOAT = 0, 1, 2, 3
@@ -315,6 +322,17 @@ def lib() -> ctypes.CDLL:
   L.mmt_records_crc.argtypes = [vp, i64, i64, vp, vp, vp, vp, ctypes.c_size_t, vp]
   L.mmt_records_crc_host.restype = ctypes.c_int
   L.mmt_records_crc_host.argtypes = [vp, i64, i64, vp, vp, vp, vp, ctypes.c_size_t]
+  pp = ctypes.POINTER(PngImage)
+  L.mmt_png_info.restype = ctypes.c_int
+  L.mmt_png_info.argtypes = [vp, i64, pp]
+  L.mmt_png_inflate.restype = ctypes.c_int
+  L.mmt_png_inflate.argtypes = [vp, i64, pp, vp, i64, vp]
+  L.mmt_png_workspace_bytes.restype = ctypes.c_size_t
+  L.mmt_png_workspace_bytes.argtypes = [i64]
+  L.mmt_png_pixels.restype = ctypes.c_int
+  L.mmt_png_pixels.argtypes = [ctypes.c_int32, vp, vp, i64, vp, vp, i64, vp, ctypes.c_size_t, vp]
+  L.mmt_png_pixels_host.restype = ctypes.c_int
+  L.mmt_png_pixels_host.argtypes = [ctypes.c_int32, vp, vp, i64, vp, vp, i64, vp, ctypes.c_size_t]
   L.mmt_write_step_scalars.restype = ctypes.c_int
   L.mmt_write_step_scalars.argtypes = [vp, vp, ctypes.c_uint64, ctypes.c_float, ctypes.c_float, ctypes.c_float, vp]
   if L.mmt_abi_version() != MMT_ABI_VERSION:

@@ -5,6 +5,9 @@ tensor transforms the reference runs inside tf.data on the host, as batched torc
   decode_jpeg_images         src/data/data_utils.py:195      (`tf.io.decode_image(example['image_data'])` for JPEG bytes: markers on
                                                               the host, Huffman decoding on the host or, with entropy='device', in
                                                               HIP; IDCT, upsampling and colour in HIP)
+  decode_png_images          src/data/data_utils.py:195      (the same call for PNG bytes: chunk walk and the library's own inflate on
+                                                              the host; unfiltering, de-interlacing, expansion and palette in HIP)
+  decode_images              src/data/data_utils.py:195      (a batch of JPEG and PNG files, each to its decoder by its signature)
   decode_image_features      src/data/data_utils.py:195-222  (`decode_fn` from the encoded bytes or the decoded pixels on, driven by the
                                                               data config: RandAugment and the flip coin when training, then the line below)
   rand_augment(_plan)        src/data/data_utils.py:125-145, 199-202  (`RandAugment(num_layers=1)`, the reference's 14 operations,
@@ -18,8 +21,9 @@ tensor transforms the reference runs inside tf.data on the host, as batched torc
 The text half of `decode_fn` (:241-278: WordPiece tokenisation, trim, field tokens, [SEP], padding, word starts) is
 mmt_amd/text_frontend.py (`decode_text_features`, HIP: csrc/text_tokens.hip); its outputs are the text_token_ids,
 num_text_wordpieces and text_word_start that `make_mlm_and_mpp_features` below takes.
-JPEG decode (baseline and extended sequential files; DESIGN.md section 4 lists what is accepted) is `decode_jpeg_images`;
-other image file formats stay out of scope.  The TFRecord container in front of all of this, and
+JPEG decode (baseline and extended sequential files; DESIGN.md section 4 lists what is accepted) is `decode_jpeg_images`,
+PNG decode (RGB at depth 8, grey and palette at depths 1 to 8; the Fashion-Gen shards) is `decode_png_images`, and
+`decode_images` sends each file of a batch to its decoder by its signature; GIF and BMP stay out of scope.  The TFRecord container in front of all of this, and
 the loader that strings these stages together, are mmt_amd/records.py and mmt_amd/pretrain_dataloader.py."""
 from __future__ import annotations
 
@@ -150,12 +154,13 @@ def _is_encoded(item) -> bool:
 
 
 def _maybe_decode(images, device, entropy='host', uploaded=None):
-  """A list whose items are encoded bytes is decoded first; a list of tensors or a packed tuple passes unchanged."""
+  """A list whose items are encoded bytes (JPEG or PNG files, `decode_images`) is decoded first; a list of tensors or a
+  packed tuple passes unchanged."""
   if isinstance(images, tuple):
     return images
   images = list(images)
   if images and all(_is_encoded(im) for im in images):
-    return decode_jpeg_images(images, device, entropy=entropy, uploaded=uploaded)
+    return decode_images(images, device, entropy=entropy, uploaded=uploaded)
   return images
 
 
@@ -406,6 +411,160 @@ def decode_jpeg_images(data, device, *, workers: int = 8, out: torch.Tensor = No
   return out, t(offs, torch.int64), t(hs, torch.int32), t(ws, torch.int32)
 
 
+# ---------------------------------------------------------------------------------------------------
+# PNG decode (`tf.io.decode_image`, src/data/data_utils.py:195; the Fashion-Gen shards store PNG files): the host walks
+# the chunks and inflates (csrc/png_decode.hip, the library's own inflate; a thread pool spreads the files), the device
+# unfilters, de-interlaces, expands and looks the palette up.  DESIGN.md section 4 "PNG decode" has the rules.
+# ---------------------------------------------------------------------------------------------------
+PNG_SIGNATURE = b'\x89PNG\r\n\x1a\n'
+
+
+def _encoded_arrays(items):
+  bufs = []
+  for i, item in enumerate(items):
+    if not _is_encoded(item):
+      raise ValueError(f'data[{i}] must be bytes, bytearray, memoryview or a uint8 numpy array, got {type(item).__name__}')
+    arr = np.ascontiguousarray(item) if isinstance(item, np.ndarray) else np.frombuffer(item, dtype=np.uint8)
+    if arr.dtype != np.uint8 or arr.ndim != 1:
+      raise ValueError(f'data[{i}] must be a 1-D uint8 array of encoded bytes')
+    bufs.append(arr)
+  return bufs
+
+
+def decode_png_images(data, device, *, workers: int = 8, out: torch.Tensor = None):
+  """PNG files -> the packed (pixels uint8 [n], offsets int64 [B], heights int32 [B], widths int32 [B]) tuple on `device`
+  that `decode_jpeg_images` returns; image b is RGB, row-major, back to back.
+
+  data: a list of bytes, bytearray, memoryview or uint8 numpy arrays, one file each.  libpng's decode with palette and
+  low-bit grey expansion, bit for bit: RGB at depth 8; grey at depths 1, 2, 4, 8 (R = G = B); palette at depths 1, 2, 4, 8
+  (an index beyond the palette's entries gives (0, 0, 0)); both interlace methods; no gamma, ancillary chunks ignored.
+  Per item mmt_png_info; one buffer of filtered scanlines for the batch (pinned when the device is a GPU); mmt_png_inflate
+  spread over `workers` threads (clamped to 1..16); one asynchronous upload of scanlines, palettes and metadata; one
+  mmt_png_pixels.  With device 'cpu' the same buffers go through mmt_png_pixels_host.  out: a contiguous uint8 tensor on
+  `device` of at least the needed size (allocated when None; bytes behind the last image are not written).  A file the
+  library refuses (depth 16, alpha, tRNS, a corrupt or truncated stream) raises ValueError naming the example."""
+  from . import _lib
+  L = _lib.lib()
+  device = torch.device(device)
+  items = list(data)
+  B = len(items)
+  if B == 0:
+    raise ValueError('data is empty')
+  bufs = _encoded_arrays(items)
+  workers = min(max(int(workers), 1), 16)
+  images = (_lib.PngImage * B)()
+  n_raw, n_pix = 0, 0
+  hs, ws, offs = [], [], []
+  for i, arr in enumerate(bufs):
+    rc = L.mmt_png_info(arr.ctypes.data, arr.size, ctypes.byref(images[i]))
+    if rc != 0:
+      raise ValueError(f'data[{i}] cannot be decoded: {L.mmt_last_error().decode()}')
+    im = images[i]
+    im.raw_offset, im.pixel_offset = n_raw, n_pix
+    n_raw += im.raw_bytes
+    hs.append(im.height); ws.append(im.width); offs.append(n_pix)
+    n_pix += im.height * im.width * 3
+  on_gpu = device.type == 'cuda'
+  o_pal = _up16(n_raw)                                           # one buffer: scanlines | palettes | metadata
+  o_img = o_pal + B * 768
+  stage = torch.empty(_up16(o_img + ctypes.sizeof(images)), dtype=torch.uint8, pin_memory=on_gpu)
+  base = stage.data_ptr()
+
+  def inflate(i):                                               # the message is thread-local: read it on the worker
+    rc = L.mmt_png_inflate(bufs[i].ctypes.data, bufs[i].size, ctypes.byref(images[i]), base, n_raw, base + o_pal + i * 768)
+    return None if rc == 0 else L.mmt_last_error().decode()
+
+  if workers == 1 or B == 1:
+    errors = [inflate(i) for i in range(B)]
+  else:
+    with ThreadPoolExecutor(max_workers=min(workers, B)) as pool:
+      errors = list(pool.map(inflate, range(B)))
+  for i, msg in enumerate(errors):
+    if msg is not None:
+      raise ValueError(f'data[{i}] cannot be decoded: {msg}')
+  stage.numpy()[o_img:o_img + ctypes.sizeof(images)] = np.frombuffer(bytes(images), dtype=np.uint8)
+  if out is None:
+    out = torch.zeros(n_pix, dtype=torch.uint8, device=device)
+  elif out.dtype != torch.uint8 or out.dim() != 1 or out.numel() < n_pix or out.device != device or not out.is_contiguous():
+    raise ValueError(f'out must be a contiguous 1-D uint8 tensor of at least {n_pix} bytes on {device}')
+  need = L.mmt_png_workspace_bytes(n_raw)
+  if on_gpu:
+    with torch.cuda.device(device):
+      stage_d = stage.to(device, non_blocking=True)
+      work = torch.empty(need, dtype=torch.uint8, device=device)
+      d = stage_d.data_ptr()
+      _lib.check(L.mmt_png_pixels(B, d + o_img, d, n_raw, d + o_pal, out.data_ptr(), out.numel(), work.data_ptr(), need,
+                                  torch.cuda.current_stream(device).cuda_stream))
+  else:
+    work = torch.empty(need, dtype=torch.uint8)
+    _lib.check(L.mmt_png_pixels_host(B, base + o_img, base, n_raw, base + o_pal, out.data_ptr(), out.numel(), work.data_ptr(), need))
+  t = lambda v, dt: torch.tensor(v, dtype=dt).to(device)
+  return out, t(offs, torch.int64), t(hs, torch.int32), t(ws, torch.int32)
+
+
+def _is_png(item) -> bool:
+  return _is_encoded(item) and bytes(memoryview(item)[:8]) == PNG_SIGNATURE
+
+
+def decode_images(data, device, *, workers: int = 8, out: torch.Tensor = None, entropy: str = 'host', subseq_bytes: int = None,
+                  max_rounds: int = None, uploaded=None):
+  """`tf.io.decode_image` for a list of encoded files, JPEG or PNG each: the packed (pixels, offsets, heights, widths)
+  tuple on `device`, images in the order of `data`.  An item that starts with the 8-byte PNG signature is a PNG file;
+  everything else is taken for a JPEG file (and refused by `decode_jpeg_images` if it is none).
+
+  A list without PNG files goes to `decode_jpeg_images` with exactly the arguments given; a list of PNG files only goes to
+  `decode_png_images` (workers, out).  A mixed list decodes the two groups into disjoint slices of one `out` -- the JPEG
+  files first, then the PNG files -- and returns offsets, heights and widths in the order of `data`; the images are then not
+  in the order of their offsets, which the packed layout allows.  entropy, subseq_bytes and max_rounds are
+  `decode_jpeg_images`'s; `uploaded` offsets are passed on for the JPEG items only.  A refusal names the example by its
+  index in `data`."""
+  items = list(data)
+  png = [i for i, item in enumerate(items) if _is_png(item)]
+  if not png:
+    return decode_jpeg_images(items, device, workers=workers, out=out, entropy=entropy, subseq_bytes=subseq_bytes, max_rounds=max_rounds,
+                              uploaded=uploaded)
+  if len(png) == len(items):
+    return decode_png_images(items, device, workers=workers, out=out)
+  device = torch.device(device)
+  jpg = [i for i in range(len(items)) if i not in set(png)]
+
+  def group(index, call):                                       # a refusal of a group names the example by its place in data
+    try:
+      return call()
+    except ValueError as e:
+      msg = str(e)
+      if msg.startswith('data['):
+        k = int(msg[5:msg.index(']')])
+        raise ValueError(f'data[{index[k]}]' + msg[msg.index(']') + 1:]) from None
+      raise
+
+  up = None if uploaded is None else (uploaded[0], [uploaded[1][i] for i in jpg])
+  jpeg_kw = dict(workers=workers, entropy=entropy, subseq_bytes=subseq_bytes, max_rounds=max_rounds, uploaded=up)
+  if out is None:                                               # the sizes are not known yet: decode, then join
+    a = group(jpg, lambda: decode_jpeg_images([items[i] for i in jpg], device, **jpeg_kw))
+    b = group(png, lambda: decode_png_images([items[i] for i in png], device, workers=workers))
+    pixels = torch.cat([a[0], b[0]])
+  else:
+    if out.dtype != torch.uint8 or out.dim() != 1 or out.device != device or not out.is_contiguous():
+      raise ValueError(f'out must be a contiguous 1-D uint8 tensor on {device}')
+    a = group(jpg, lambda: decode_jpeg_images([items[i] for i in jpg], device, out=out, **jpeg_kw))
+    n_a = int(a[1][-1]) + int(a[2][-1]) * int(a[3][-1]) * 3
+    if out.numel() <= n_a:
+      raise ValueError(f'out must hold more than the {n_a} bytes of the JPEG files')
+    b = group(png, lambda: decode_png_images([items[i] for i in png], device, workers=workers, out=out[n_a:]))
+    pixels = out
+  n_a = int(a[0].numel()) if out is None else n_a
+  B = len(items)
+  order = torch.tensor(jpg + png, dtype=torch.int64, device=device)
+  offsets = torch.empty(B, dtype=torch.int64, device=device)
+  heights = torch.empty(B, dtype=torch.int32, device=device)
+  widths = torch.empty(B, dtype=torch.int32, device=device)
+  offsets[order] = torch.cat([a[1], b[1] + n_a])
+  heights[order] = torch.cat([a[2], b[2]])
+  widths[order] = torch.cat([a[3], b[3]])
+  return pixels, offsets, heights, widths
+
+
 def images_to_patch_features(images, image_size: int, patch_size: int, *, flip: torch.Tensor = None,
                              out_dtype: torch.dtype = torch.float32, keep_unnormalized: bool = False,
                              output_channel_bits: int = 0, mean=IMAGENET_DEFAULT_MEAN, device=None,
@@ -414,8 +573,8 @@ def images_to_patch_features(images, image_size: int, patch_size: int, *, flip: 
 
   images: list of uint8 [h, w, 3] tensors, or an already packed (pixels uint8 [n], offsets int64 [B], heights int32
   [B], widths int32 [B]) tuple (example b is heights[b] x widths[b] x 3 bytes, row-major, from pixels[offsets[b]]), or a
-  list of encoded JPEG files (bytes, bytearray, memoryview, uint8 numpy arrays), which `decode_jpeg_images` decodes first
-  onto `device` (default: the GPU when there is one) with its `entropy` mode.
+  list of encoded JPEG or PNG files (bytes, bytearray, memoryview, uint8 numpy arrays; the two may be mixed), which
+  `decode_images` decodes first onto `device` (default: the GPU when there is one), JPEG files with its `entropy` mode.
   Per example: x = u8 / 255; bilinear resize to image_size x image_size (tf.image.resize, TF2 defaults);
   patch_embeddings from (r - mean) / mean -- the reference's line 204 divides by the MEAN -- and
   unnormalized_patch_embeddings from r; flip [B] (bool / uint8; the reference's training-time coin, :209-211, as an
@@ -659,14 +818,15 @@ def decode_image_features(data_config, images, *, generator: torch.Generator = N
                           out_dtype: torch.dtype = torch.float32, keep_unnormalized: bool = False,
                           device=None, entropy: str = 'host', uploaded=None) -> Dict[str, torch.Tensor]:
   """`decode_fn` (src/data/data_utils.py:195-222) as the data config drives it.  images: a list of uint8 [h, w, 3] tensors,
-  a packed tuple, or a list of encoded JPEG files, which `decode_jpeg_images` decodes first onto `device` (default: the
-  GPU when there is one; `entropy` is its mode):
+  a packed tuple, or a list of encoded JPEG or PNG files, which `decode_images` decodes first onto `device` (default: the
+  GPU when there is one; `entropy` is the JPEG decode's mode):
     is_training and use_rand_aug   `rand_augment` with a `rand_augment_plan` drawn from `generator`      (:199-202)
     is_training                    one flip coin per example, flipped when u > 0.5                        (:209-211)
     then `images_to_patch_features` with the config's image_size, patch_size and, where the config has the field,
     output_channel_bits (the pretraining loader's MPP ids).
   Draws come from `generator` in this order: operation ids, signs, flip coins.  With is_training false the result is
-  `images_to_patch_features(images, image_size, patch_size, ...)` bit for bit.  `uploaded` is `decode_jpeg_images`'s."""
+  `images_to_patch_features(images, image_size, patch_size, ...)` bit for bit.  `uploaded` is `decode_jpeg_images`'s; PNG
+  files do not use it."""
   images = _maybe_decode(images, _default_device(device), entropy, uploaded)
   packed = _check_packed(images) if isinstance(images, tuple) else _pack_images(list(images))
   pixels, offsets, heights, widths = packed

@@ -1,6 +1,6 @@
 """Pretraining loader on TFRecord shards (`MmtPretrainDataLoader`, src/data/pretrain_dataloader.py:74-224): the
 reference's tf.data stages in its order, with the host doing files, frames and field lookup and the device doing
-checksums, JPEG decode, RandAugment, patches, tokenisation, masking, matching and side inputs.  DESIGN.md section 4,
+checksums, JPEG and PNG decode, RandAugment, patches, tokenisation, masking, matching and side inputs.  DESIGN.md section 4,
 "Records", has the stage table against the reference's lines.
 
 tf.data's shuffle order cannot be reproduced (another generator); the contract is that the same seed, rank and files
@@ -71,8 +71,9 @@ class MmtPretrainDataLoader:
 
   params: an `MmtPretrainDataConfig`.  device: where the batches live (a GPU: the side inputs are HIP only).
   shuffle_buffer / example_shuffle_buffer: the record shuffle (host, payloads) and the example shuffle behind the
-  matching step (device) -- 4096 in the reference.  entropy: `decode_jpeg_images`'s mode; 'auto' decodes the Huffman
-  scan on the device from the blob that is uploaded once."""
+  matching step (device) -- 4096 in the reference.  `image_data` may hold JPEG or PNG files, mixed at will
+  (`feature_pipeline.decode_images`).  entropy: `decode_jpeg_images`'s mode; 'auto' decodes the Huffman scan on the device
+  from the blob that is uploaded once; PNG files are inflated on the host and uploaded as scanlines."""
 
   def __init__(self, params, *, device=None, shuffle_buffer: int = 4096, example_shuffle_buffer: int = 4096,
                entropy: str = 'auto', dense_side_inputs: bool = False, chunk_bytes: int = 1 << 22):

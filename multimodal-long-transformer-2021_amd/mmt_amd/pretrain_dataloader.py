@@ -7,65 +7,17 @@ tf.data's shuffle order cannot be reproduced (another generator); the contract i
 give the same batches, and that the stages and their order are the reference's."""
 from __future__ import annotations
 
-import glob
-import json
-import os
-import random
-from typing import Dict, Iterator, List, Optional, Tuple
+from typing import Dict, Optional
 
 import torch
 
 from . import feature_pipeline as fp
-from . import input_utils, records, text_frontend
-from .ops import side_inputs
+from .record_stages import RecordStages, _Pool, check_input_patterns, wants_records      # noqa: F401  (the last two are read through this module)
 
 MIN_TEXT_WORDPIECES = 6               # pretrain_dataloader.py:156
 
 
-def wants_records(input_path: str, vocab_filename: str) -> bool:
-  """Whether `tasks.build_inputs` reads records: a non-empty input_path without a URL scheme, and a vocabulary file.
-  Everything else -- the empty path and the `gs://` placeholder of the committed YAMLs -- stays synthetic; a path with a
-  scheme is never opened."""
-  return bool(input_path) and '://' not in input_path and bool(vocab_filename) and os.path.isfile(vocab_filename)
-
-
-def check_input_patterns(patterns) -> List[str]:
-  """`data_utils.check_input_patterns`: every pattern must match at least one file.  Returns the sorted files."""
-  files: List[str] = []
-  for pattern in patterns:
-    hit = glob.glob(pattern)
-    if not hit:
-      raise ValueError(f'input pattern {pattern!r} matches no file')
-    files.extend(hit)
-  return sorted(files)
-
-
-def _cat(chunks: List[Dict[str, torch.Tensor]]) -> Dict[str, torch.Tensor]:
-  return chunks[0] if len(chunks) == 1 else {k: torch.cat([c[k] for c in chunks]) for k in chunks[0]}
-
-
-class _Pool:
-  """Examples in hand, as one dict of tensors with a common leading dimension."""
-
-  def __init__(self):
-    self.chunks: List[Dict[str, torch.Tensor]] = []
-    self.n = 0
-
-  def push(self, feats: Dict[str, torch.Tensor]):
-    n = next(iter(feats.values())).shape[0]
-    if n:
-      self.chunks.append(feats)
-      self.n += n
-
-  def pop(self, n: int) -> Dict[str, torch.Tensor]:
-    allf = _cat(self.chunks)
-    head = {k: v[:n] for k, v in allf.items()}
-    self.n -= n
-    self.chunks = [{k: v[n:] for k, v in allf.items()}] if self.n else []
-    return head
-
-
-class MmtPretrainDataLoader:
+class MmtPretrainDataLoader(RecordStages):
   """`MmtPretrainDataLoader(params).load(...)`: an iterator of (inputs, labels) with the keys, shapes and dtypes of
   `input_utils.synthetic_batch(task='pretrain')`.
 
@@ -77,132 +29,30 @@ class MmtPretrainDataLoader:
 
   def __init__(self, params, *, device=None, shuffle_buffer: int = 4096, example_shuffle_buffer: int = 4096,
                entropy: str = 'auto', dense_side_inputs: bool = False, chunk_bytes: int = 1 << 22):
-    self.params = params
-    self.device = torch.device(device) if device is not None else torch.device('cuda')
-    self.shuffle_buffer, self.example_shuffle_buffer = int(shuffle_buffer), int(example_shuffle_buffer)
-    self.entropy, self.dense_side_inputs, self.chunk_bytes = entropy, bool(dense_side_inputs), int(chunk_bytes)
-    self.field_dict = json.loads(params.text_special_token_field_dict)
-    if not isinstance(self.field_dict, dict) or not self.field_dict:
-      raise ValueError('text_special_token_field_dict must name at least one field')
+    super().__init__(params, device=device, shuffle_buffer=shuffle_buffer, entropy=entropy, dense_side_inputs=dense_side_inputs,
+                     chunk_bytes=chunk_bytes)
+    self.example_shuffle_buffer = int(example_shuffle_buffer)
     self.names = [params.image_data_field, params.image_key_field] + list(self.field_dict)
-    self._vocab = None
-    self._key_ids: Dict[bytes, int] = {}
 
-  # ---- stage 1: files (:106-130) ----------------------------------------------------------------------------------
-  def files(self) -> List[str]:
-    return check_input_patterns(self.params.input_path.split(','))
-
-  def _file_stream(self, rank: int, num_replicas: int) -> Iterator[str]:
-    files = self.files()
-    if len(files) < num_replicas:
-      raise ValueError(f'{len(files)} input files cannot be sharded over {num_replicas} input pipelines')
-    rng = random.Random(int(self.params.seed))
-    while True:
-      order = list(files)
-      if self.params.is_training:
-        rng.shuffle(order)                                       # every pipeline draws the same order, so the shards are disjoint
-      yield from order[rank::num_replicas] if num_replicas > 1 else order
-      if not self.params.is_training:
-        return
-
-  # ---- stage 2: interleave (:132-135), one record of each of cycle_length files in turn --------------------------------
-  def _interleave(self, file_stream) -> Iterator[Tuple[bytes, int, str, int]]:
-    def open_next():
-      for path in file_stream:
-        return ((p, c, path, i) for i, (p, c) in enumerate(records.read_shard(path, self.chunk_bytes)))
-      return None
-    slots = []
-    for _ in range(max(int(self.params.cycle_length), 1)):
-      it = open_next()
-      if it is None:
-        break
-      slots.append(it)
-    while slots:
-      for s in range(len(slots)):
-        while slots[s] is not None:
-          item = next(slots[s], None)
-          if item is not None:
-            yield item
-            break
-          slots[s] = open_next()
-      slots = [it for it in slots if it is not None]
-
-  # ---- stage 3: record shuffle (:137-138) ----------------------------------------------------------------------------
-  def _shuffle(self, stream, rank: int):
-    if not self.params.is_training or self.shuffle_buffer <= 1:
-      yield from stream
-      return
-    rng = random.Random(int(self.params.seed) * 7919 + rank)
-    buf = []
-    for item in stream:
-      if len(buf) < self.shuffle_buffer:
-        buf.append(item)
-        continue
-      i = rng.randrange(len(buf))
-      buf[i], item = item, buf[i]
-      yield item
-    rng.shuffle(buf)
-    yield from buf
+  # ---- stages 1 to 3 (:106-138): files, interleave and record shuffle are `RecordStages`' -------------------------------
 
   # ---- stage 4: decode on the device (:140-150) ---------------------------------------------------------------------
-  def vocab(self) -> text_frontend.WordpieceVocab:
-    if self._vocab is None:
-      self._vocab = text_frontend.WordpieceVocab(self.params.vocab_filename).to(self.device)
-    return self._vocab
-
-  def _special(self, token: str) -> int:
-    try:
-      return self.vocab().id(token)
-    except KeyError:
-      raise ValueError(f'the vocabulary {self.params.vocab_filename!r} has no token {token!r}') from None
-
   def _decode(self, group, gen) -> Dict[str, torch.Tensor]:
     """One group of (payload, stored crc, file, index) -> the decoded features of its examples on the device."""
-    from . import _lib
     cfg, dev = self.params, self.device
     n = len(group)
-    try:
-      blob, recs, fields = records.pack_records([g[0] for g in group], [g[1] for g in group], self.names)
-    except ValueError as e:
-      i = int(str(e).split()[1])
-      raise ValueError(f'{group[i][2]}: record {group[i][3]}: {e}') from None
-    blob_d = blob.to(dev, non_blocking=True)                    # the one upload of the group's bytes
-    bad = records.payload_checksums(blob_d, recs, n).cpu()
-    if bool(bad.any()):
-      i = int(torch.nonzero(bad)[0])
-      raise ValueError(f'{group[i][2]}: record {group[i][3]}: the payload checksum does not match (corrupt record)')
-    view = blob.numpy()
-    images, image_at, keys, t_off, t_len = [], [], [], [], []
-    for i, f in enumerate(fields):
-      for j, what in ((0, cfg.image_data_field), (1, cfg.image_key_field)):
-        if f[j].kind != _lib.MMT_FIELD_BYTES or f[j].count != 1:
-          raise ValueError(f'{group[i][2]}: record {group[i][3]}: feature {what!r} must hold exactly one bytes value')
-      images.append(view[f[0].offset:f[0].offset + f[0].length])
-      image_at.append(int(f[0].offset))
-      key = view[f[1].offset:f[1].offset + f[1].length].tobytes()
-      keys.append(self._key_ids.setdefault(key, len(self._key_ids)))
-      for j, name in enumerate(self.field_dict, start=2):
-        if f[j].kind == _lib.MMT_FIELD_MISSING or (f[j].kind == _lib.MMT_FIELD_BYTES and f[j].count == 0):
-          t_off.append(0); t_len.append(0)                       # FixedLenFeature(default_value='')
-        elif f[j].kind != _lib.MMT_FIELD_BYTES or f[j].count != 1:
-          raise ValueError(f'{group[i][2]}: record {group[i][3]}: text feature {name!r} must hold one bytes value')
-        else:
-          t_off.append(int(f[j].offset)); t_len.append(int(f[j].length))
+    blob, blob_d, fields = self._open_group(group, self.names)
+    images, image_at, keys, t_off, t_len = self._image_key_text_fields(group, blob.numpy(), fields)
     try:
       im = fp.decode_image_features(cfg, images, generator=gen, keep_unnormalized=True, device=dev, entropy=self.entropy,
                                     uploaded=(blob_d, image_at))
     except ValueError as e:
       raise ValueError(f'{group[0][2]} (records from {group[0][3]}): {e}') from None
-    meta = lambda v, dt: torch.tensor(v, dtype=dt).to(dev)
-    tx = text_frontend.decode_text_features(cfg, self.vocab(), (blob_d, meta(t_off, torch.int64), meta(t_len, torch.int32)))
-    P2 = im['patch_embeddings'].shape[1]
-    ptok = torch.empty(n, 2 + P2, dtype=torch.int32, device=dev)
-    ptok[:, 0], ptok[:, 1] = self._special('[CLS]'), self._special('[PATCH]')
-    ptok[:, 2:] = input_utils.PATCH_START_UNUSED_INDEX + torch.arange(P2, dtype=torch.int32, device=dev)
-    return {'patch_token_ids': ptok, 'patch_embeddings': im['patch_embeddings'],
+    tx = self._decode_texts(blob_d, t_off, t_len)
+    return {'patch_token_ids': self._patch_token_ids(n, im['patch_embeddings'].shape[1]), 'patch_embeddings': im['patch_embeddings'],
             'unnormalized_patch_embeddings': im['unnormalized_patch_embeddings'],
             'text_token_ids': tx['text_token_ids'], 'num_text_wordpieces': tx['num_text_wordpieces'],
-            'text_word_start': tx['text_word_start'], 'image_key': meta(keys, torch.int64)}
+            'text_word_start': tx['text_word_start'], 'image_key': self._meta(keys, torch.int64)}
 
   # ---- stage 6: masking (:165-181) ------------------------------------------------------------------------------------
   def _mask(self, feats, gen) -> Dict[str, torch.Tensor]:
@@ -234,25 +84,7 @@ class MmtPretrainDataLoader:
 
   # ---- stage 8: side inputs and the split (:199-221), as synthetic_batch builds them ------------------------------------
   def _finish(self, ex, with_itm: bool):
-    cfg, dev = self.params, self.device
-    S = cfg.max_seq_len
-    B, W = ex['patch_token_ids'].shape
-    n_image = torch.full((B,), W, device=dev, dtype=torch.int32)
-    n_text = ex['num_text_wordpieces'].to(torch.int32)
-    pattern = input_utils.attention_pattern_from_config(cfg)
-    inputs = {'word_ids': torch.cat([ex['patch_token_ids'], ex['text_token_ids']], dim=1),       # make_word_ids_features
-              'patch_embeddings': ex['patch_embeddings']}
-    if self.dense_side_inputs:
-      si = side_inputs(pattern, n_image, n_text, S,
-                       materialize_pattern=pattern.local_radius < S or pattern.n_global > 0 or pattern.grid_radius > 0)
-      inputs.update(si)
-      if si['relative_att_ids'] is None:
-        inputs.pop('relative_att_ids')
-    else:
-      si = side_inputs(pattern, n_image, n_text, S, want_mask=False, want_ids=False)
-      inputs['segment_ids'] = si['segment_ids']
-      inputs['attention_pattern'] = pattern
-      inputs['valid_len'] = (n_image + n_text).to(torch.int32)
+    inputs = self._encoder_inputs(ex)
     inputs.update(mlm_positions=ex['mlm_positions'], mpp_positions=ex['mpp_positions'])
     labels = {k: ex[k] for k in ('mlm_label_ids', 'mlm_label_weights', 'mpp_label_ids', 'mpp_label_weights')}
     if with_itm:
@@ -297,30 +129,9 @@ class MmtPretrainDataLoader:
         yield self._mask(pool.pop(pool.n), gen)
 
     def shuffled():                                              # :214-215, on the device
-      N = self.example_shuffle_buffer
-      if not (with_itm and training) or N <= 1:
-        yield from matched()
-        return
-      held, count = None, 0
-      for ex in matched():
-        m = next(iter(ex.values())).shape[0]
-        while m:
-          if count < N:                                          # filling
-            take = min(N - count, m)
-            head = {k: v[:take] for k, v in ex.items()}
-            held = head if held is None else _cat([held, head])
-            count += take
-          else:                                                  # full: every newcomer takes a random place and frees its holder
-            take = min(m, N)
-            slots = torch.randperm(N, generator=gen, device=dev)[:take]
-            yield {k: v[slots] for k, v in held.items()}
-            for k in held:
-              held[k][slots] = ex[k][:take]
-          ex = {k: v[take:] for k, v in ex.items()}
-          m -= take
-      if held is not None:
-        order = torch.randperm(count, generator=gen, device=dev)
-        yield {k: v[order] for k, v in held.items()}
+      if not (with_itm and training):
+        return matched()
+      return self._example_shuffle(matched(), gen, self.example_shuffle_buffer)
 
     def batches():                                               # :221
       pool = _Pool()

@@ -5,6 +5,7 @@ group of records into one blob that is uploaded once.
                     reused (pinned, when there is a GPU) buffer, the partial tail is carried into the next chunk
   pack_records      payloads -> one (pinned) blob, the mmt_record array over it and every named feature's place in it
                     (mmt_example_fields per payload)
+  example_fields    one payload -> its named features where it lies, for reading ids before anything is copied or uploaded
   payload_checksums the blob on its device -> bad flags, one mmt_records_crc call (mmt_records_crc_host for CPU tensors)
 
 Compressed shards (TFRecordOptions GZIP / ZLIB) are refused."""
@@ -99,6 +100,20 @@ def pack_records(payloads: Sequence[bytes], stored: Sequence[int], names: Sequen
     fields.append(out)
     at += len(p)
   return blob, recs, fields
+
+
+def example_fields(payload: bytes, names: Sequence[str]):
+  """The named features of one payload, looked up where it lies (no copy, nothing uploaded): the `ExampleField` array of
+  `names`, offsets relative to the payload.  For reading a record's ids before deciding whether it is decoded at all.
+  A payload that is no well-formed Example raises ValueError."""
+  from . import _lib
+  L = _lib.lib()
+  view = np.frombuffer(payload, dtype=np.uint8) if len(payload) else np.zeros(1, dtype=np.uint8)
+  c_names = (ctypes.c_char_p * len(names))(*[s.encode() for s in names])
+  out = (_lib.ExampleField * len(names))()
+  if L.mmt_example_fields(view.ctypes.data, len(payload), len(names), c_names, out) != 0:
+    raise ValueError(f'no tf.train.Example: {L.mmt_last_error().decode()}')
+  return out
 
 
 def payload_checksums(blob_d: torch.Tensor, recs, n: int) -> torch.Tensor:

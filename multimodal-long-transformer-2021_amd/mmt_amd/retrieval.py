@@ -8,7 +8,8 @@ two sets stay resident in device memory (`RetrievalSets`), a batch of pairs is t
 `mmt_embed_fwd_pairs`), and the scores land in one [I, T] matrix (`PairScorer`) from which recall@k and the reference's
 two result files are computed without one Python object per pair (`recall_at_k_from_scores`,
 `write_results_from_scores`).  `RetrievalSets.materialize` builds the batch the reference's loader would emit for the
-same pairs: the route that existed before, and the yardstick of this one."""
+same pairs: the route that existed before, and the yardstick of this one.  `evaluate_from_records` fills the sets from
+TFRecord files (`retrieval_dataloader.MmtRetrievalDataLoader`) and goes on to recall@k and the result files."""
 from __future__ import annotations
 
 import collections
@@ -367,3 +368,35 @@ def write_results_from_scores(scores, scored, image_index, text_index, gt_image_
   with open(os.path.join(output_dir, 'recall.json'), 'w') as f:
     json.dump(recall, f, indent=4)
   return recall
+
+
+# ---- from records to recall@k -------------------------------------------------------------------------------------------
+def evaluate_from_records(task, model, data_cfg, batch_size: int, output_dir: Optional[str] = None,
+                          topks: Sequence[int] = (1, 3, 5, 10), shard=(0, 1), **loader_args):
+  """Retrieval evaluation on TFRecord files: `retrieval_dataloader.MmtRetrievalDataLoader(data_cfg, **loader_args)`
+  fills the sets, a `PairScorer` scores this shard's pairs -- all of them (`score_all`) for separate sets, the listed
+  ones (`score_pairs`, scattered into the [I, T] matrix and its `scored` mask) for pairs in records -- and
+  `recall_at_k_from_scores` turns the matrix into the recall dictionary, which is returned.  With `output_dir` the
+  reference's two result files are written too (`write_results_from_scores`).  shard (id, n) scores the pairs with
+  p % n == id only; merging the shards of several ranks into one result is not built."""
+  from .retrieval_dataloader import MmtRetrievalDataLoader
+  loader = MmtRetrievalDataLoader(data_cfg, **loader_args)
+  sets, listed = loader.sets(), loader.pairs()
+  scorer = PairScorer(task, model, sets, batch_size)
+  try:
+    if listed is None:
+      scores, scored = scorer.score_all(shard)
+    else:
+      num_shard_pairs(0, 0, shard)                               # the shard check
+      ie = torch.from_numpy(listed[0][int(shard[0])::int(shard[1])].copy()).to(sets.device)
+      te = torch.from_numpy(listed[1][int(shard[0])::int(shard[1])].copy()).to(sets.device)
+      scores = torch.full((sets.num_images, sets.num_texts), -1.0, dtype=torch.float32, device=sets.device)
+      scored = torch.zeros(sets.num_images, sets.num_texts, dtype=torch.bool, device=sets.device)
+      scores[ie.long(), te.long()] = scorer.score_pairs(ie, te)
+      scored[ie.long(), te.long()] = True
+  finally:
+    scorer.close()
+  idx = (sets.image_index, sets.text_index, sets.gt_image_index)
+  if output_dir:
+    return write_results_from_scores(scores, scored, *idx, output_dir, topks)
+  return recall_at_k_from_scores(scores, scored, *idx, topks)

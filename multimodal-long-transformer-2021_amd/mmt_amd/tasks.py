@@ -69,11 +69,14 @@ class _TaskBase:
   def build_inputs(self, params, device='cuda', rank: int = 0, dense_side_inputs: bool = False,
                    batch_size: Optional[int] = None, ragged: bool = False, loader_args: Optional[Dict] = None):
     """An iterator of (inputs, labels) with the reference's feature contract; per-replica batch =
-    global_batch_size / replicas (`pretrain_dataloader.py:107-108`), seeded per rank.  The pretraining task reads
-    TFRecord shards through `pretrain_dataloader.MmtPretrainDataLoader` when `params.input_path` is a local pattern (no
-    URL scheme) and `params.vocab_filename` names a file; everything else -- the empty path, the `gs://` placeholder of
-    the committed YAMLs, the classification task -- draws the endless synthetic stand-in.  `self.input_source` says
-    which ('records' | 'synthetic'); `loader_args` are keyword arguments of the loader (its shuffle buffer sizes)."""
+    global_batch_size / replicas (`pretrain_dataloader.py:107-108`), seeded per rank.  A task reads TFRecord shards
+    when `params.input_path` is a local pattern (no URL scheme) and `params.vocab_filename` names a file: the pretraining
+    task through `pretrain_dataloader.MmtPretrainDataLoader`, the classification task through
+    `classification_dataloader.MmtClassificationDataLoader`, whose labels are `itm_label_ids`, `itm_label_weights` and
+    `itm_pos_weights` -- the task's `label_field`, `label_weights_field` and `pos_weights_field` must name them
+    (ValueError here, not a KeyError in the first step).  Everything else -- the empty path, the `gs://` placeholder of
+    the committed YAMLs -- draws the endless synthetic stand-in.  `self.input_source` says which ('records' |
+    'synthetic'); `loader_args` are keyword arguments of the loader (its shuffle buffer sizes)."""
     per_replica = batch_size or max(1, params.global_batch_size // self.num_replicas)
     self.input_source = 'synthetic'
     if isinstance(self, PretrainingTask):
@@ -85,7 +88,21 @@ class _TaskBase:
         return loader.load(rank=rank, num_replicas=self.num_replicas, batch_size=per_replica)
       if params.input_path and '://' not in params.input_path:
         pretrain_dataloader.check_input_patterns(params.input_path.split(','))     # a local pattern must match, vocabulary or not
-    gen = torch.Generator(device=device).manual_seed(1234 + rank)
+    elif isinstance(self, ClassificationTask):
+      from . import classification_dataloader, record_stages
+      if record_stages.wants_records(getattr(params, 'input_path', ''), getattr(params, 'vocab_filename', '')):
+        keys = classification_dataloader.LABEL_KEYS
+        for what in ('label_field', 'label_weights_field', 'pos_weights_field'):     # else a KeyError in the first step
+          if getattr(self, what) not in keys:
+            raise ValueError(f'task.train_data.{what} is {getattr(self, what)!r}, but the loader on records gives the labels '
+                             f'{list(keys)}: name one of them')
+        self.input_source = 'records'
+        loader = classification_dataloader.MmtClassificationDataLoader(params, device=device, dense_side_inputs=dense_side_inputs,
+                                                                       **(loader_args or {}))
+        return loader.load(rank=rank, num_replicas=self.num_replicas, batch_size=per_replica)
+      if params.input_path and '://' not in params.input_path:
+        record_stages.check_input_patterns(params.input_path.split(','))           # a local pattern must match, vocabulary or not
+    gen =torch.Generator(device=device).manual_seed(1234 + rank)
     vocab = self.task_config.model.encoder.get().vocab_size
     task = 'pretrain' if isinstance(self, PretrainingTask) else 'classification'
     def it():

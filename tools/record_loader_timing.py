@@ -9,8 +9,11 @@ rounds; host stages by wall clock, best of 3.  A record, not a gate: nothing is 
       on shards written here from the same synthesised files: host milliseconds for read + scan, copy + field lookup and
       the JPEG plan; the upload; the device stages one by one; and a whole `next(loader)`.  tasks = 'mlm': the matching
       step needs more than 7 examples in a batch (ratio 1, min_shift 5), which a per-replica batch of 4 does not give.
+  (c) with --finetune, alone: the fine-tuning loader (mmt_amd/classification_dataloader.py) per batch and the retrieval
+      set build (mmt_amd/retrieval_dataloader.py, 64 images and 512 texts) at the fine-tuning shape (batch 64,
+      max_seq_len 256, image 224, patch 16, ratio 1), beside the fine-tuning step of the same run.
 
-Writes one JSON record (--out, default profiles/record_loader_timing.json)."""
+Writes one JSON record (--out, default profiles/record_loader_timing.json; profiles/finetune_loader_timing.json for (c))."""
 import argparse
 import ctypes
 import json
@@ -234,8 +237,136 @@ def loader_leg(torch, _lib, files, args):
   return out
 
 
+def example_with_ints(feats):
+  """feats: (name, bytes | int) in wire order; an int becomes an int64 list of one value."""
+  def feature(v):
+    return ld(3, ld(1, varint(v))) if isinstance(v, int) else ld(1, ld(1, v))
+  return ld(1, b''.join(ld(1, ld(1, k.encode()) + ld(2, feature(v))) for k, v in feats))
+
+
+def write_shard(torch, _lib, path, payloads):
+  """A TFRecord file of the payloads; the payload checksums come from the library's host mirror (plain Python over
+  megabytes would take minutes)."""
+  from mmt_amd import records
+  L = _lib.lib()
+  n = len(payloads)
+  blob, recs, _ = records.pack_records(payloads, [0] * n, [])
+  crc, bad = torch.empty(n, dtype=torch.int32), torch.empty(n, dtype=torch.int32)
+  need = L.mmt_records_crc_workspace_bytes(n)
+  ws = torch.empty(need + 16, dtype=torch.uint8)
+  _lib.check(L.mmt_records_crc_host(blob.data_ptr(), blob.numel(), n, ctypes.addressof(recs), crc.data_ptr(), bad.data_ptr(),
+                                    (ws.data_ptr() + 15) & ~15, need))
+  with open(path, 'wb') as f:
+    for p, c in zip(payloads, crc.numpy().view(np.uint32).tolist()):
+      head = struct.pack('<Q', len(p))
+      f.write(head + struct.pack('<I', mask(crc32c(head))) + p + struct.pack('<I', mask(c)))
+  return path
+
+
+def finetune_leg(torch, _lib, args):
+  """(c) the fine-tuning loader per batch and the retrieval set build at the fine-tuning shape (max_seq_len 256, image
+  224, patch 16, per-replica batch 64, ratio 1), beside the fine-tuning step of the same run: the base encoder in
+  bfloat16 with one ITM head, one `train_step` on loader batches.  The loader decodes a matching group (128 records)
+  at a time and hands it out as four batches, so `next(loader)` is timed over whole groups: the mean per batch, and the
+  longest single call (the one that decodes).  The set build is 64 images and 512 texts from separate files, the sets
+  of tools/retrieval_pairs_timing.py; decode time is taken around the two decode stages with a device synchronisation."""
+  import mmt_amd
+  from mmt_amd import classification_dataloader as cd, configs, optimization, retrieval_dataloader as rd
+  B, S, IMG, PATCH, I, T = 64, 256, 224, 16, 64, 512
+  rng = np.random.default_rng(2)
+  text = lambda n: ' '.join(WORDS[int(i)] for i in rng.integers(0, 15, size=n))
+  t0 = time.perf_counter()
+  files = [encode_jpeg(rng.integers(0, 256, size=(IMG, IMG, 3), dtype=np.uint8), args.quality) for _ in range(16)]
+  print(f'encoded 16 contents of {IMG} x {IMG} in {time.perf_counter() - t0:.1f} s; {len(files[0])} bytes per file')
+  work = tempfile.mkdtemp(prefix='finetune_loader_timing_')
+  vocab_path = os.path.join(work, 'vocab.txt')
+  with open(vocab_path, 'w') as f:
+    f.write('\n'.join(VOCAB + WORDS) + '\n')
+  fields = {'caption_attribution_description': '[ATT]', 'caption_reference_description': '[REF]'}
+  texts = lambda: [('caption_attribution_description', text(20).encode()), ('caption_reference_description', text(30).encode())]
+  n_rec = 4 * 2 * B
+  for s in range(2):
+    write_shard(torch, _lib, os.path.join(work, f'train-{s}.tfrecord'),
+                [example([('image_key', f'k{i}'.encode()), ('image_data', files[i % len(files)])] + texts()) for i in range(s, n_rec, 2)])
+  write_shard(torch, _lib, os.path.join(work, 'image.tfrecord'),
+              [example_with_ints([('image_index', 3 * i + 1), ('image_data', files[i % len(files)])]) for i in range(I)])
+  write_shard(torch, _lib, os.path.join(work, 'text.tfrecord'),
+              [example_with_ints([('text_index', 5 * t + 2), ('gt_image_index', 3 * (t % I) + 1)] + texts()) for t in range(T)])
+
+  exp = configs.get_exp_config('mmt/classification')
+  exp.override({'task': {'model': {'num_classes': 2, 'cls_heads': [{'inner_dim': 768, 'num_classes': 2, 'name': 'itm'}]},
+                         'train_data': dict(input_path=os.path.join(work, 'train-*.tfrecord'), vocab_filename=vocab_path, is_training=True,
+                                            global_batch_size=B, max_seq_len=S, image_size=IMG, patch_size=PATCH,
+                                            negative_positive_ratio=1, text_special_token_field_dict=json.dumps(fields), seed=3,
+                                            label_field='itm_label_ids', label_weights_field='itm_label_weights',
+                                            pos_weights_field='itm_pos_weights')}}, strict=False)
+  d = exp.task.train_data
+  out = {'shape': dict(batch=B, max_seq_len=S, image_size=IMG, patch_size=PATCH, negative_positive_ratio=1,
+                       matching_group=int(2 * B)), 'image_file_bytes': len(files[0])}
+  task = mmt_amd.tasks.get_task(exp.task, compute_dtype=torch.bfloat16)
+  torch.manual_seed(0)
+  model = task.build_model().cuda()
+  opt = optimization.create_optimizer(model, exp.trainer.optimizer_config)
+  it = task.build_inputs(d, device='cuda', batch_size=B)
+  assert task.input_source == 'records'
+  for _ in range(8):                                             # two groups: warm-up of every stage
+    next(it)
+  torch.cuda.synchronize()
+  ts = []
+  for _ in range(16):
+    t0 = time.perf_counter()
+    batch = next(it)
+    torch.cuda.synchronize()
+    ts.append((time.perf_counter() - t0) * 1e3)
+  out['loader_next_ms'] = {'mean_per_batch': round(sum(ts) / len(ts), 2), 'longest_call': round(max(ts), 2),
+                           'median_call': round(statistics.median(ts), 2), 'calls': len(ts)}
+  out['loader_examples_per_s'] = round(B * len(ts) / (sum(ts) / 1e3), 1)
+  steps = []
+  for k in range(3 + 5):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    task.train_step(batch, model, opt, clip_norm=1.0, step=k + 1, micro_batch_size=B)
+    torch.cuda.synchronize()
+    steps.append((time.perf_counter() - t0) * 1e3)
+  out['finetune_step_ms'] = {'median': round(statistics.median(steps[3:]), 2), 'min': round(min(steps[3:]), 2),
+                             'max': round(max(steps[3:]), 2), 'steps': len(steps) - 3, 'model': 'base encoder, bfloat16, one ITM head'}
+  del model, opt
+
+  rcfg = configs.MmtRetrievalDataConfig(image_input_path=os.path.join(work, 'image.tfrecord'), text_input_path=os.path.join(work, 'text.tfrecord'),
+                                        vocab_filename=vocab_path, is_training=False, max_seq_len=S, image_size=IMG, patch_size=PATCH,
+                                        text_special_token_field_dict=json.dumps(fields))
+  builds = []
+  for _ in range(3):                                             # the first build warms up; the best of the others is kept
+    loader = rd.MmtRetrievalDataLoader(rcfg, device='cuda', chunk=64)
+    spent = {'images': 0.0, 'texts': 0.0}
+
+    def timed(call, key):
+      def run(*a):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        call(*a)
+        torch.cuda.synchronize()
+        spent[key] += time.perf_counter() - t0
+      return run
+    loader._decode_images = timed(loader._decode_images, 'images')
+    loader._decode_text_rows = timed(loader._decode_text_rows, 'texts')
+    t0 = time.perf_counter()
+    sets = loader.sets()
+    torch.cuda.synchronize()
+    builds.append((time.perf_counter() - t0, spent['images'], spent['texts']))
+  assert sets.num_images == I and sets.num_texts == T
+  total, t_img, t_txt = min(builds[1:])
+  out['retrieval_set_build'] = {'images': I, 'texts': T, 'chunk': 64, 'whole_build_ms': round(total * 1e3, 2),
+                                'image_decode_ms': round(t_img * 1e3, 2), 'text_decode_ms': round(t_txt * 1e3, 2),
+                                'images_per_s': round(I / t_img, 1), 'texts_per_s': round(T / t_txt, 1)}
+  for k, v in out.items():
+    print(f'  finetune {k}: {v}')
+  return out
+
+
 def main():
   ap = argparse.ArgumentParser()
+  ap.add_argument('--finetune', action='store_true', help='run leg (c) alone and write profiles/finetune_loader_timing.json')
   ap.add_argument('--batch', type=int, default=64)
   ap.add_argument('--size', type=int, default=1008)
   ap.add_argument('--quality', type=int, default=90)
@@ -248,6 +379,14 @@ def main():
   import torch
   from mmt_amd import _lib
   assert torch.cuda.is_available(), 'record_loader_timing needs a GPU'
+  if args.finetune:
+    out = args.out if args.out != ap.get_default('out') else os.path.join(ROOT, 'profiles', 'finetune_loader_timing.json')
+    record = {'device': torch.cuda.get_device_name(0), 'finetune': finetune_leg(torch, _lib, args)}
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'w') as f:
+      json.dump(record, f, indent=1)
+    print('wrote', out)
+    return
   rng = np.random.default_rng(0)
   t0 = time.perf_counter()
   distinct = [encode_jpeg(rng.integers(0, 256, size=(args.size, args.size, 3), dtype=np.uint8), args.quality)

@@ -715,6 +715,68 @@ int mmt_png_pixels_host(int32_t B, const mmt_png_image* images, const uint8_t* r
                         const uint8_t* palettes, uint8_t* pixels_out, int64_t pixels_bytes, void* workspace,
                         size_t workspace_bytes);
 
+/* ------------------------------------------------------------------------------------------------
+ * PNG inflate on the device (csrc/png_inflate.hip, csrc/png_inflate.h; DESIGN.md section 4, "PNG inflate on the
+ * device"): the opt-in replacement of mmt_png_inflate's DEFLATE stage.  The host keeps the chunk walk
+ * (mmt_png_gather); one workgroup of 256 threads per image inflates the zlib stream by self-synchronising speculative
+ * Huffman decoding with parallel resolution of the LZ77 copies, and makes every check the host inflate makes.  The
+ * contract is an equivalence: status_out[b] == 0 exactly when mmt_png_inflate returns MMT_OK on the same file, and
+ * then the scanlines are the same bytes.
+ *
+ * One struct per image describes its compressed bytes. */
+typedef struct mmt_png_stream {
+  int64_t comp_offset;   /* first byte of the image's zlib stream in comp (the IDAT payloads, concatenated) */
+  int64_t comp_bytes;    /* its size, zlib header and everything behind the last block included               */
+} mmt_png_stream;
+
+/* status_out[b] of mmt_png_scanlines: 0, or why the stream was refused. */
+enum {
+  MMT_PNG_ST_OK = 0,
+  MMT_PNG_ST_TRUNCATED = 1,      /* the stream ends inside a block, a token or the check value             */
+  MMT_PNG_ST_BLOCK_TYPE = 2,     /* reserved block type 3                                                  */
+  MMT_PNG_ST_STORED_LEN = 3,     /* the length of a stored block does not match its complement             */
+  MMT_PNG_ST_CODE_LENGTHS = 4,   /* a bad code-length set (counts, repeats, over-subscribed, incomplete)    */
+  MMT_PNG_ST_BAD_CODE = 5,       /* an unused literal/length or distance code, or a reserved symbol        */
+  MMT_PNG_ST_DISTANCE = 6,       /* a distance before the start of the output                              */
+  MMT_PNG_ST_TOO_LONG = 7,       /* more output than raw_bytes                                             */
+  MMT_PNG_ST_TOO_SHORT = 8,      /* the final block ended before raw_bytes                                 */
+  MMT_PNG_ST_ADLER = 9,          /* Adler-32 mismatch                                                      */
+  MMT_PNG_ST_FILTER = 10,        /* a filter-type byte above 4                                             */
+  MMT_PNG_ST_NO_PROGRESS = 11    /* a round that took no bit (a guard; no stream is known to reach it)     */
+};
+
+/* Host only, re-entrant, no device call, never reads past len.  The host work that remains: walks the chunks from the
+ * first IDAT to IEND by the rules of mmt_png_inflate and with its messages (CRC-32 of IDAT and IEND, the stream ends at
+ * the first gap between IDAT chunks, truncation, tRNS and unknown critical chunks behind the data), copies the IDAT
+ * payloads back to back to comp_out + stream->comp_offset (HOST memory, pinned if it is to be uploaded; the payloads
+ * are fewer bytes than the file, so len bytes always suffice), validates the two zlib header bytes, sets
+ * stream->comp_bytes and fills the palette as mmt_png_inflate does.  It decodes no DEFLATE block.  `image` must
+ * describe this file (mmt_png_info).  A refusal here is one mmt_png_inflate makes too. */
+int mmt_png_gather(const uint8_t* bytes, int64_t len, const mmt_png_image* image, uint8_t* comp_out,
+                   int64_t comp_capacity, mmt_png_stream* stream /* in: comp_offset; out: comp_bytes */,
+                   uint8_t* palette_out /* [256][3] */);
+
+/* The device call takes DEVICE memory throughout (images [B], streams [B], comp, raw_out, status_out [B] and the
+ * workspace), allocates nothing and does not wait, so it can be recorded into a graph; one launch whatever the
+ * arguments are (grid B, 256 threads), no floating point, no atomics, no workgroup waits for another, no scratch; lanes
+ * own disjoint output ranges, so the bytes are the same on every run, also for a stream that is refused.  Image b's
+ * filtered scanlines go to raw_out + images[b].raw_offset -- the layout mmt_png_pixels reads.  subseq_bytes: the bytes of
+ * the stream a lane owns in a round, a power of two in [8, 128].  The return value is about the arguments only: a bad
+ * stream is a status.  The front end's safety rule holds: every offset and size of `images`, `streams` and the stream
+ * itself is clamped into its buffer, no byte is written outside [raw_offset, raw_offset + raw_bytes) cut to
+ * [0, raw_bytes of the call), none is read outside comp, every loop is bounded by the buffer sizes -- wrong metadata or
+ * a hostile stream gives a status or wrong bytes, not a fault.  comp_bytes and raw_bytes in [1, 2^60).  The workspace
+ * (mmt_png_scanlines_workspace_bytes(B) bytes, no initialisation) holds the group's state for the host variant, which
+ * runs the same functions with the 256 lanes as a loop over HOST memory (CPU tensors, host tests, the sanitizer
+ * program); the device call keeps that state in LDS and leaves the workspace alone. */
+size_t mmt_png_scanlines_workspace_bytes(int32_t B);           /* host only; 0 for B < 1 */
+int mmt_png_scanlines(int32_t B, const mmt_png_image* images, const mmt_png_stream* streams, const uint8_t* comp,
+                      int64_t comp_bytes, uint8_t* raw_out, int64_t raw_bytes, int32_t* status_out /* [B] */,
+                      int32_t subseq_bytes, void* workspace, size_t workspace_bytes, void* stream);
+int mmt_png_scanlines_host(int32_t B, const mmt_png_image* images, const mmt_png_stream* streams, const uint8_t* comp,
+                           int64_t comp_bytes, uint8_t* raw_out, int64_t raw_bytes, int32_t* status_out /* [B] */,
+                           int32_t subseq_bytes, void* workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,8 @@
 //           copied together), a 10-bit lookup per Huffman code with the canonical walk behind it for longer codes,
 //           output straight into the caller's buffer, which also serves as the window.  Output: the filtered
 //           scanlines, per pass rows x (1 + row bytes), and the palette.
+//           mmt_png_gather: the same chunk walk without the DEFLATE -- the IDAT payloads back to back, for the inflate on
+//           the device (png_inflate.hip).
 //   device  one kernel, grid (images, 7), one wave per (image, pass): an anti-diagonal wavefront over bands of 64 rows.
 //           Lane r of a band reconstructs filter unit x of its row at step x + r; the unit above comes from lane r - 1
 //           by a lane shift (it was reconstructed one step earlier), the unit above left is the one received the step
@@ -590,6 +592,64 @@ int mmt_png_inflate(const uint8_t* bytes, int64_t len, const mmt_png_image* imag
   // behind the stream: more IDAT (ignored, as libpng does, but for its CRC), ancillary chunks, IEND
   b.p = b.end;
   for (int64_t next = b.next;;) {
+    mmt::Chunk c;
+    if (next == len) return mmt::fail(MMT_E_INVALID, "png: truncated: the file ends without an IEND chunk");
+    if ((rc = mmt::read_chunk(bytes, len, next, c))) return rc;
+    if (mmt::is_type(c.type, "IEND")) return mmt::check_crc(c);
+    if (mmt::is_type(c.type, "IDAT")) {
+      if ((rc = mmt::check_crc(c))) return rc;
+    } else if (mmt::is_type(c.type, "tRNS")) {
+      return mmt::fail(MMT_E_UNSUPPORTED, "png: a tRNS chunk (transparency) is not supported");
+    } else if (!(c.type[0] & 0x20) && !mmt::is_type(c.type, "PLTE")) {
+      return mmt::fail(MMT_E_UNSUPPORTED, "png: unknown critical chunk 0x%02x%02x%02x%02x", c.type[0], c.type[1], c.type[2], c.type[3]);
+    }
+    next += 12 + c.size;
+  }
+}
+
+// The host stage of the device inflate (png_inflate.hip): the chunk walk of mmt_png_inflate without its DEFLATE -- the
+// same rules in the same order, the same messages -- with the IDAT payloads copied back to back.
+int mmt_png_gather(const uint8_t* bytes, int64_t len, const mmt_png_image* image, uint8_t* comp_out, int64_t comp_capacity,
+                   mmt_png_stream* stream, uint8_t* palette_out) {
+  int rc = mmt::check_bytes("mmt_png_gather", bytes, len);
+  if (rc) return rc;
+  if (!image || !comp_out || !stream || !palette_out)
+    return mmt::fail(MMT_E_INVALID, "mmt_png_gather: NULL argument (image, comp_out, stream and palette_out are required)");
+  mmt::Header h;
+  if ((rc = mmt::read_header(bytes, len, h))) return rc;
+  const mmt_png_image& own = h.im;
+  if (image->width != own.width || image->height != own.height || image->bit_depth != own.bit_depth || image->color_type != own.color_type ||
+      image->interlace != own.interlace || image->palette_entries != own.palette_entries || image->raw_bytes != own.raw_bytes)
+    return mmt::fail(MMT_E_INVALID, "mmt_png_gather: image does not describe this stream (take it from mmt_png_info)");
+  if (stream->comp_offset < 0 || stream->comp_offset > comp_capacity)
+    return mmt::fail(MMT_E_INVALID, "mmt_png_gather: comp_offset %lld outside comp_out (%lld bytes)", (long long)stream->comp_offset,
+                     (long long)comp_capacity);
+  std::memset(palette_out, 0, 768);
+  if (h.plte) std::memcpy(palette_out, h.plte, (size_t)own.palette_entries * 3);
+  uint8_t* comp = comp_out + stream->comp_offset;
+  const int64_t room = comp_capacity - stream->comp_offset;
+  int64_t n = 0, next = h.first_idat;
+  int err = 0;
+  while (next != len) {                                         // the IDAT chunks that follow each other directly
+    mmt::Chunk c;
+    if ((err = mmt::read_chunk(bytes, len, next, c))) break;
+    if (!mmt::is_type(c.type, "IDAT")) break;
+    if ((err = mmt::check_crc(c))) break;
+    if (c.size > room - n)
+      return mmt::fail(MMT_E_INVALID, "mmt_png_gather: the IDAT payloads leave comp_out (%lld bytes from %lld)", (long long)comp_capacity,
+                       (long long)stream->comp_offset);
+    std::memcpy(comp + n, c.data, (size_t)c.size);
+    n += c.size; next += 12 + c.size;
+  }
+  if (n < 2) return err ? err : mmt::truncated_stream();
+  const unsigned cmf = comp[0], flg = comp[1];
+  if ((cmf & 15u) != 8) return mmt::fail(MMT_E_INVALID, "png: bad zlib header: compression method %u is not 8 (deflate)", cmf & 15u);
+  if ((cmf >> 4) > 7) return mmt::fail(MMT_E_INVALID, "png: bad zlib header: a window larger than 32 KiB");
+  if (((cmf << 8) | flg) % 31 != 0) return mmt::fail(MMT_E_INVALID, "png: bad zlib header: the check bits do not match");
+  if (flg & 0x20) return mmt::fail(MMT_E_INVALID, "png: bad zlib header: a preset dictionary");
+  if (err) return err;
+  stream->comp_bytes = n;
+  for (;;) {                                                    // behind the stream, as mmt_png_inflate walks on
     mmt::Chunk c;
     if (next == len) return mmt::fail(MMT_E_INVALID, "png: truncated: the file ends without an IEND chunk");
     if ((rc = mmt::read_chunk(bytes, len, next, c))) return rc;

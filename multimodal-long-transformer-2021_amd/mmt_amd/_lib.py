@@ -52,7 +52,8 @@ EXPORTS = ('mmt_abi_version', 'mmt_last_error', 'mmt_write_step_scalars', 'mmt_w
            'mmt_jpeg_info', 'mmt_jpeg_coefficients', 'mmt_jpeg_workspace_bytes', 'mmt_jpeg_pixels', 'mmt_jpeg_pixels_host',
            'mmt_jpeg_scan_plan', 'mmt_jpeg_entropy_workspace_bytes', 'mmt_jpeg_entropy', 'mmt_jpeg_entropy_host',
            'mmt_records_scan', 'mmt_example_fields', 'mmt_records_crc_workspace_bytes', 'mmt_records_crc', 'mmt_records_crc_host',
-           'mmt_png_info', 'mmt_png_inflate', 'mmt_png_workspace_bytes', 'mmt_png_pixels', 'mmt_png_pixels_host')
+           'mmt_png_info', 'mmt_png_inflate', 'mmt_png_workspace_bytes', 'mmt_png_pixels', 'mmt_png_pixels_host',
+           'mmt_png_gather', 'mmt_png_scanlines_workspace_bytes', 'mmt_png_scanlines', 'mmt_png_scanlines_host')
 
 
 class EmbedDesc(ctypes.Structure):
@@ -119,6 +120,15 @@ class JpegScan(ctypes.Structure):
               ('max_segment_subseq', ctypes.c_int32), ('components', ctypes.c_int32), ('dc_table', ctypes.c_int32 * 3),
               ('ac_table', ctypes.c_int32 * 3), ('restart_interval', ctypes.c_int32), ('mcus', ctypes.c_int32),
               ('subseq_bytes', ctypes.c_int32), ('uniform_tables', ctypes.c_int32)]
+
+
+class PngStream(ctypes.Structure):
+  _fields_ = [('comp_offset', ctypes.c_int64), ('comp_bytes', ctypes.c_int64)]
+
+
+# status words of mmt_png_scanlines (include/mmt_layer.h, MMT_PNG_ST_*)
+PNG_ST_NAMES = ('ok', 'truncated', 'block type', 'stored length', 'code lengths', 'bad code', 'distance', 'too long', 'too short',
+                'adler', 'filter byte', 'no progress')
 
 
 class PngImage(ctypes.Structure):
@@ -333,6 +343,14 @@ def lib() -> ctypes.CDLL:
   L.mmt_png_pixels.argtypes = [ctypes.c_int32, vp, vp, i64, vp, vp, i64, vp, ctypes.c_size_t, vp]
   L.mmt_png_pixels_host.restype = ctypes.c_int
   L.mmt_png_pixels_host.argtypes = [ctypes.c_int32, vp, vp, i64, vp, vp, i64, vp, ctypes.c_size_t]
+  L.mmt_png_gather.restype = ctypes.c_int
+  L.mmt_png_gather.argtypes = [vp, i64, pp, vp, i64, ctypes.POINTER(PngStream), vp]
+  L.mmt_png_scanlines_workspace_bytes.restype = ctypes.c_size_t
+  L.mmt_png_scanlines_workspace_bytes.argtypes = [ctypes.c_int32]
+  L.mmt_png_scanlines.restype = ctypes.c_int
+  L.mmt_png_scanlines.argtypes = [ctypes.c_int32, vp, vp, vp, i64, vp, i64, vp, ctypes.c_int32, vp, ctypes.c_size_t, vp]
+  L.mmt_png_scanlines_host.restype = ctypes.c_int
+  L.mmt_png_scanlines_host.argtypes = [ctypes.c_int32, vp, vp, vp, i64, vp, i64, vp, ctypes.c_int32, vp, ctypes.c_size_t]
   L.mmt_write_step_scalars.restype = ctypes.c_int
   L.mmt_write_step_scalars.argtypes = [vp, vp, ctypes.c_uint64, ctypes.c_float, ctypes.c_float, ctypes.c_float, vp]
   if L.mmt_abi_version() != MMT_ABI_VERSION:

@@ -6,7 +6,8 @@ tensor transforms the reference runs inside tf.data on the host, as batched torc
                                                               the host, Huffman decoding on the host or, with entropy='device', in
                                                               HIP; IDCT, upsampling and colour in HIP)
   decode_png_images          src/data/data_utils.py:195      (the same call for PNG bytes: chunk walk and the library's own inflate on
-                                                              the host; unfiltering, de-interlacing, expansion and palette in HIP)
+                                                              the host, or with inflate='device' the inflate in HIP too;
+                                                              unfiltering, de-interlacing, expansion and palette in HIP)
   decode_images              src/data/data_utils.py:195      (a batch of JPEG and PNG files, each to its decoder by its signature)
   decode_image_features      src/data/data_utils.py:195-222  (`decode_fn` from the encoded bytes or the decoded pixels on, driven by the
                                                               data config: RandAugment and the flip coin when training, then the line below)
@@ -153,14 +154,14 @@ def _is_encoded(item) -> bool:
   return isinstance(item, (bytes, bytearray, memoryview, np.ndarray))
 
 
-def _maybe_decode(images, device, entropy='host', uploaded=None):
+def _maybe_decode(images, device, entropy='host', uploaded=None, png_inflate='host'):
   """A list whose items are encoded bytes (JPEG or PNG files, `decode_images`) is decoded first; a list of tensors or a
   packed tuple passes unchanged."""
   if isinstance(images, tuple):
     return images
   images = list(images)
   if images and all(_is_encoded(im) for im in images):
-    return decode_images(images, device, entropy=entropy, uploaded=uploaded)
+    return decode_images(images, device, entropy=entropy, uploaded=uploaded, png_inflate=png_inflate)
   return images
 
 
@@ -414,7 +415,9 @@ def decode_jpeg_images(data, device, *, workers: int = 8, out: torch.Tensor = No
 # ---------------------------------------------------------------------------------------------------
 # PNG decode (`tf.io.decode_image`, src/data/data_utils.py:195; the Fashion-Gen shards store PNG files): the host walks
 # the chunks and inflates (csrc/png_decode.hip, the library's own inflate; a thread pool spreads the files), the device
-# unfilters, de-interlaces, expands and looks the palette up.  DESIGN.md section 4 "PNG decode" has the rules.
+# unfilters, de-interlaces, expands and looks the palette up.  DESIGN.md section 4 "PNG decode" has the rules.  Opt-in
+# (inflate='device') the host only gathers the IDAT payloads and a kernel inflates them (csrc/png_inflate.hip; DESIGN.md
+# section 4 "PNG inflate on the device").
 # ---------------------------------------------------------------------------------------------------
 PNG_SIGNATURE = b'\x89PNG\r\n\x1a\n'
 
@@ -431,7 +434,7 @@ def _encoded_arrays(items):
   return bufs
 
 
-def decode_png_images(data, device, *, workers: int = 8, out: torch.Tensor = None):
+def decode_png_images(data, device, *, workers: int = 8, out: torch.Tensor = None, inflate: str = 'host', subseq_bytes: int = None):
   """PNG files -> the packed (pixels uint8 [n], offsets int64 [B], heights int32 [B], widths int32 [B]) tuple on `device`
   that `decode_jpeg_images` returns; image b is RGB, row-major, back to back.
 
@@ -442,8 +445,19 @@ def decode_png_images(data, device, *, workers: int = 8, out: torch.Tensor = Non
   spread over `workers` threads (clamped to 1..16); one asynchronous upload of scanlines, palettes and metadata; one
   mmt_png_pixels.  With device 'cpu' the same buffers go through mmt_png_pixels_host.  out: a contiguous uint8 tensor on
   `device` of at least the needed size (allocated when None; bytes behind the last image are not written).  A file the
-  library refuses (depth 16, alpha, tRNS, a corrupt or truncated stream) raises ValueError naming the example."""
+  library refuses (depth 16, alpha, tRNS, a corrupt or truncated stream) raises ValueError naming the example.
+
+  inflate: 'host' (the default) is the path above.  'device' uploads the compressed bytes instead of the scanlines and
+  inflates them in a kernel: mmt_png_gather per file on the thread pool (chunk walk, IDAT payloads back to back) into one
+  pinned buffer of compressed bytes, palettes, metadata and stream descriptors; one asynchronous upload;
+  mmt_png_scanlines (subseq_bytes: the bytes of a stream a lane owns in a round, a power of two in [8, 128], default
+  PNG_INFLATE_SUBSEQ_BYTES); one read-back of the status words; mmt_png_pixels.  A file whose status is not 0 goes
+  through mmt_png_inflate on the host: its refusal is raised as the host path raises it, and if the host accepts the
+  file its scanlines are uploaded into the image's slice, so the pixels never depend on the path.  With device 'cpu'
+  the same buffers go through mmt_png_scanlines_host."""
   from . import _lib
+  if inflate not in ('host', 'device'):
+    raise ValueError(f"inflate must be 'host' or 'device', got {inflate!r}")
   L = _lib.lib()
   device = torch.device(device)
   items = list(data)
@@ -452,6 +466,8 @@ def decode_png_images(data, device, *, workers: int = 8, out: torch.Tensor = Non
     raise ValueError('data is empty')
   bufs = _encoded_arrays(items)
   workers = min(max(int(workers), 1), 16)
+  if inflate == 'device':
+    return _decode_png_device_inflate(L, _lib, bufs, device, workers, out, subseq_bytes)
   images = (_lib.PngImage * B)()
   n_raw, n_pix = 0, 0
   hs, ws, offs = [], [], []
@@ -502,12 +518,114 @@ def decode_png_images(data, device, *, workers: int = 8, out: torch.Tensor = Non
   return out, t(offs, torch.int64), t(hs, torch.int32), t(ws, torch.int32)
 
 
+# Default of the device inflate, from profiles/png_inflate_timing.json ("PNG inflate on the device").
+PNG_INFLATE_SUBSEQ_BYTES = 16
+
+
+def _decode_png_device_inflate(L, _lib, bufs, device, workers, out, subseq_bytes):
+  """The `inflate='device'` path of decode_png_images."""
+  B = len(bufs)
+  sb = PNG_INFLATE_SUBSEQ_BYTES if subseq_bytes is None else int(subseq_bytes)
+  if sb < 8 or sb > 128 or sb & (sb - 1):
+    raise ValueError(f'subseq_bytes must be a power of two in [8, 128], got {subseq_bytes!r}')
+  images = (_lib.PngImage * B)()
+  streams = (_lib.PngStream * B)()
+  n_raw, n_pix, n_comp = 0, 0, 0
+  hs, ws, offs = [], [], []
+  for i, arr in enumerate(bufs):
+    rc = L.mmt_png_info(arr.ctypes.data, arr.size, ctypes.byref(images[i]))
+    if rc != 0:
+      raise ValueError(f'data[{i}] cannot be decoded: {L.mmt_last_error().decode()}')
+    im = images[i]
+    im.raw_offset, im.pixel_offset = n_raw, n_pix
+    n_raw += im.raw_bytes
+    hs.append(im.height); ws.append(im.width); offs.append(n_pix)
+    n_pix += im.height * im.width * 3
+    streams[i].comp_offset = n_comp                             # the IDAT payloads are fewer bytes than the file
+    n_comp += arr.size
+  on_gpu = device.type == 'cuda'
+  o_pal = _up16(n_comp)                                          # one buffer: compressed bytes | palettes | metadata | streams
+  o_img = o_pal + B * 768
+  o_str = _up16(o_img + ctypes.sizeof(images))
+  stage = torch.empty(_up16(o_str + ctypes.sizeof(streams)), dtype=torch.uint8, pin_memory=on_gpu)
+  base = stage.data_ptr()
+
+  def host_inflate(i):                                          # (scanlines, None) or (None, the host path's message)
+    im = _lib.PngImage.from_buffer_copy(images[i])
+    im.raw_offset = 0
+    raw = np.empty(max(im.raw_bytes, 1), dtype=np.uint8)
+    pal = np.empty(768, dtype=np.uint8)
+    rc = L.mmt_png_inflate(bufs[i].ctypes.data, bufs[i].size, ctypes.byref(im), raw.ctypes.data, im.raw_bytes, pal.ctypes.data)
+    return (raw, None) if rc == 0 else (None, L.mmt_last_error().decode())
+
+  def gather(i):                                                # the message is thread-local: read it on the worker
+    rc = L.mmt_png_gather(bufs[i].ctypes.data, bufs[i].size, ctypes.byref(images[i]), base, n_comp, ctypes.byref(streams[i]),
+                          base + o_pal + i * 768)
+    if rc == 0:
+      return None
+    msg = L.mmt_last_error().decode()
+    return host_inflate(i)[1] or msg                            # the host path's words for what it refuses too
+
+  if workers == 1 or B == 1:
+    errors = [gather(i) for i in range(B)]
+  else:
+    with ThreadPoolExecutor(max_workers=min(workers, B)) as pool:
+      errors = list(pool.map(gather, range(B)))
+  for i, msg in enumerate(errors):
+    if msg is not None:
+      raise ValueError(f'data[{i}] cannot be decoded: {msg}')
+  view = stage.numpy()
+  view[o_img:o_img + ctypes.sizeof(images)] = np.frombuffer(bytes(images), dtype=np.uint8)
+  view[o_str:o_str + ctypes.sizeof(streams)] = np.frombuffer(bytes(streams), dtype=np.uint8)
+  if out is None:
+    out = torch.zeros(n_pix, dtype=torch.uint8, device=device)
+  elif out.dtype != torch.uint8 or out.dim() != 1 or out.numel() < n_pix or out.device != device or not out.is_contiguous():
+    raise ValueError(f'out must be a contiguous 1-D uint8 tensor of at least {n_pix} bytes on {device}')
+  need_inf = L.mmt_png_scanlines_workspace_bytes(B)
+  need = L.mmt_png_workspace_bytes(n_raw)
+
+  def repair(raw_t, status):                                    # files the kernel refused: the host decides
+    for i in np.flatnonzero(status):
+      lines, msg = host_inflate(int(i))
+      if msg is not None:
+        raise ValueError(f'data[{int(i)}] cannot be decoded: {msg}')
+      at = images[int(i)].raw_offset
+      raw_t[at:at + lines.size].copy_(torch.from_numpy(lines))
+
+  if on_gpu:
+    with torch.cuda.device(device):
+      stream = torch.cuda.current_stream(device).cuda_stream
+      stage_d = stage.to(device, non_blocking=True)
+      raw_t = torch.empty(n_raw, dtype=torch.uint8, device=device)
+      status_t = torch.empty(B, dtype=torch.int32, device=device)
+      work_inf = torch.empty(need_inf, dtype=torch.uint8, device=device)
+      work = torch.empty(need, dtype=torch.uint8, device=device)
+      d = stage_d.data_ptr()
+      _lib.check(L.mmt_png_scanlines(B, d + o_img, d + o_str, d, n_comp, raw_t.data_ptr(), n_raw, status_t.data_ptr(), sb,
+                                     work_inf.data_ptr(), need_inf, stream))
+      repair(raw_t, status_t.cpu().numpy())
+      _lib.check(L.mmt_png_pixels(B, d + o_img, raw_t.data_ptr(), n_raw, d + o_pal, out.data_ptr(), out.numel(), work.data_ptr(), need,
+                                  stream))
+  else:
+    raw_t = torch.empty(n_raw, dtype=torch.uint8)
+    status_t = torch.empty(B, dtype=torch.int32)
+    work_inf = torch.empty(need_inf, dtype=torch.uint8)
+    work = torch.empty(need, dtype=torch.uint8)
+    _lib.check(L.mmt_png_scanlines_host(B, base + o_img, base + o_str, base, n_comp, raw_t.data_ptr(), n_raw, status_t.data_ptr(), sb,
+                                        work_inf.data_ptr(), need_inf))
+    repair(raw_t, status_t.numpy())
+    _lib.check(L.mmt_png_pixels_host(B, base + o_img, raw_t.data_ptr(), n_raw, base + o_pal, out.data_ptr(), out.numel(), work.data_ptr(),
+                                     need))
+  t = lambda v, dt: torch.tensor(v, dtype=dt).to(device)
+  return out, t(offs, torch.int64), t(hs, torch.int32), t(ws, torch.int32)
+
+
 def _is_png(item) -> bool:
   return _is_encoded(item) and bytes(memoryview(item)[:8]) == PNG_SIGNATURE
 
 
 def decode_images(data, device, *, workers: int = 8, out: torch.Tensor = None, entropy: str = 'host', subseq_bytes: int = None,
-                  max_rounds: int = None, uploaded=None):
+                  max_rounds: int = None, uploaded=None, png_inflate: str = 'host'):
   """`tf.io.decode_image` for a list of encoded files, JPEG or PNG each: the packed (pixels, offsets, heights, widths)
   tuple on `device`, images in the order of `data`.  An item that starts with the 8-byte PNG signature is a PNG file;
   everything else is taken for a JPEG file (and refused by `decode_jpeg_images` if it is none).
@@ -516,15 +634,18 @@ def decode_images(data, device, *, workers: int = 8, out: torch.Tensor = None, e
   `decode_png_images` (workers, out).  A mixed list decodes the two groups into disjoint slices of one `out` -- the JPEG
   files first, then the PNG files -- and returns offsets, heights and widths in the order of `data`; the images are then not
   in the order of their offsets, which the packed layout allows.  entropy, subseq_bytes and max_rounds are
-  `decode_jpeg_images`'s; `uploaded` offsets are passed on for the JPEG items only.  A refusal names the example by its
-  index in `data`."""
+  `decode_jpeg_images`'s; `uploaded` offsets are passed on for the JPEG items only.  png_inflate is `decode_png_images`'s
+  `inflate` ('host' or 'device') and takes effect for the PNG items only.  A refusal names the example by its index in
+  `data`."""
+  if png_inflate not in ('host', 'device'):
+    raise ValueError(f"png_inflate must be 'host' or 'device', got {png_inflate!r}")
   items = list(data)
   png = [i for i, item in enumerate(items) if _is_png(item)]
   if not png:
     return decode_jpeg_images(items, device, workers=workers, out=out, entropy=entropy, subseq_bytes=subseq_bytes, max_rounds=max_rounds,
                               uploaded=uploaded)
   if len(png) == len(items):
-    return decode_png_images(items, device, workers=workers, out=out)
+    return decode_png_images(items, device, workers=workers, out=out, inflate=png_inflate)
   device = torch.device(device)
   jpg = [i for i in range(len(items)) if i not in set(png)]
 
@@ -542,7 +663,7 @@ def decode_images(data, device, *, workers: int = 8, out: torch.Tensor = None, e
   jpeg_kw = dict(workers=workers, entropy=entropy, subseq_bytes=subseq_bytes, max_rounds=max_rounds, uploaded=up)
   if out is None:                                               # the sizes are not known yet: decode, then join
     a = group(jpg, lambda: decode_jpeg_images([items[i] for i in jpg], device, **jpeg_kw))
-    b = group(png, lambda: decode_png_images([items[i] for i in png], device, workers=workers))
+    b = group(png, lambda: decode_png_images([items[i] for i in png], device, workers=workers, inflate=png_inflate))
     pixels = torch.cat([a[0], b[0]])
   else:
     if out.dtype != torch.uint8 or out.dim() != 1 or out.device != device or not out.is_contiguous():
@@ -551,7 +672,7 @@ def decode_images(data, device, *, workers: int = 8, out: torch.Tensor = None, e
     n_a = int(a[1][-1]) + int(a[2][-1]) * int(a[3][-1]) * 3
     if out.numel() <= n_a:
       raise ValueError(f'out must hold more than the {n_a} bytes of the JPEG files')
-    b = group(png, lambda: decode_png_images([items[i] for i in png], device, workers=workers, out=out[n_a:]))
+    b = group(png, lambda: decode_png_images([items[i] for i in png], device, workers=workers, out=out[n_a:], inflate=png_inflate))
     pixels = out
   n_a = int(a[0].numel()) if out is None else n_a
   B = len(items)
@@ -568,13 +689,14 @@ def decode_images(data, device, *, workers: int = 8, out: torch.Tensor = None, e
 def images_to_patch_features(images, image_size: int, patch_size: int, *, flip: torch.Tensor = None,
                              out_dtype: torch.dtype = torch.float32, keep_unnormalized: bool = False,
                              output_channel_bits: int = 0, mean=IMAGENET_DEFAULT_MEAN, device=None,
-                             entropy: str = 'host') -> Dict[str, torch.Tensor]:
+                             entropy: str = 'host', png_inflate: str = 'host') -> Dict[str, torch.Tensor]:
   """The tensor half of `decode_fn` (src/data/data_utils.py:195-222) for a batch of decoded RGB images of any sizes.
 
   images: list of uint8 [h, w, 3] tensors, or an already packed (pixels uint8 [n], offsets int64 [B], heights int32
   [B], widths int32 [B]) tuple (example b is heights[b] x widths[b] x 3 bytes, row-major, from pixels[offsets[b]]), or a
   list of encoded JPEG or PNG files (bytes, bytearray, memoryview, uint8 numpy arrays; the two may be mixed), which
-  `decode_images` decodes first onto `device` (default: the GPU when there is one), JPEG files with its `entropy` mode.
+  `decode_images` decodes first onto `device` (default: the GPU when there is one), JPEG files with its `entropy` mode,
+  PNG files with its `png_inflate` mode.
   Per example: x = u8 / 255; bilinear resize to image_size x image_size (tf.image.resize, TF2 defaults);
   patch_embeddings from (r - mean) / mean -- the reference's line 204 divides by the MEAN -- and
   unnormalized_patch_embeddings from r; flip [B] (bool / uint8; the reference's training-time coin, :209-211, as an
@@ -595,7 +717,7 @@ def images_to_patch_features(images, image_size: int, patch_size: int, *, flip: 
     raise ValueError('output_channel_bits must be in [0, 8]')
   if len(mean) != 3 or any(float(m) == 0.0 for m in mean):
     raise ValueError('mean must be three non-zero numbers')
-  images = _maybe_decode(images, _default_device(device), entropy)
+  images = _maybe_decode(images, _default_device(device), entropy, png_inflate=png_inflate)
   pixels, offsets, heights, widths = _check_packed(images) if isinstance(images, tuple) else _pack_images(list(images))
   B, dev = offsets.shape[0], pixels.device
   if flip is not None:
@@ -816,10 +938,10 @@ def rand_augment(images, op: torch.Tensor, arg: torch.Tensor, out: torch.Tensor 
 
 def decode_image_features(data_config, images, *, generator: torch.Generator = None,
                           out_dtype: torch.dtype = torch.float32, keep_unnormalized: bool = False,
-                          device=None, entropy: str = 'host', uploaded=None) -> Dict[str, torch.Tensor]:
+                          device=None, entropy: str = 'host', uploaded=None, png_inflate: str = 'host') -> Dict[str, torch.Tensor]:
   """`decode_fn` (src/data/data_utils.py:195-222) as the data config drives it.  images: a list of uint8 [h, w, 3] tensors,
   a packed tuple, or a list of encoded JPEG or PNG files, which `decode_images` decodes first onto `device` (default: the
-  GPU when there is one; `entropy` is the JPEG decode's mode):
+  GPU when there is one; `entropy` is the JPEG decode's mode, `png_inflate` the PNG decode's):
     is_training and use_rand_aug   `rand_augment` with a `rand_augment_plan` drawn from `generator`      (:199-202)
     is_training                    one flip coin per example, flipped when u > 0.5                        (:209-211)
     then `images_to_patch_features` with the config's image_size, patch_size and, where the config has the field,
@@ -827,7 +949,7 @@ def decode_image_features(data_config, images, *, generator: torch.Generator = N
   Draws come from `generator` in this order: operation ids, signs, flip coins.  With is_training false the result is
   `images_to_patch_features(images, image_size, patch_size, ...)` bit for bit.  `uploaded` is `decode_jpeg_images`'s; PNG
   files do not use it."""
-  images = _maybe_decode(images, _default_device(device), entropy, uploaded)
+  images = _maybe_decode(images, _default_device(device), entropy, uploaded, png_inflate)
   packed = _check_packed(images) if isinstance(images, tuple) else _pack_images(list(images))
   pixels, offsets, heights, widths = packed
   flip = None

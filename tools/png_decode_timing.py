@@ -12,7 +12,14 @@ Reported:
            time the bytes it reads and writes would take at the sustained HBM rate that profiles/record_loader_timing.json
            records.  The pixels are checked against the synthesised images before anything is timed.
 
-A record, not a gate: nothing is asserted on the times.  Writes one JSON record (--out)."""
+  inflate  the device inflate (csrc/png_inflate.hip) on the same files in the same run, so that its yardstick -- the host
+           rows above: mmt_png_inflate at 16 workers plus its upload -- is measured beside it: mmt_png_gather at workers 1
+           and 16, the upload of compressed bytes, palettes, metadata and stream descriptors, mmt_png_scanlines at
+           subseq_bytes 16, 32, 64 and 128 by HIP events (median and range over the rounds), and
+           decode_png_images(inflate='device') end to end.  Status 0 and the scanlines' bytes are checked against the host
+           inflate's before anything is timed.  A second record (--inflate-out).
+
+A record, not a gate: nothing is asserted on the times.  Writes the JSON records (--out, --inflate-out)."""
 import argparse
 import ctypes
 import json
@@ -89,6 +96,7 @@ def main():
   ap.add_argument('--calls', type=int, default=4, help='calls per round (at least 20 calls over all rounds)')
   ap.add_argument('--host-rounds', type=int, default=3)
   ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'png_decode_timing.json'))
+  ap.add_argument('--inflate-out', default=os.path.join(ROOT, 'profiles', 'png_inflate_timing.json'))
   args = ap.parse_args()
   assert args.rounds * args.calls >= 20
 
@@ -195,6 +203,93 @@ def main():
     json.dump(rec, f, indent=1)
     f.write('\n')
   print('wrote', args.out)
+
+  # ---- the device inflate, against the host rows above ----
+  streams_c = (_lib.PngStream * B)()
+  n_comp = 0
+  for i, a in enumerate(files):
+    streams_c[i].comp_offset = n_comp
+    n_comp += a.size
+  comp = torch.empty(n_comp, dtype=torch.uint8).pin_memory()
+
+  def gather(i):
+    _lib.check(L.mmt_png_gather(files[i].ctypes.data, files[i].size, ctypes.byref(images[i]), comp.data_ptr(), n_comp, ctypes.byref(streams_c[i]),
+                                pal.data_ptr() + i * 768))
+
+  gather_ms = {str(w): round(best_of(args.host_rounds, lambda: over(w, gather, B)) * 1e3, 2) for w in (1, 16)}
+  smeta = torch.frombuffer(bytearray(bytes(streams_c)), dtype=torch.uint8).pin_memory()
+  comp_d, smeta_d = (torch.empty(t.numel(), dtype=torch.uint8, device=dev) for t in (comp, smeta))
+  ups_c = []
+  for _ in range(6):
+    e0.record()
+    for d, h in ((comp_d, comp), (pal_d, pal), (meta_d, meta), (smeta_d, smeta)):
+      d.copy_(h, non_blocking=True)
+    e1.record()
+    torch.cuda.synchronize()
+    ups_c.append(e0.elapsed_time(e1) * 1e3)
+  ups_c = ups_c[1:]
+  lines_d = torch.empty(n_raw, dtype=torch.uint8, device=dev)
+  status_d = torch.empty(B, dtype=torch.int32, device=dev)
+  need_inf = L.mmt_png_scanlines_workspace_bytes(B)
+  work_inf = torch.empty(need_inf, dtype=torch.uint8, device=dev)
+  scan = {}
+  for sb in (16, 32, 64, 128):
+    def inflate_call():
+      _lib.check(L.mmt_png_scanlines(B, meta_d.data_ptr(), smeta_d.data_ptr(), comp_d.data_ptr(), n_comp, lines_d.data_ptr(), n_raw,
+                                     status_d.data_ptr(), sb, work_inf.data_ptr(), need_inf, stream))
+    lines_d.zero_()
+    inflate_call()
+    torch.cuda.synchronize()
+    assert not bool(status_d.any()), status_d.cpu().tolist()
+    assert torch.equal(lines_d, raw_d), sb                      # the host inflate's scanlines, uploaded above
+    inflate_call()
+    ts = []
+    for _ in range(args.rounds):
+      e0.record()
+      for _ in range(args.calls):
+        inflate_call()
+      e1.record()
+      torch.cuda.synchronize()
+      ts.append(e0.elapsed_time(e1) / args.calls * 1e3)
+    scan[str(sb)] = {'us_median': round(statistics.median(ts), 1), 'us_min': round(min(ts), 1), 'us_max': round(max(ts), 1)}
+    print(f'  mmt_png_scanlines subseq_bytes {sb}: {scan[str(sb)]}')
+  one = {}
+  for sb in (16, 32, 64, 128):                                  # a single image: the latency of one workgroup
+    ts = []
+    for _ in range(args.rounds):
+      e0.record()
+      _lib.check(L.mmt_png_scanlines(1, meta_d.data_ptr(), smeta_d.data_ptr(), comp_d.data_ptr(), n_comp, lines_d.data_ptr(), n_raw,
+                                     status_d.data_ptr(), sb, work_inf.data_ptr(), need_inf, stream))
+      e1.record()
+      torch.cuda.synchronize()
+      ts.append(e0.elapsed_time(e1) * 1e3)
+    one[str(sb)] = {'us_median': round(statistics.median(ts[1:]), 1), 'us_min': round(min(ts[1:]), 1), 'us_max': round(max(ts[1:]), 1)}
+  whole_dev = fp.decode_png_images(files, dev, workers=16, inflate='device')[0]
+  assert torch.equal(whole_dev, out)
+  t_dev = {str(sb): round(best_of(args.host_rounds, lambda: (fp.decode_png_images(files, dev, workers=16, inflate='device', subseq_bytes=sb),
+                                                             torch.cuda.synchronize())) * 1e3, 2) for sb in (16, 32, 64, 128)}
+  best_sb = min(scan, key=lambda k: scan[k]['us_median'])
+  rec2 = {
+      'tool': 'tools/png_decode_timing.py', 'device': torch.cuda.get_device_name(0), 'batch': B, 'size': args.size, 'distinct_contents': args.distinct,
+      'file_bytes': [len(m[1]) for m in made], 'raw_bytes': n_raw, 'compressed_bytes': int(sum(s.comp_bytes for s in streams_c)),
+      'host_yardstick_same_run': {'mmt_png_inflate_ms_by_workers': {w: host[w]['mmt_png_inflate_ms'] for w in host},
+                                  'upload_bytes': rec['upload_bytes'], 'upload_us_median': rec['upload_us_median'],
+                                  'pixels_us_median': rec['pixels_us_median'], 'decode_png_images_ms_workers_16': rec['decode_png_images_ms_workers_16']},
+      'gather_ms_by_workers': gather_ms,
+      'upload_bytes': comp.numel() + pal.numel() + meta.numel() + smeta.numel(), 'upload_us_median': round(statistics.median(ups_c), 1),
+      'upload_us_min': round(min(ups_c), 1), 'upload_us_max': round(max(ups_c), 1),
+      'scanlines_us_by_subseq_bytes': scan, 'scanlines_one_image_us_by_subseq_bytes': one,
+      'scanlines_rounds': args.rounds, 'scanlines_calls_per_round': args.calls, 'launches': 1, 'best_subseq_bytes': int(best_sb),
+      'decode_png_images_device_inflate_ms_workers_16_by_subseq_bytes': t_dev,
+      'device_stages_ms': round(gather_ms['16'] + statistics.median(ups_c) / 1e3 + scan[best_sb]['us_median'] / 1e3, 2),
+      'host_stages_ms': round(host['16']['mmt_png_inflate_ms'] + rec['upload_us_median'] / 1e3, 2)}
+  print(f'  gather {gather_ms} ms; upload {rec2["upload_bytes"]} bytes {rec2["upload_us_median"]} us; one image {one}; '
+        f'decode_png_images(inflate=device) {t_dev} ms against {rec["decode_png_images_ms_workers_16"]} ms')
+  os.makedirs(os.path.dirname(os.path.abspath(args.inflate_out)), exist_ok=True)
+  with open(args.inflate_out, 'w') as f:
+    json.dump(rec2, f, indent=1)
+    f.write('\n')
+  print('wrote', args.inflate_out)
 
 
 if __name__ == '__main__':

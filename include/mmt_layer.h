@@ -145,6 +145,44 @@ int mmt_adamw_step(const mmt_adamw_desc* desc, float* param, float* grad, float*
                    float* exp_avg_sq, void* param_bf16, const float* chunk_wd,
                    const float* grad_scale, void* stream);
 
+/* One LAMB step over a flat parameter slab (TFM `optimizer.type: lamb` = tfa.optimizers.LAMB, restated from memory: no
+ * TensorFlow was at hand to pin it).  The slab is cut into n_segments parameters, each of whole 1024-element chunks:
+ * segment s owns chunks [segment_start[s], segment_start[s + 1]).  Per element i of chunk c in segment s, all in fp32:
+ *   g  = grad[i] * (*grad_scale)                     (clip factor / deferred 1/replicas, device scalar, may be NULL)
+ *   m  = b1 m + (1-b1) g;   v = b2 v + (1-b2) g^2;   mh = m / bc1;   vh = v / bc2
+ *   u  = mh / (sqrt(vh) + eps) + chunk_wd[c] * w     (chunk_wd is 0 for parameters excluded from weight decay)
+ *   r  = 1                                           when segment_adapt[s] == 0 (excluded from layer adaptation)
+ *   r  = ||w||2 / ||u||2 over the whole segment      otherwise, if both norms are > 0; else 1
+ *   w -= lr * r * u
+ * writes param, exp_avg, exp_avg_sq (fp32), the bf16 shadow copy (nullable) and, with zero_grad != 0, clears grad;
+ * with zero_grad == 0 grad holds u on return (the step uses the gradient slab for it).  Padding elements of a
+ * parameter's last chunk must be zero in all four slabs on entry and are zero on exit.  Three launches and no atomics:
+ * the sums have one fixed order that depends on the segment alone, so a step is bitwise reproducible and a
+ * parameter's ratio does not depend on what shares the slab with it.  chunk_wd (n / 1024 floats), segment_start
+ * (n_segments + 1 int32) and segment_adapt (n_segments int32) are DEVICE arrays; every chunk index read from
+ * segment_start is clamped into [0, n / 1024], so a wrong table gives wrong ratios and never a stray access.
+ * n must be a multiple of 1024; the fp32 slabs and the workspace 16-byte aligned; workspace: 12 bytes per chunk
+ * (mmt_lamb_workspace_bytes; 0 for a bad n), caller-owned, nothing is allocated and the host does not wait.
+ * `hyper` as in mmt_adamw_desc.  mmt_lamb_step_host runs the same per-element and per-chunk functions (csrc/lamb.h) as
+ * plain loops on HOST arrays. */
+typedef struct mmt_lamb_desc {
+  int64_t n;
+  float lr, beta1, beta2, eps;
+  float bias_correction1, bias_correction2;   /* 1 - beta^t */
+  int32_t zero_grad;
+  int32_t n_segments;
+  const float* hyper;    /* DEVICE {lr, bias_correction1, bias_correction2} read by the kernels INSTEAD of the three
+                            fields above, or NULL (mmt_attn.h: mmt_write_step_scalars)                                 */
+} mmt_lamb_desc;
+
+size_t mmt_lamb_workspace_bytes(int64_t n);
+int mmt_lamb_step(const mmt_lamb_desc* desc, float* param, float* grad, float* exp_avg, float* exp_avg_sq,
+                  void* param_bf16, const float* chunk_wd, const int32_t* segment_start, const int32_t* segment_adapt,
+                  const float* grad_scale, void* workspace, size_t workspace_bytes, void* stream);
+int mmt_lamb_step_host(const mmt_lamb_desc* desc, float* param, float* grad, float* exp_avg, float* exp_avg_sq,
+                       void* param_bf16, const float* chunk_wd, const int32_t* segment_start, const int32_t* segment_adapt,
+                       const float* grad_scale, void* workspace, size_t workspace_bytes);
+
 /* Weight gradient of a Dense layer, accumulated into the fp32 master gradient:
  *   dw[M,N] += dy[K,M]^T . x[K,N]        (bf16 operands, fp32 accumulation, float atomics)
  * = the per-layer `tape.gradient` product + `AccumulateGrad` of src/tasks/pretraining.py:262-296.

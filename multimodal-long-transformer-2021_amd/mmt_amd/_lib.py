@@ -53,7 +53,8 @@ EXPORTS = ('mmt_abi_version', 'mmt_last_error', 'mmt_write_step_scalars', 'mmt_w
            'mmt_jpeg_scan_plan', 'mmt_jpeg_entropy_workspace_bytes', 'mmt_jpeg_entropy', 'mmt_jpeg_entropy_host',
            'mmt_records_scan', 'mmt_example_fields', 'mmt_records_crc_workspace_bytes', 'mmt_records_crc', 'mmt_records_crc_host',
            'mmt_png_info', 'mmt_png_inflate', 'mmt_png_workspace_bytes', 'mmt_png_pixels', 'mmt_png_pixels_host',
-           'mmt_png_gather', 'mmt_png_scanlines_workspace_bytes', 'mmt_png_scanlines', 'mmt_png_scanlines_host')
+           'mmt_png_gather', 'mmt_png_scanlines_workspace_bytes', 'mmt_png_scanlines', 'mmt_png_scanlines_host',
+           'mmt_lamb_workspace_bytes', 'mmt_lamb_step', 'mmt_lamb_step_host')
 
 
 class EmbedDesc(ctypes.Structure):
@@ -95,6 +96,13 @@ class AdamwDesc(ctypes.Structure):
               ('beta2', ctypes.c_float), ('eps', ctypes.c_float), ('bias_correction1', ctypes.c_float),
               ('bias_correction2', ctypes.c_float), ('zero_grad', ctypes.c_int32),
               ('reserved', ctypes.c_int32), ('hyper', ctypes.c_void_p)]
+
+
+class LambDesc(ctypes.Structure):       # mmt_adamw_desc with the slab's parameter-segment count in the reserved word
+  _fields_ = [('n', ctypes.c_int64), ('lr', ctypes.c_float), ('beta1', ctypes.c_float),
+              ('beta2', ctypes.c_float), ('eps', ctypes.c_float), ('bias_correction1', ctypes.c_float),
+              ('bias_correction2', ctypes.c_float), ('zero_grad', ctypes.c_int32),
+              ('n_segments', ctypes.c_int32), ('hyper', ctypes.c_void_p)]
 
 
 class ImageDesc(ctypes.Structure):
@@ -282,6 +290,12 @@ def lib() -> ctypes.CDLL:
   L.mmt_wgrad_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64]
   L.mmt_adamw_step.restype = ctypes.c_int
   L.mmt_adamw_step.argtypes = [ctypes.POINTER(AdamwDesc)] + [vp] * 8
+  L.mmt_lamb_workspace_bytes.restype = ctypes.c_size_t
+  L.mmt_lamb_workspace_bytes.argtypes = [ctypes.c_int64]
+  L.mmt_lamb_step.restype = ctypes.c_int
+  L.mmt_lamb_step.argtypes = [ctypes.POINTER(LambDesc)] + [vp] * 10 + [ctypes.c_size_t, vp]
+  L.mmt_lamb_step_host.restype = ctypes.c_int
+  L.mmt_lamb_step_host.argtypes = [ctypes.POINTER(LambDesc)] + [vp] * 10 + [ctypes.c_size_t]
   L.mmt_grad_clip_scale.restype = ctypes.c_int
   L.mmt_grad_clip_scale.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64), ctypes.c_float,
                                     ctypes.c_float, vp, vp, vp, ctypes.c_size_t, vp]

@@ -219,6 +219,16 @@ class OptimizerConfig(Config):   # the adamw / polynomial / warmup block of `_TR
   power: float = 1.0
   warmup_steps: int = 0
   warmup_power: float = 1.0
+  # Build-visible: which block of TFM's `optimizer` OneOf the fields above were flattened from -- 'adamw' or 'lamb'
+  # (`optimization.create_optimizer` dispatches on it) -- and LAMB's second exclusion list (None = the same list as
+  # exclude_from_weight_decay)
+  optimizer_type: str = 'adamw'
+  exclude_from_layer_adaptation: Optional[List[str]] = None
+
+
+# TFM `LAMBConfig` defaults for the keys a `lamb` block omits (recalled, not pinned: no TF Model Garden at hand)
+_LAMB_DEFAULTS = {'weight_decay_rate': 0.0, 'exclude_from_weight_decay': [], 'exclude_from_layer_adaptation': None,
+                  'epsilon': 1e-6, 'beta_1': 0.9, 'beta_2': 0.999}
 
 
 @dataclasses.dataclass
@@ -239,11 +249,16 @@ class TrainerConfig(Config):
 
   def override(self, values, strict=False, _path=''):
     # accept the nested TFM layout optimizer_config.{optimizer.adamw, learning_rate.polynomial,
-    # warmup.polynomial}.* by flattening it onto OptimizerConfig
+    # warmup.polynomial}.* by flattening it onto OptimizerConfig; `optimizer.type: lamb` takes the `lamb` block instead,
+    # over LAMBConfig's defaults, and says so in `optimizer_type` (any other type: the adamw block, as ever)
     oc = values.get('optimizer_config')
     if isinstance(oc, dict):
       flat = {}
-      for block, inner in (('optimizer', 'adamw'), ('learning_rate', 'polynomial'), ('warmup', 'polynomial')):
+      opt_block = 'adamw'
+      if (oc.get('optimizer') or {}).get('type') == 'lamb':
+        opt_block = 'lamb'
+        flat = dict(copy.deepcopy(_LAMB_DEFAULTS), optimizer_type='lamb')
+      for block, inner in (('optimizer', opt_block), ('learning_rate', 'polynomial'), ('warmup', 'polynomial')):
         sub = (oc.get(block) or {}).get(inner) or {}
         for k, v in sub.items():
           flat['warmup_power' if (block == 'warmup' and k == 'power') else k] = v

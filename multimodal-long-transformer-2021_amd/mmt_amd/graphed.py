@@ -35,7 +35,7 @@ class GraphedTrainStep:
   def __init__(self, task, model, optimizer, reducer, opt_cfg, *, metrics=None, clip_norm: Optional[float] = None,
                eager_steps: int = 3, static_inputs: bool = False):
     if not hasattr(optimizer, 'slabs'):
-      raise ValueError('GraphedTrainStep needs the flat optimizer (optimization.FusedAdamW): its state has fixed addresses')
+      raise ValueError('GraphedTrainStep needs a flat optimizer (optimization.FusedAdamW / FusedLamb): its state has fixed addresses')
     self.task, self.model, self.optimizer, self.reducer = task, model, optimizer, reducer
     self.opt_cfg, self.metrics, self.clip_norm = opt_cfg, metrics, clip_norm
     self.eager_left = max(1, int(eager_steps))

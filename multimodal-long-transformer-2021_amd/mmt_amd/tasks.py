@@ -154,7 +154,7 @@ class _TaskBase:
           grad_loss = loss / num_small_steps
         grad_loss.backward()
         all_loss = all_loss + (loss / num_small_steps).detach()
-      fused_opt = hasattr(optimizer, 'slabs')          # optimization.FusedAdamW
+      fused_opt = hasattr(optimizer, 'slabs')          # optimization.FusedAdamW / FusedLamb
       scale = None
       if reducer is not None:
         # gradient all-reduce == optimizer.apply_gradients(:273); a fused optimizer applies 1/world itself

@@ -82,7 +82,10 @@ int mmt_colsum_reduce(const mmt_rows_desc* desc, int32_t kind, const void* works
 
 /* The same for up to 48 deferred reduces in ONE launch (a host that needs no parameter gradient before the backward
  * pass ends queues them: ~32 five-microsecond launches per step otherwise).  rows / H / kind / accumulate as in the
- * desc and call they stand for. */
+ * desc and call they stand for.  The outputs of the items (H floats each) must not overlap one another: every output is
+ * read, added to and stored by a workgroup of its own item, so of two sums into the same memory one could be lost.  Such a
+ * batch is refused before any launch with MMT_E_INVALID and a message that names both items (a parameter used twice in
+ * one backward pass: launch its reduces one after the other). */
 typedef struct mmt_colsum_item {
   const void* workspace;
   float* o0; float* o1; float* o2;
@@ -215,7 +218,12 @@ int mmt_wgrad_bias_accumulate(float* dw, int64_t ldw, float* dbias, const void* 
  * the whole K, and only the tail that does not fill a round is split -- into compact per-tile slabs, reduced by a small
  * second launch (seven blocks: 756 tiles = 2 rounds + 244 unsplit; five: 2 rounds + 28 tiles x 8 slices).
  * Every problem needs M % 256 == 0, N % 256 == 0; K % 64 == 0; the workspace (mmt_wgrad_group_workspace_bytes, may be
- * 0 bytes) is required.  dbias may be NULL per problem.  Results are bitwise those of a fixed-order sum over the slices. */
+ * 0 bytes) is required.  dbias may be NULL per problem.  Results are bitwise those of a fixed-order sum over the slices.
+ * The outputs of a group must not overlap one another, judged by address range: dw from its first element to the last
+ * one of row M - 1 (row stride ldw), dbias M floats.  Tiles of different problems are added into dw by different
+ * workgroups with plain loads and stores, so of two products into the same memory one could be lost.  Such a group is
+ * refused before any launch: mmt_wgrad_grouped returns MMT_E_INVALID and mmt_wgrad_group_workspace_bytes 0, each with a
+ * message (mmt_last_error) that names the two problems.  Launch them one after the other. */
 typedef struct mmt_wgrad_problem {
   float* dw;        /* [M, N] fp32, row stride ldw, accumulated into */
   int64_t ldw;

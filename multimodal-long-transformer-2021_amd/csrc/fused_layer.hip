@@ -734,6 +734,18 @@ int mmt_colsum_reduce_batch(int32_t n, const mmt_colsum_item* items, void* strea
     end += (ksets * it.H + mmt::kCsCols - 1) / mmt::kCsCols;
     g.blocks_end[i] = end;
   }
+  // two outputs on the same memory (a parameter used twice in one backward pass): each is read, added to and stored by a
+  // workgroup of its own item, so one sum could be lost -- refused here, the host launches such items one after the other
+  for (int i = 0; i < n; ++i)
+    for (int a = 0; a < g.ksets[i]; ++a) {
+      const uintptr_t lo = (uintptr_t)(a == 0 ? g.o0[i] : (a == 1 ? g.o1[i] : g.o2[i])), hi = lo + (uintptr_t)g.H[i] * sizeof(float);
+      for (int j = i; j < n; ++j)
+        for (int b = (j == i ? a + 1 : 0); b < g.ksets[j]; ++b) {
+          const uintptr_t lo2 = (uintptr_t)(b == 0 ? g.o0[j] : (b == 1 ? g.o1[j] : g.o2[j])), hi2 = lo2 + (uintptr_t)g.H[j] * sizeof(float);
+          if (lo < hi2 && lo2 < hi)
+            return lfail(MMT_E_INVALID, "mmt_colsum_reduce_batch: output %d of item %d overlaps output %d of item %d", b, j, a, i);
+        }
+    }
   hipError_t e = mmt::launch_colsum_reduce_batch(g, (hipStream_t)stream);
   return e == hipSuccess ? MMT_OK : lfail(MMT_E_LAUNCH, "mmt_colsum_reduce_batch: %s", hipGetErrorString(e));
 }

@@ -668,6 +668,26 @@ bool group_ok(int32_t n, const mmt_wgrad_problem* pr, int64_t K) {
   }
   return true;
 }
+// Two problems of one group that name the same output memory: the unsplit tiles read, add and store dw (and dbias) from
+// one workgroup per tile and problem, and the grouped reduce does the same per problem, so one of the two contributions
+// could be lost.  Judged by address range -- dw: from its first element to the last one of row M - 1; dbias: M floats --
+// so a view into another problem's buffer counts.  Returns 0, or fails with the two problems' indices.
+int group_outputs_disjoint(const char* who, int32_t n, const mmt_wgrad_problem* pr) {
+  struct Range { uintptr_t lo, hi; int problem; const char* what; };
+  Range r[2 * mmt::kBigMax];
+  int m = 0;
+  for (int i = 0; i < n; ++i) {
+    const uintptr_t dw = (uintptr_t)pr[i].dw;
+    r[m++] = {dw, dw + (((uintptr_t)pr[i].M - 1) * (uintptr_t)pr[i].ldw + (uintptr_t)pr[i].N) * sizeof(float), i, "dw"};
+    if (pr[i].dbias) r[m++] = {(uintptr_t)pr[i].dbias, (uintptr_t)pr[i].dbias + (uintptr_t)pr[i].M * sizeof(float), i, "dbias"};
+  }
+  for (int a = 0; a < m; ++a)
+    for (int b = a + 1; b < m; ++b)
+      if (r[a].lo < r[b].hi && r[b].lo < r[a].hi)
+        return mmt::fail(MMT_E_INVALID, "%s: %s of problem %d overlaps %s of problem %d (launch them one after the other)",
+                         who, r[b].what, r[b].problem, r[a].what, r[a].problem);
+  return MMT_OK;
+}
 // split-K factor and rows per slice of a group with `tiles` 256 x 256 tiles in all
 void group_split(int tiles, int64_t K, int& split, int& kps) {
   const int cus = g_cu_budget.load(std::memory_order_relaxed);
@@ -710,6 +730,7 @@ bool use_big(int32_t n, const mmt_wgrad_problem* pr) {
 
 extern "C" size_t mmt_wgrad_group_workspace_bytes(int32_t n, const mmt_wgrad_problem* problems, int64_t K) {
   if (!group_ok(n, problems, K)) return 0;
+  if (group_outputs_disjoint("mmt_wgrad_group_workspace_bytes", n, problems) != MMT_OK) return 0;
   if (use_big(n, problems)) {
     const BigPlan b = big_plan(n, problems, K);
     return b.split > 1 ? (size_t)b.tail * b.split * (65536 + 256) * sizeof(float) : 0;
@@ -726,6 +747,7 @@ extern "C" int mmt_wgrad_grouped(int32_t n, const mmt_wgrad_problem* problems, i
                                  size_t workspace_bytes, void* stream) {
   if (!group_ok(n, problems, K))
     return mmt::fail(MMT_E_UNSUPPORTED, "mmt_wgrad_grouped: needs 1..28 problems with M %% 256 == 0, N %% 256 == 0, K %% 64 == 0, 16-byte aligned operands");
+  if (int rc = group_outputs_disjoint("mmt_wgrad_grouped", n, problems)) return rc;
   const size_t need = mmt_wgrad_group_workspace_bytes(n, problems, K);
   if (need > 0 && (!workspace || workspace_bytes < need)) return mmt::fail(MMT_E_WORKSPACE, "mmt_wgrad_grouped: workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
   if (use_big(n, problems)) {

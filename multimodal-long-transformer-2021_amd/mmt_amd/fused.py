@@ -28,6 +28,7 @@ def set_seed_stream(step: int, micro_step: int = 0, rank: int = 0) -> None:
   _seed_state['base'] = ((int(micro_step) * 0xC2B2AE3D27D4EB4F) ^ ((int(rank) + 1) * 0x165667B19E3779F9)) & ((1 << 63) - 1)
   _seed_state['n'] = 0
   step_scalars.set_step(step)
+  _forget_stale_queues()
 
 
 def next_seed(base: int = 0) -> int:
@@ -39,6 +40,7 @@ def next_seed(base: int = 0) -> int:
 
 
 def _desc(x2d: torch.Tensor, eps=1e-12, p=0.0, seed=0) -> _lib.RowsDesc:
+  _forget_stale_queues()
   d = _lib.RowsDesc()
   d.rows, d.H = x2d.shape[0], x2d.shape[1]
   if x2d.dtype == torch.float32:
@@ -100,7 +102,44 @@ def _finish(param, buf, direct):
 # reduces are queued (desc.defer_reduce; the workspaces stay alive in the queue) and launched ONCE by an engine callback
 # at the end of backward (`mmt_colsum_reduce_batch`).
 _CS_MAX = 48
-_cs_deferred = {}          # device -> (graph-task id, [(workspace, rows, H, kind, outs)])
+# (device, graph-task id) -> (graph-task id, [(workspace, rows, H, kind, outs)]): ONE entry per backward pass and device.
+# A re-entrant pass (torch.utils.checkpoint(..., use_reentrant=True) runs one inside a node of the outer pass) has an id
+# and an entry of its own, flushed by its own end-of-backward callback; the outer pass's entry waits for the outer one.
+_cs_deferred = {}
+
+
+def _byte_range(t: torch.Tensor):
+  """[lo, hi) addresses a row-strided 2-D (or contiguous 1-D) tensor spans, gaps between its rows included."""
+  lo = t.data_ptr()
+  n = t.numel() if t.dim() != 2 else (t.shape[0] - 1) * t.stride(0) + t.shape[1]
+  return lo, lo + n * t.element_size()
+
+
+def _ranges_overlap(a, b) -> bool:
+  return any(x[0] < y[1] and y[0] < x[1] for x in a for y in b)
+
+
+def _drop_entries(queue, stale) -> None:
+  for key in stale:
+    for item in queue.pop(key)[1]:
+      for prm in (item[4] if queue is _wg_deferred else ()):
+        prm._mmt_grad_deferred = False
+
+
+def _forget_passes_after(gid) -> None:
+  """A pass whose id is larger than the running one's began after it, i.e. inside one of its nodes, and has returned: what
+  it still has queued was left behind when it raised (its end-of-backward callback never ran) and is nobody's to launch."""
+  for queue in (_cs_deferred, _wg_deferred):
+    _drop_entries(queue, [key for key in queue if key[1] > gid])
+
+
+def _forget_stale_queues() -> None:
+  """Called where a forward pass starts work (descriptors, the step's seed stream): OUTSIDE any backward pass every queued
+  item was left behind by a pass that raised -- its operands belong to a step that is over -- and is dropped.  (Inside
+  one -- a checkpointed segment recomputed by the outer pass -- the outer pass's items are alive and stay.)"""
+  if (_wg_deferred or _cs_deferred) and _graph_task_id() == -1 and grouping_is_safe():
+    for queue in (_cs_deferred, _wg_deferred):
+      _drop_entries(queue, list(queue))
 
 
 def _defer_colsum_ok(direct: bool, *params) -> bool:
@@ -108,13 +147,10 @@ def _defer_colsum_ok(direct: bool, *params) -> bool:
           and not any(getattr(p, '_mmt_grad_ready_hooks', ()) for p in params if p is not None))
 
 
-def _flush_colsum(device) -> None:
-  entry = _cs_deferred.pop(device, None)
-  if not entry or not entry[1]:
-    return
-  items = entry[1]
+def _launch_colsum_batch(items, device) -> None:
+  """The queued reduces in one launch on the current stream of `device`."""
   arr = (_lib.ColsumItem * len(items))()
-  for q, (ws, rows, H, kind, outs) in zip(arr, items):
+  for q, (ws, rows, H, kind, outs, *_) in zip(arr, items):
     o = list(outs) + [None] * (3 - len(outs))
     q.workspace, q.o0, q.o1, q.o2 = ws.data_ptr(), _p(o[0]), _p(o[1]), _p(o[2])
     q.rows, q.H, q.kind, q.accumulate = rows, H, kind, 1
@@ -122,24 +158,39 @@ def _flush_colsum(device) -> None:
     _lib.check(_lib.lib().mmt_colsum_reduce_batch(len(items), arr, torch.cuda.current_stream(device).cuda_stream))
 
 
+def _flush_colsum(key) -> None:
+  entry = _cs_deferred.pop(key, None)
+  if not entry or not entry[1]:
+    return
+  _launch_colsum_batch(entry[1], key[0])
+
+
 def _flush_all_colsum():
-  for device in list(_cs_deferred):
-    _flush_colsum(device)
+  """End-of-backward callback: the reduces of the pass that is ending (the callback runs under its graph-task id)."""
+  gid = _graph_task_id()
+  for key in [k for k in _cs_deferred if k[1] == gid]:
+    _flush_colsum(key)
+  _forget_passes_after(gid)
 
 
 def _defer_colsum(ws, rows: int, H: int, kind: int, outs) -> None:
-  device = ws.device
   gid = _graph_task_id()
-  entry = _cs_deferred.get(device)
-  if entry is not None and entry[0] != gid:              # left behind by a backward pass that raised: not ours to launch
-    _cs_deferred.pop(device)
+  key = (ws.device, gid)
+  _forget_passes_after(gid)
+  outs = tuple(outs)
+  ranges = tuple(_byte_range(o) for o in outs if o is not None)
+  entry = _cs_deferred.get(key)
+  # an output another queued reduce adds to as well (a bias or LayerNorm parameter used twice in this pass): every reduce
+  # of a batch reads, adds and stores from a workgroup of its own, so the two go in launches one after the other
+  if entry is not None and any(_ranges_overlap(ranges, item[5]) for item in entry[1]):
+    _flush_colsum(key)
     entry = None
   if entry is None:
-    entry = _cs_deferred[device] = (gid, [])
+    entry = _cs_deferred[key] = (gid, [])
     torch.autograd.Variable._execution_engine.queue_callback(_flush_all_colsum)    # end of this backward pass
-  entry[1].append((ws, rows, H, kind, tuple(outs)))
+  entry[1].append((ws, rows, H, kind, outs, ranges))
   if len(entry[1]) >= _CS_MAX:
-    _flush_colsum(device)          # (a later item opens a new entry and queues another callback: harmless)
+    _flush_colsum(key)             # (a later item opens a new entry and queues another callback: harmless)
 
 
 class _LayerNormFn(torch.autograd.Function):
@@ -495,9 +546,10 @@ _WG_GROUP = 4
 _WG_GROUP_ALONE = 28
 
 
-def _launch_wgrad_group(items, device, stream) -> None:
-  """The queued products on `stream` (the current stream of the caller's `torch.cuda.stream` context)."""
+def _launch_wgrad_group(items, device) -> None:
+  """The queued products on the current stream of `device` (that of the caller's `torch.cuda.stream` context)."""
   L = _lib.lib()
+  stream = torch.cuda.current_stream(device)
   if len(items) == 1:
     dw, dy, x, dbias = items[0][:4]
     if not wgrad_accumulate_(dw, dy, x, dbias):
@@ -517,59 +569,70 @@ def _launch_wgrad_group(items, device, stream) -> None:
 # The products are queued and launched together on the CURRENT stream, and only then are the
 # parameters reported ready -- the reducer ignores autograd's own post-accumulate notification for a parameter
 # while `_mmt_grad_deferred` is set, so a bucket's all-reduce can never be enqueued ahead of its last product.
+# (device, graph-task id) -> (graph-task id, [(dw, dy, x, dbias, notify, output ranges)]), keyed as `_cs_deferred` is.
 _wg_deferred = {}
 
 
-def _flush_wgrad_deferred(device) -> None:
-  entry = _wg_deferred.pop(device, None)
+def _flush_wgrad_deferred(key) -> None:
+  entry = _wg_deferred.pop(key, None)
   if not entry or not entry[1]:
     return
   items = entry[1]
-  _launch_wgrad_group(items, device, torch.cuda.current_stream(device))
+  _launch_wgrad_group(items, key[0])
+  still_queued = {id(prm) for e in _wg_deferred.values() for item in e[1] for prm in item[4]}
   for item in items:
     for prm in item[4]:
-      for hook in getattr(prm, '_mmt_grad_ready_hooks', ()):
-        hook(prm)
+      if id(prm) not in still_queued:          # (a parameter used again later in the pass is reported at that launch)
+        prm._mmt_grad_deferred = False
+        for hook in getattr(prm, '_mmt_grad_ready_hooks', ()):
+          hook(prm)
 
 
 def reset_host_queues() -> None:
-  """Forgets every weight-gradient product a backward pass has queued but not launched.  For a step that was ABANDONED half-way (a graph capture that raised inside backward, `graphed.py`): its
-  queued products point at activations of a step that never ran; the retry must not launch them."""
-  _wg_deferred.clear()
-  _cs_deferred.clear()
+  """Forgets every weight-gradient product and column-sum reduce a backward pass has queued but not launched.  For a step
+  that was ABANDONED half-way (a graph capture that raised inside backward, `graphed.py`): its queued products point at
+  activations of a step that never ran; the retry must not launch them."""
+  for queue in (_cs_deferred, _wg_deferred):
+    _drop_entries(queue, list(queue))
 
 
 def _flush_all_deferred():
-  for device in list(_wg_deferred):
-    _flush_wgrad_deferred(device)
+  """End-of-backward callback: the products of the pass that is ending (the callback runs under its graph-task id)."""
+  gid = _graph_task_id()
+  for key in [k for k in _wg_deferred if k[1] == gid]:
+    _flush_wgrad_deferred(key)
+  _forget_passes_after(gid)
 
 
 def wgrad_accumulate_deferred_(dw, dy, x, dbias, notify) -> bool:
   """Queues dw += dy^T x (dbias += column sums) for a grouped launch on the current stream; `notify` = the
   parameters whose gradient-ready hooks run once the launch is enqueued.  False: not a shape the grouped kernel
   takes (the caller launches and notifies at once)."""
-  device = dw.device
   if _WG_GROUP <= 1 or not _wgrad_groupable(dw, dy, x, dbias):
     return False
   gid = _graph_task_id()
-  entry = _wg_deferred.get(device)
-  if entry is not None and entry[0] != gid:              # left behind by a backward pass that raised
-    for item in _wg_deferred.pop(device)[1]:
-      for prm in item[4]:
-        prm._mmt_grad_deferred = False
-    entry = None
+  key = (dw.device, gid)
+  _forget_passes_after(gid)
+  ranges = (_byte_range(dw),) + (() if dbias is None else (_byte_range(dbias),))
+  entry = _wg_deferred.get(key)
   if entry is not None and entry[1] and entry[1][0][1].shape[0] != dy.shape[0]:
-    _flush_wgrad_deferred(device)
+    _flush_wgrad_deferred(key)
+    entry = None
+  # an output a queued product adds to as well (a weight or bias used twice in this pass, or a view into the same
+  # gradient buffer): the tiles of one launch are added by different workgroups with plain loads and stores, so the
+  # queue is launched first and this product goes into the next one, stream-ordered behind it
+  if entry is not None and any(_ranges_overlap(ranges, item[5]) for item in entry[1]):
+    _flush_wgrad_deferred(key)
     entry = None
   if entry is None:
-    entry = _wg_deferred[device] = (gid, [])
+    entry = _wg_deferred[key] = (gid, [])
     torch.autograd.Variable._execution_engine.queue_callback(_flush_all_deferred)    # end of this backward pass
   for prm in notify:
     prm._mmt_grad_deferred = True
-  entry[1].append((dw, dy, x, dbias, tuple(notify)))
+  entry[1].append((dw, dy, x, dbias, tuple(notify), ranges))
   exchanged = any(getattr(prm, '_mmt_grad_ready_hooks', ()) for item in entry[1] for prm in item[4])
   if len(entry[1]) >= (_WG_GROUP if exchanged else _WG_GROUP_ALONE):
-    _flush_wgrad_deferred(device)
+    _flush_wgrad_deferred(key)
   return True
 
 

@@ -18,7 +18,10 @@ from typing import Optional
 
 import torch
 
-from . import fused, optimization, step_scalars
+from . import fused, ops, optimization, step_scalars
+
+# arrival counters reserved for a recorded step (one word per attention plane, batch x heads: ops.reserve_sync_words)
+_SYNC_WORDS = 4096
 
 
 def _tensors(tree):
@@ -44,6 +47,7 @@ class GraphedTrainStep:
     self.static_inputs = bool(static_inputs)
     self.graph = None
     self.scalars = None
+    self.sync_words = None
     self.static_batch = None
     self.out = None
     self._warned_shape = False
@@ -94,15 +98,20 @@ class GraphedTrainStep:
     t_before = self.optimizer.t
     torch.cuda.synchronize(dev)
     graph = torch.cuda.CUDAGraph()
+    # the capture stream is this step's own, with arrival counters reserved on it BEFORE the capture (made and zeroed
+    # eagerly, held until close()): the recorded attention launches name them, and nothing else ever does
+    stream = torch.cuda.Stream(dev)
+    self.sync_words = ops.reserve_sync_words(dev, stream, _SYNC_WORDS)
     # the device-resident scalars are "active" (named by every descriptor that is filled in) ONLY while the step is
     # being recorded: the recorded launches keep the pointers, replays fill in no descriptor at all, and eager steps
     # of this or any other model in the process go on taking their epoch and learning rate from the host
     self.scalars.enable()
     try:
-      with torch.cuda.graph(graph):
+      with torch.cuda.graph(graph, stream=stream):
         self.out = self.task.train_step(self.static_batch, self.model, self.optimizer, metrics=self.metrics,
                                         reducer=self.reducer, clip_norm=self.clip_norm, step=step)
     finally:
+      ops.release_sync_words(dev, stream)
       self.scalars.disable()
       self.optimizer.t = t_before          # recording runs nothing: the step itself is the first replay
     self.graph = graph
@@ -148,9 +157,10 @@ class GraphedTrainStep:
     torch.cuda.synchronize()
 
   def close(self):
-    """Drops the recorded graph and the device-resident scalars its launches read (the graph goes first: it holds
-    their addresses)."""
+    """Drops the recorded graph, then the device-resident scalars its launches read and the arrival counters they
+    name (the graph goes first: it holds their addresses)."""
     self.graph = None
+    self.sync_words = None
     if self.scalars is not None:
       self.scalars.disable()
       self.scalars = None

@@ -245,19 +245,60 @@ def _strides(t: torch.Tensor):
   return (t.stride(0), t.stride(1), t.stride(2))
 
 
+# Arrival counters of the kernels that merge partial results inside one launch (`mmt_attn_desc.sync`).  Who owns them:
+#   * eager calls: `_SYNC`, one zero-filled buffer per (device, stream), created and grown here on that stream.  Calls
+#     that share one are stream-ordered and every call leaves it zeroed.  Never named by a captured launch, so an entry
+#     may be replaced by a larger one or evicted: the allocator frees it in the order of the stream it was made on.
+#   * launches recorded into a graph: ONLY counters reserved before the capture (`reserve_sync_words`).  Whoever records
+#     the graph holds that tensor for as long as the graph lives; it is handed out on its stream between `reserve` and
+#     `release` only, so no eager call and no other graph shares it.  Without a reservation a capturing call gets no
+#     counters (nothing is allocated or zero-filled by a captured node -- a fill that exists only as a node of a graph
+#     that is abandoned, or never replayed, never runs) and the library takes its forms without an in-launch merge.
 _SYNC = {}
+_SYNC_RESERVED = {}
+_SYNC_MAX_KEYS = 64
+_SYNC_MIN_WORDS = 1024
 
 
-def _sync_words(device, stream_ptr: int, words: int) -> torch.Tensor:
-  """The zero-initialised arrival counters kernels that combine partial results inside one launch need
-  (`mmt_attn_desc.sync`): one buffer per (device, stream) -- calls that share one must be stream-ordered -- created
-  zeroed once; every call leaves it zeroed."""
-  key = (str(device), int(stream_ptr))
+def _sync_key(device, stream_ptr):
+  device = torch.device(device)
+  if device.index is None:
+    device = torch.device(device.type, torch.cuda.current_device())
+  return (str(device), int(stream_ptr))
+
+
+def reserve_sync_words(device, stream, words: int) -> torch.Tensor:
+  """Zero-filled arrival counters for the launches about to be CAPTURED on `stream` (a `torch.cuda.Stream` the caller
+  owns and passes to `torch.cuda.graph(..., stream=stream)`).  Call it before the capture begins, keep the tensor until
+  the graph is dropped, and call `release_sync_words` when the capture has ended (or raised)."""
+  if torch.cuda.is_current_stream_capturing():
+    raise RuntimeError('reserve_sync_words: reserve the counters before the capture begins')
+  key = _sync_key(device, stream.cuda_stream)
+  with torch.cuda.stream(stream):
+    t = torch.zeros(max(int(words), _SYNC_MIN_WORDS), dtype=torch.int32, device=device)
+  stream.synchronize()             # the fill has run: replays may come from any stream
+  _SYNC_RESERVED[key] = t
+  return t
+
+
+def release_sync_words(device, stream) -> None:
+  """Ends the reservation of `reserve_sync_words`: the counters are handed to no further call (the caller keeps them
+  alive for the recorded launches that name them)."""
+  _SYNC_RESERVED.pop(_sync_key(device, stream.cuda_stream), None)
+
+
+def _sync_words(device, stream_ptr: int, words: int) -> Optional[torch.Tensor]:
+  """The arrival counters for a call on (device, stream), or None: a call that is being captured on a stream nobody
+  reserved counters for (or too few)."""
+  key = _sync_key(device, stream_ptr)
+  if torch.cuda.is_current_stream_capturing():
+    t = _SYNC_RESERVED.get(key)
+    return t if t is not None and t.numel() >= words else None
   t = _SYNC.get(key)
   if t is None or t.numel() < words:
-    if len(_SYNC) > 64:
-      _SYNC.clear()
-    t = _SYNC[key] = torch.zeros(max(int(words), 1024), dtype=torch.int32, device=device)
+    if key not in _SYNC and len(_SYNC) >= _SYNC_MAX_KEYS:
+      _SYNC.pop(next(iter(_SYNC)))            # (oldest first; eager-only buffers, see above)
+    t = _SYNC[key] = torch.zeros(max(int(words), _SYNC_MIN_WORDS), dtype=torch.int32, device=device)
   return t
 
 
@@ -292,7 +333,10 @@ def _make_desc(q, k, v, out, R, pattern, valid_len, scale, mask_value, scale_bef
   d.mask = (pattern or AttentionPattern(id_mode=_lib.MMT_IDS_NONE)).to_desc(valid_len, q.device)
   d.tuning = int(tuning)
   sync = _sync_words(q.device, _stream_ptr(q.device), B * N)
-  d.sync, d.sync_words = sync.data_ptr(), sync.numel()
+  if sync is not None:
+    d.sync, d.sync_words = sync.data_ptr(), sync.numel()
+  else:
+    d.sync, d.sync_words = None, 0
   return d
 
 

@@ -202,6 +202,7 @@ class PairScorer:
     self.image_entry = torch.full((self.batch_size,), -1, dtype=torch.int32, device=dev)
     self.text_entry = torch.full((self.batch_size,), -1, dtype=torch.int32, device=dev)
     self.graph = None
+    self.sync_words = None
     self.out = None
     self._eager_done = False
     from .encoder import MmtEncoder
@@ -220,10 +221,19 @@ class PairScorer:
     return scores_from_logits(outputs[self.logits_key])
 
   def _record(self):
-    torch.cuda.synchronize(self.sets.device)
+    from . import ops
+    dev = self.sets.device
+    torch.cuda.synchronize(dev)
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-      self.out = self._forward(self.image_entry, self.text_entry)
+    # a capture stream of the scorer's own with arrival counters reserved on it before the capture; the scorer holds them
+    # for as long as the graph lives (ops.reserve_sync_words)
+    stream = torch.cuda.Stream(dev)
+    self.sync_words = ops.reserve_sync_words(dev, stream, 4096)
+    try:
+      with torch.cuda.graph(graph, stream=stream):
+        self.out = self._forward(self.image_entry, self.text_entry)
+    finally:
+      ops.release_sync_words(dev, stream)
     self.graph = graph
 
   def _batch(self) -> torch.Tensor:
@@ -296,7 +306,8 @@ class PairScorer:
     return torch.cat(parts)[:n] if parts else torch.empty(0, dtype=torch.float32, device=dev)
 
   def close(self):
-    self.graph = None
+    self.graph = None            # (first: its launches name the counters)
+    self.sync_words = None
     self.out = None
 
 

@@ -823,6 +823,56 @@ int mmt_png_scanlines_host(int32_t B, const mmt_png_image* images, const mmt_png
                            int64_t comp_bytes, uint8_t* raw_out, int64_t raw_bytes, int32_t* status_out /* [B] */,
                            int32_t subseq_bytes, void* workspace, size_t workspace_bytes);
 
+/* Packing short examples into long rows for the train step ("Packed batches").  In: E unpacked
+ * examples, word_ids and segment_ids int32 [E, S], lengths int32 [E] (the loaders' valid_len), and up to two position
+ * tables int32 [E, n_mlm] / [E, n_mpp] (positions inside the example; either may be NULL).  Out: R rows of S_row positions.
+ *
+ * Rule (next-fit, arrival order): example i joins the current row if used + len_i <= S_row, otherwise it opens the next
+ * row; packing stops before the first example that would open row R, and after E_max examples.  `consumed` examples
+ * are taken, always a prefix of the input; packed example e is input example e.
+ *
+ * Outputs, every element written by every call (nothing needs initialising):
+ *   out_word_ids, out_segment_ids  [R, S_row]  the examples' first len positions back to back; tails 0
+ *   example_ids, example_starts, patch_slots  [R, S_row]  the layout the packed kernels read (mmt_attn.h,
+ *                   MMT_FLAG_EXAMPLE_IDS | MMT_FLAG_EXAMPLE_STARTS; mmt_embed_fwd_packed): ids fall from the row's example
+ *                   count to 1 and are 0 in the tail, starts name the first position of the run (the tail is a run),
+ *                   the slot is the example's index in the input (every example carries an image), -1 in the tail
+ *   first_positions int64 [E_max, 2]   (row, first position); (0, 0) for an absent slot e >= consumed
+ *   example_weight  float [E_max]      1 for a consumed example, 0 for an absent slot
+ *   out_mlm_positions, out_mpp_positions  [E_max, n_k]  flat indices row * S_row + first + position; 0 for an absent slot
+ *   consumed        int32 [1]
+ *
+ * DEVICE memory throughout, nothing allocated, no host wait, two launches whatever the arguments and the data are (the
+ * call records into a graph), no atomics, no floating-point sum: bitwise reproducible.  The plan (prefix sums of the
+ * lengths, row ends) runs in ONE workgroup with the lengths in LDS, hence E and E_max <= MMT_PACK_MAX_EXAMPLES; the fill
+ * is one thread per output position.  `lengths` and the position tables are data: a length is clamped into [1, S], a
+ * position into [0, S), a flat index into [0, R * S_row) -- wrong values give wrong rows, never a stray access.
+ * MMT_E_INVALID before any launch: a NULL pointer other than the position tables (a table that is given needs n_k >= 1
+ * and its output); E, R or E_max below 1; S < 1 or S_row < S; E or E_max above the limit; E * S or R * S_row at or above
+ * 2^31.  MMT_E_WORKSPACE: less than mmt_pack_rows_workspace_bytes (4 * (R + 1 + 2 E) bytes rounded up to 16; 0 for a bad
+ * descriptor), caller-owned, no initialisation.  mmt_pack_rows_host runs the same functions (csrc/pack_rows.h) as loops
+ * over HOST memory (CPU tensors, the host tests, the sanitizer program). */
+#define MMT_PACK_MAX_EXAMPLES 4096
+typedef struct mmt_pack_desc {
+  int32_t E, S;          /* unpacked examples in, positions of each                */
+  int32_t R, S_row;      /* rows out, positions of each                            */
+  int32_t E_max;         /* example slots of the per-example outputs               */
+  int32_t n_mlm, n_mpp;  /* columns of the two position tables (ignored when NULL) */
+  int32_t reserved;
+} mmt_pack_desc;
+
+size_t mmt_pack_rows_workspace_bytes(const mmt_pack_desc* desc);
+int mmt_pack_rows(const mmt_pack_desc* desc, const int32_t* word_ids, const int32_t* segment_ids, const int32_t* lengths,
+                  const int32_t* mlm_positions, const int32_t* mpp_positions, int32_t* out_word_ids,
+                  int32_t* out_segment_ids, int32_t* example_ids, int32_t* example_starts, int32_t* patch_slots,
+                  int64_t* first_positions, float* example_weight, int32_t* out_mlm_positions, int32_t* out_mpp_positions,
+                  int32_t* consumed, void* workspace, size_t workspace_bytes, void* stream);
+int mmt_pack_rows_host(const mmt_pack_desc* desc, const int32_t* word_ids, const int32_t* segment_ids, const int32_t* lengths,
+                       const int32_t* mlm_positions, const int32_t* mpp_positions, int32_t* out_word_ids,
+                       int32_t* out_segment_ids, int32_t* example_ids, int32_t* example_starts, int32_t* patch_slots,
+                       int64_t* first_positions, float* example_weight, int32_t* out_mlm_positions, int32_t* out_mpp_positions,
+                       int32_t* consumed, void* workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,7 +54,8 @@ EXPORTS = ('mmt_abi_version', 'mmt_last_error', 'mmt_write_step_scalars', 'mmt_w
            'mmt_records_scan', 'mmt_example_fields', 'mmt_records_crc_workspace_bytes', 'mmt_records_crc', 'mmt_records_crc_host',
            'mmt_png_info', 'mmt_png_inflate', 'mmt_png_workspace_bytes', 'mmt_png_pixels', 'mmt_png_pixels_host',
            'mmt_png_gather', 'mmt_png_scanlines_workspace_bytes', 'mmt_png_scanlines', 'mmt_png_scanlines_host',
-           'mmt_lamb_workspace_bytes', 'mmt_lamb_step', 'mmt_lamb_step_host')
+           'mmt_lamb_workspace_bytes', 'mmt_lamb_step', 'mmt_lamb_step_host',
+           'mmt_pack_rows_workspace_bytes', 'mmt_pack_rows', 'mmt_pack_rows_host')
 
 
 class EmbedDesc(ctypes.Structure):
@@ -103,6 +104,14 @@ class LambDesc(ctypes.Structure):       # mmt_adamw_desc with the slab's paramet
               ('beta2', ctypes.c_float), ('eps', ctypes.c_float), ('bias_correction1', ctypes.c_float),
               ('bias_correction2', ctypes.c_float), ('zero_grad', ctypes.c_int32),
               ('n_segments', ctypes.c_int32), ('hyper', ctypes.c_void_p)]
+
+
+MMT_PACK_MAX_EXAMPLES = 4096             # examples (and example slots) of one mmt_pack_rows call: its plan lives in LDS
+
+
+class PackDesc(ctypes.Structure):
+  _fields_ = [('E', ctypes.c_int32), ('S', ctypes.c_int32), ('R', ctypes.c_int32), ('S_row', ctypes.c_int32),
+              ('E_max', ctypes.c_int32), ('n_mlm', ctypes.c_int32), ('n_mpp', ctypes.c_int32), ('reserved', ctypes.c_int32)]
 
 
 class ImageDesc(ctypes.Structure):
@@ -296,6 +305,12 @@ def lib() -> ctypes.CDLL:
   L.mmt_lamb_step.argtypes = [ctypes.POINTER(LambDesc)] + [vp] * 10 + [ctypes.c_size_t, vp]
   L.mmt_lamb_step_host.restype = ctypes.c_int
   L.mmt_lamb_step_host.argtypes = [ctypes.POINTER(LambDesc)] + [vp] * 10 + [ctypes.c_size_t]
+  L.mmt_pack_rows_workspace_bytes.restype = ctypes.c_size_t
+  L.mmt_pack_rows_workspace_bytes.argtypes = [ctypes.POINTER(PackDesc)]
+  L.mmt_pack_rows.restype = ctypes.c_int
+  L.mmt_pack_rows.argtypes = [ctypes.POINTER(PackDesc)] + [vp] * 16 + [ctypes.c_size_t, vp]
+  L.mmt_pack_rows_host.restype = ctypes.c_int
+  L.mmt_pack_rows_host.argtypes = [ctypes.POINTER(PackDesc)] + [vp] * 16 + [ctypes.c_size_t]
   L.mmt_grad_clip_scale.restype = ctypes.c_int
   L.mmt_grad_clip_scale.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64), ctypes.c_float,
                                     ctypes.c_float, vp, vp, vp, ctypes.c_size_t, vp]

@@ -89,4 +89,4 @@ class MmtClassificationDataLoader(RecordStages):
       if pool.n and not training:
         yield self._finish(pool.pop(pool.n))
 
-    return batches()
+    return self._maybe_packed(batches(), B)

@@ -143,6 +143,9 @@ class MmtDataConfig(Config):        # data/configs.py:20-55 (+ TFM DataConfig ba
   local_radius: int = 1 << 30
   num_global_tokens: int = 0
   image_grid_radius: int = 0        # App. A.5 `grid_radius`: 2-D neighbourhood of the image patches; 0 = off
+  # Packed batches ("Packed batches"): rows per batch, 0 = off (the reference's one example per row)
+  pack_rows: int = 0
+  pack_row_len: int = 0             # positions of a packed row; 0 = max_seq_len
 
 
 @dataclasses.dataclass

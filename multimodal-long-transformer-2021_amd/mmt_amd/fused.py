@@ -971,3 +971,50 @@ def softmax_cross_entropy(logits: torch.Tensor, labels: torch.Tensor) -> torch.T
   if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] > 65535:
     raise ValueError('softmax_cross_entropy expects [rows <= 65535, C] logits with unit column stride')
   return _SoftmaxXentFn.apply(logits, labels)
+
+
+def pack_rows(word_ids, segment_ids, lengths, rows: int, row_len: int, max_examples: int, mlm_positions=None,
+              mpp_positions=None):
+  """`mmt_pack_rows` (include/mmt_layer.h): E unpacked examples (`word_ids`, `segment_ids` int32 [E,S], `lengths` int32 [E],
+  optional position tables int32 [E,n]) into `rows` rows of `row_len` positions by the next-fit rule in arrival order,
+  at most `max_examples` of them.  Returns a dict of fresh tensors on the inputs' device: `word_ids`, `segment_ids`,
+  `example_ids`, `example_starts`, `patch_slots` int32 [rows,row_len]; `first_positions` int64 [max_examples,2];
+  `example_weight` float32 [max_examples]; `mlm_positions` / `mpp_positions` int32 [max_examples,n] as flat indices
+  into [rows * row_len] (when given); `consumed` int32 [1] -- on the device: reading it is the caller's wait.  GPU
+  tensors take the kernels on the current stream (no allocation inside the call, no host wait, two launches); CPU
+  tensors take `mmt_pack_rows_host`, the same functions as loops."""
+  if word_ids.dim() != 2 or segment_ids.shape != word_ids.shape or lengths.shape != word_ids.shape[:1]:
+    raise ValueError('pack_rows expects word_ids and segment_ids [E,S] and lengths [E]')
+  dev = word_ids.device
+  E, S = word_ids.shape
+  i32 = lambda t: t.to(device=dev, dtype=torch.int32).contiguous()
+  word_ids, segment_ids, lengths = i32(word_ids), i32(segment_ids), i32(lengths)
+  tables = []
+  for t in (mlm_positions, mpp_positions):
+    if t is not None and (t.dim() != 2 or t.shape[0] != E):
+      raise ValueError('pack_rows expects position tables [E,n]')
+    tables.append(None if t is None else i32(t))
+  d = _lib.PackDesc()
+  d.E, d.S, d.R, d.S_row, d.E_max = E, S, int(rows), int(row_len), int(max_examples)
+  d.n_mlm = 0 if tables[0] is None else tables[0].shape[1]
+  d.n_mpp = 0 if tables[1] is None else tables[1].shape[1]
+  R, L, M = max(d.R, 0), max(d.S_row, 0), max(d.E_max, 0)        # (a bad size is the library's to refuse, with its message)
+  new = lambda shape, dtype=torch.int32: torch.empty(shape, dtype=dtype, device=dev)
+  out = {k: new((R, L)) for k in ('word_ids', 'segment_ids', 'example_ids', 'example_starts', 'patch_slots')}
+  out['first_positions'] = new((M, 2), torch.int64)
+  out['example_weight'] = new((M,), torch.float32)
+  outs = [None if t is None else new((M, t.shape[1])) for t in tables]
+  out['consumed'] = new((1,))
+  ws = new((max(_lib.lib().mmt_pack_rows_workspace_bytes(d) // 4, 4),))     # (0 for a size the call refuses)
+  args = (d, _p(word_ids), _p(segment_ids), _p(lengths), _p(tables[0]), _p(tables[1]), _p(out['word_ids']), _p(out['segment_ids']),
+          _p(out['example_ids']), _p(out['example_starts']), _p(out['patch_slots']), _p(out['first_positions']),
+          _p(out['example_weight']), _p(outs[0]), _p(outs[1]), _p(out['consumed']), _p(ws), ws.numel() * 4)
+  if dev.type == 'cuda':
+    with torch.cuda.device(dev):
+      _lib.check(_lib.lib().mmt_pack_rows(*args, _stream(word_ids)))
+  else:
+    _lib.check(_lib.lib().mmt_pack_rows_host(*args))
+  for name, t in zip(('mlm_positions', 'mpp_positions'), outs):
+    if t is not None:
+      out[name] = t
+  return out

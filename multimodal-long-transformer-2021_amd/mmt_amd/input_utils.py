@@ -114,6 +114,73 @@ def packed_example_layout(lengths, has_image, S: int, device=None):
   return ids, starts, slots, first
 
 
+def pack_examples_per_row(data_cfg, row_len: int) -> int:
+  """Examples a row of `row_len` positions can hold at the most: every example has [CLS][PATCH], P*P patches, the field
+  token and [SEP] at the least."""
+  P = data_cfg.image_size // data_cfg.patch_size
+  return max(1, int(row_len) // (2 + P * P + 2))
+
+
+def pack_max_examples(data_cfg, batch_size: int, row_len: int) -> int:
+  """The example slots of a packed batch (`MmtDataConfig.pack_rows`): the per-replica batch size times the examples a
+  row can hold, capped at the kernel's limit (`MMT_PACK_MAX_EXAMPLES`)."""
+  return min(int(batch_size) * pack_examples_per_row(data_cfg, row_len), _lib.MMT_PACK_MAX_EXAMPLES)
+
+
+def pack_batch(inputs, labels, rows: int, row_len: int, max_examples: int):
+  """Packs a prefix of an unpacked structured batch (`word_ids`, `segment_ids` [E,S], `valid_len` [E], optional
+  `mlm_positions` / `mpp_positions`, per-example tensors such as `patch_embeddings`, and per-example `labels`) into `rows`
+  rows of `row_len` positions: next-fit in arrival order, at most `max_examples` examples (`fused.pack_rows`,
+  include/mmt_layer.h).  Returns (packed_inputs, packed_labels, consumed).
+
+  Per-example tensors are not moved: packed example e is pool example e, so `patch_embeddings` and every label are the
+  pool's first `max_examples` entries (zero entries behind a shorter pool).  Every `*_weights` label is multiplied by
+  `example_weight` (0 for the slots at or behind `consumed`), so absent slots count in no loss and no metric, and every
+  per-example input whose name ends in `_index` (`image_index`, `text_index`, `gt_image_index` of the retrieval loader)
+  is -1 there, whatever the pool holds behind the prefix: `predict.predict` drops those slots.
+  `packed_inputs` carries `example_ids`, `example_starts`, `patch_slots`, `first_positions`, the positions as flat
+  indices into [rows * row_len] (the models' `flat_positions=True`) and the batch's `attention_pattern`; with
+  `num_global_tokens > 0` the attention calls set MMT_FLAG_EXAMPLE_GLOBALS themselves (ops.py).  `consumed` is an int32
+  [1] tensor on the batch's device: nothing here waits for it -- the loader reads it, the step never does."""
+  from . import fused
+  for k in ('word_ids', 'segment_ids', 'valid_len'):
+    if inputs.get(k) is None:
+      raise ValueError(f'pack_batch needs the structured batch\'s {k!r}')
+  if 'att_mask' in inputs or 'relative_att_ids' in inputs:
+    raise ValueError('pack_batch takes the structured batch (attention_pattern + valid_len), not dense side inputs')
+  E, M = inputs['word_ids'].shape[0], int(max_examples)
+  packed = fused.pack_rows(inputs['word_ids'], inputs['segment_ids'], inputs['valid_len'], rows, row_len, M,
+                           mlm_positions=inputs.get('mlm_positions'), mpp_positions=inputs.get('mpp_positions'))
+  weight = packed.pop('example_weight')
+  consumed = packed.pop('consumed')
+
+  def head(t):                                                   # the pool's first M entries, zeros behind a shorter pool
+    if E >= M:
+      return t[:M]
+    return torch.cat([t, t.new_zeros((M - E,) + tuple(t.shape[1:]))])
+
+  out_inputs = {}
+  for k, v in inputs.items():
+    if k == 'valid_len':
+      continue
+    if k in packed:
+      out_inputs[k] = packed.pop(k)
+    elif not torch.is_tensor(v):
+      out_inputs[k] = v
+    elif k.endswith('_index'):                                   # ids of the example (the retrieval loader's): -1 names an absent slot
+      out_inputs[k] = torch.where(weight.reshape((M,) + (1,) * (v.dim() - 1)) > 0, head(v), torch.full_like(head(v), -1))
+    else:
+      out_inputs[k] = head(v)
+  out_inputs.update(packed)                                      # example_ids, example_starts, patch_slots, first_positions
+  out_labels = {}
+  for k, v in labels.items():
+    v = head(v)
+    if k.endswith('_weights'):
+      v = v * weight.to(v.dtype).reshape((M,) + (1,) * (v.dim() - 1))
+    out_labels[k] = v
+  return out_inputs, out_labels, consumed
+
+
 def synthetic_retrieval_sets(data_cfg, n_images: int, n_texts: int, device, generator: Optional[torch.Generator] = None,
                              vocab_size: int = 30522):
   """A synthetic image set and text set (`retrieval.RetrievalSets`) with the layout and id ranges of `synthetic_batch`:
@@ -149,9 +216,23 @@ def synthetic_retrieval_sets(data_cfg, n_images: int, n_texts: int, device, gene
 
 def synthetic_batch(data_cfg, batch_size: int, device, generator: Optional[torch.Generator] = None,
                     vocab_size: int = 30522, dense_side_inputs: bool = False,
-                    ragged: bool = False, task: str = 'pretrain'):
+                    ragged: bool = False, task: str = 'pretrain', pack_rows: int = 0, pack_row_len: int = 0,
+                    text_lengths=None):
   """One (inputs, labels) pair with the shapes/dtypes of the reference's feature contract.
-  Layout `[CLS][PATCH] patch_1..patch_{P^2} [ATT] text ... [SEP] pad` (data_utils.py:224-231)."""
+  Layout `[CLS][PATCH] patch_1..patch_{P^2} [ATT] text ... [SEP] pad` (data_utils.py:224-231).
+
+  `pack_rows > 0` (structured inputs only): `batch_size * (row_len // (2 + P^2 + 2))` examples are drawn (capped at the
+  kernel limit) and as many of them as fit go into `pack_rows` rows of `pack_row_len` positions (0 = max_seq_len) through
+  `pack_batch`; the slots of the others carry weight 0 -- the stand-in draws afresh every batch and keeps no pool.
+  `text_lengths`: int32 [B] text wordpiece counts to use instead of the drawn ones (clamped into [2, S - 2 - P^2])."""
+  if pack_rows:
+    if dense_side_inputs:
+      raise ValueError('packed batches take the structured side inputs (dense_side_inputs=False)')
+    row_len = int(pack_row_len) or data_cfg.max_seq_len
+    n = pack_max_examples(data_cfg, batch_size, row_len)
+    inputs, labels = synthetic_batch(data_cfg, n, device, generator, vocab_size, False, ragged, task, text_lengths=text_lengths)
+    inputs, labels, _ = pack_batch(inputs, labels, int(pack_rows), row_len, n)
+    return inputs, labels
   S = data_cfg.max_seq_len
   P = data_cfg.image_size // data_cfg.patch_size
   n_patch = P * P
@@ -166,7 +247,9 @@ def synthetic_batch(data_cfg, batch_size: int, device, generator: Optional[torch
   word_ids[:, 2:n_img] = PATCH_START_UNUSED_INDEX + torch.arange(n_patch, device=device, dtype=torch.int32)
   word_ids[:, n_img] = ATT_ID
   max_text = S - n_img
-  if ragged:
+  if text_lengths is not None:
+    n_text = torch.as_tensor(text_lengths).to(device=device, dtype=torch.int32).clamp(2, max_text)
+  elif ragged:
     lo = max(2, int(0.75 * S) - n_img)
     n_text = ri(lo, max_text + 1, (B,))
   else:

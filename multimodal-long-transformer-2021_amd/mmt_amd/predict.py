@@ -43,6 +43,9 @@ def predict(task, batches: Iterable, model, logits_key: str = 'itm_logits') -> L
       out = torch.softmax(logits, dim=1)[:, 1]
     else:
       out = torch.argmax(logits, dim=1)
+    if inputs.get('example_starts') is not None:      # a packed batch (`input_utils.pack_batch`): absent slots carry index -1
+      here = (image_index >= 0) & (text_index >= 0)
+      image_index, text_index, gt_image_index, out = image_index[here], text_index[here], gt_image_index[here], out[here]
     for a, b, c, d in zip(image_index.tolist(), text_index.tolist(), gt_image_index.tolist(), out.tolist()):
       results.append(RawResult(a, b, c, d))
   model.train(was_training)

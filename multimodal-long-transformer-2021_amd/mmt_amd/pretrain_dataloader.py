@@ -143,4 +143,4 @@ class MmtPretrainDataLoader(RecordStages):
       if pool.n and not training:
         yield self._finish(pool.pop(pool.n), with_itm)
 
-    return batches()
+    return self._maybe_packed(batches(), B)

@@ -10,6 +10,7 @@ import glob
 import json
 import os
 import random
+import time
 from typing import Dict, Iterator, List, Optional, Tuple
 
 import torch
@@ -110,6 +111,12 @@ class RecordStages:
       raise ValueError('text_special_token_field_dict must name at least one field')
     self._vocab = None
     self._key_ids: Dict[bytes, int] = {}
+    if int(getattr(params, 'pack_rows', 0) or 0) < 0 or int(getattr(params, 'pack_row_len', 0) or 0) < 0:
+      raise ValueError('pack_rows and pack_row_len must not be negative')
+    if int(getattr(params, 'pack_rows', 0) or 0) and self.dense_side_inputs:
+      raise ValueError('pack_rows takes the structured side inputs: dense_side_inputs must be off')
+    # the packing stage's own cost: batches packed, and the seconds spent waiting for their `consumed` words
+    self.pack_batches, self.pack_wait_seconds = 0, 0.0
 
   # ---- stage 1: files ------------------------------------------------------------------------------------------------
   def files(self, input_path: Optional[str] = None) -> List[str]:
@@ -271,8 +278,57 @@ class RecordStages:
       if si['relative_att_ids'] is None:
         inputs.pop('relative_att_ids')
     else:
-      si = side_inputs(pattern, n_image, n_text, S, want_mask=False, want_ids=False)
-      inputs['segment_ids'] = si['segment_ids']
+      if dev.type == 'cuda':
+        inputs['segment_ids'] = side_inputs(pattern, n_image, n_text, S, want_mask=False, want_ids=False)['segment_ids']
+      else:     # `make_segment_ids` (data_utils.py:350-361) in torch, for the host stages: 1 image part, 2 text part, 0 boundary / pad
+        pos = torch.arange(S, device=dev)[None]
+        inputs['segment_ids'] = ((pos < W).to(torch.int32) + 2 * ((pos > W) & (pos < W + n_text[:, None])).to(torch.int32))
       inputs['attention_pattern'] = pattern
       inputs['valid_len'] = (n_image + n_text).to(torch.int32)
     return inputs
+
+  # ---- the last stage when `pack_rows` is set: short examples into long rows -------------------------------------------------
+  def _maybe_packed(self, batches, B: int):
+    return self._packed(batches, B) if int(getattr(self.params, 'pack_rows', 0) or 0) else batches
+
+  def _packed(self, batches, B: int):
+    """Packs the stream of unpacked (inputs, labels) batches into batches of `pack_rows` rows of `pack_row_len` positions
+    (`input_utils.pack_batch`).  The examples in hand form a pool on the device, in arrival order.  `max_examples` is the
+    per-replica batch size times the examples a row can hold, capped at the kernel's limit.  As soon as the pool holds as
+    many examples as a batch could take at the most (max_examples, or rows times the examples a row can hold) a batch
+    packs a prefix of the pool, the one `consumed` word is read back -- the stage's only host wait -- and the
+    rest stays at the front for the next batch: nothing is dropped, repeated or reordered.  When a finite pass ends
+    (is_training off) the remainder goes out in as many last batches as it takes."""
+    cfg = self.params
+    rows = int(cfg.pack_rows)
+    row_len = int(getattr(cfg, 'pack_row_len', 0) or 0) or int(cfg.max_seq_len)
+    if row_len < int(cfg.max_seq_len):
+      raise ValueError(f'pack_row_len {row_len} is shorter than max_seq_len {cfg.max_seq_len}')
+    M = input_utils.pack_max_examples(cfg, B, row_len)
+    need = min(M, rows * input_utils.pack_examples_per_row(cfg, row_len))     # more examples in hand cannot change the batch
+    pool_in, pool_lab = _Pool(), _Pool()
+    constants = {}
+
+    def pack_one():
+      n = min(pool_in.n, M)
+      all_in, all_lab = _cat(pool_in.chunks), _cat(pool_lab.chunks)
+      head_in = {k: v[:n] for k, v in all_in.items()}
+      head_in.update(constants)
+      packed_in, packed_lab, consumed = input_utils.pack_batch(head_in, {k: v[:n] for k, v in all_lab.items()}, rows, row_len, M)
+      t0 = time.perf_counter()
+      taken = int(consumed)                                      # the read-back: waits for the pack (and all before it)
+      self.pack_wait_seconds += time.perf_counter() - t0
+      self.pack_batches += 1
+      for pool, everything in ((pool_in, all_in), (pool_lab, all_lab)):
+        pool.n -= taken
+        pool.chunks = [{k: v[taken:] for k, v in everything.items()}] if pool.n else []
+      return packed_in, packed_lab
+
+    for inputs, labels in batches:
+      constants = {k: v for k, v in inputs.items() if not torch.is_tensor(v)}
+      pool_in.push({k: v for k, v in inputs.items() if torch.is_tensor(v)})
+      pool_lab.push(labels)
+      while pool_in.n >= need:
+        yield pack_one()
+    while pool_in.n and not cfg.is_training:                     # a training stream that ends drops its remainder, as the unpacked loaders do
+      yield pack_one()

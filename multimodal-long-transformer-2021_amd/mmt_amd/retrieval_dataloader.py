@@ -227,4 +227,4 @@ class MmtRetrievalDataLoader(RecordStages):
         else:
           yield sets.materialize(ie_all[first:first + count], te_all[first:first + count])
 
-    return batches()
+    return self._maybe_packed(batches(), B)

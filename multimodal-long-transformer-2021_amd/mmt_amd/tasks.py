@@ -76,7 +76,9 @@ class _TaskBase:
     `itm_pos_weights` -- the task's `label_field`, `label_weights_field` and `pos_weights_field` must name them
     (ValueError here, not a KeyError in the first step).  Everything else -- the empty path, the `gs://` placeholder of
     the committed YAMLs -- draws the endless synthetic stand-in.  `self.input_source` says which ('records' |
-    'synthetic'); `loader_args` are keyword arguments of the loader (its shuffle buffer sizes)."""
+    'synthetic'); `loader_args` are keyword arguments of the loader (its shuffle buffer sizes).  With
+    `params.pack_rows > 0` either source serves packed batches (`input_utils.pack_batch`; DESIGN.md section 4, "Packed
+    batches"), which `train_step` and `validation_step` recognise by `example_starts`."""
     per_replica = batch_size or max(1, params.global_batch_size // self.num_replicas)
     self.input_source = 'synthetic'
     if isinstance(self, PretrainingTask):
@@ -108,7 +110,9 @@ class _TaskBase:
     def it():
       while True:
         yield input_utils.synthetic_batch(params, per_replica, device, gen, vocab_size=vocab,
-                                          dense_side_inputs=dense_side_inputs, ragged=ragged, task=task)
+                                          dense_side_inputs=dense_side_inputs, ragged=ragged, task=task,
+                                          pack_rows=int(getattr(params, 'pack_rows', 0) or 0),
+                                          pack_row_len=int(getattr(params, 'pack_row_len', 0) or 0))
     return it()
 
   # ---- the reference's gradient-accumulation train step (pretraining.py:224-298) ----------
@@ -116,8 +120,15 @@ class _TaskBase:
                  micro_batch_size: Optional[int] = None, clip_norm: Optional[float] = None,
                  step: Optional[int] = None):
     """`step` = global train step (from the trainer loop / checkpoint): with the micro-step index and
-    the data-parallel rank it determines every dropout mask of this call (`fused.set_seed_stream`)."""
+    the data-parallel rank it determines every dropout mask of this call (`fused.set_seed_stream`).
+
+    A packed batch (`input_utils.pack_batch`; recognised by `example_starts` in the inputs) runs as ONE micro step
+    whatever `micro_batch_size` says: its inputs are per row and its labels per example, so no slice of the leading
+    dimension is a batch.  Its shapes are static (rows, row length, example slots), so `GraphedTrainStep` records it."""
     inputs, labels = inputs
+    packed = inputs.get('example_starts') is not None
+    if packed:
+      inputs = dict(inputs, flat_positions=True)
     if step is None:
       step = self._auto_step = getattr(self, '_auto_step', 0) + 1
     rank = torch.distributed.get_rank() if (torch.distributed.is_available() and
@@ -125,7 +136,7 @@ class _TaskBase:
     try:
       micro = micro_batch_size or getattr(self.task_config, 'micro_batch_size', None)
       batch_size = inputs['word_ids'].shape[0]
-      micro = micro or batch_size
+      micro = batch_size if packed else (micro or batch_size)
       num_small_steps = batch_size // micro
       if num_small_steps == 0:
         warnings.warn('per-replica batch smaller than the micro batch: zero micro-steps run '
@@ -142,8 +153,11 @@ class _TaskBase:
           reducer.set_armed(i == num_small_steps - 1)
         fused.set_seed_stream(step, i, rank)
         sl = slice(i * micro, (i + 1) * micro)
-        small_inputs = {k: (v[sl] if is_t(v) else v) for k, v in inputs.items()}
-        small_labels = {k: v[sl] for k, v in labels.items()}
+        if packed:                            # rows and example slots have different leading dimensions: no slice
+          small_inputs, small_labels = inputs, labels
+        else:
+          small_inputs = {k: (v[sl] if is_t(v) else v) for k, v in inputs.items()}
+          small_labels = {k: v[sl] for k, v in labels.items()}
         outputs = model(**small_inputs, training=True)
         loss = self.build_losses(small_labels, outputs, metrics)
         if metrics:                        # pretraining.py:297 / classification.py:211 (after the gradient in the reference;
@@ -186,6 +200,8 @@ class _TaskBase:
   def validation_step(self, inputs, model, metrics=None):
     """`pretraining.py:300-313` / `classification.py:214-227`: forward, losses, metrics."""
     inputs, labels = inputs
+    if inputs.get('example_starts') is not None:      # a packed batch: flat positions, logits per example slot
+      inputs = dict(inputs, flat_positions=True)
     outputs = model(**inputs, training=False)
     loss = self.build_losses(labels, outputs, metrics)
     if metrics:

@@ -243,8 +243,11 @@ class TrainerConfig(Config):
   max_to_keep: int = 5
   validation_interval: int = 1000
   validation_steps: int = -1
-  # TFM `TrainerConfig` keys the fine-tune YAMLs set (itm_2d_from_vit.yaml:84-86): accepted and carried; exporting a
-  # best checkpoint needs the validation loop's metric of that name
+  # validation_interval / validation_steps drive the validation loop of train.py (evaluation.evaluation_due;
+  # validation_steps < 0 = until the validation data end).  The next three are the TFM `TrainerConfig` keys the fine-tune
+  # YAMLs set (itm_2d_from_vit.yaml:84-86): with a subdir, evaluation.BestCheckpointExporter keeps the checkpoint with
+  # the best value of that metric in model_dir/<subdir>; the metric is a key of the evaluation's result, with or
+  # without its validation_ prefix ('auc' = 'validation_auc'), checked before the first train step
   best_checkpoint_export_subdir: str = ''
   best_checkpoint_eval_metric: str = ''
   best_checkpoint_metric_comp: str = 'higher'

@@ -43,6 +43,15 @@ class Metric:
       self.state = torch.zeros(self.n_state, dtype=torch.float32, device=device)
     return self.state
 
+  def ensure(self, device) -> 'Metric':
+    """Makes the sums exist on `device` (zeros when nothing was ever added).  A replica that ran no batch calls this
+    before it reads: `synced_state` then takes part in the all-reduce the other replicas are waiting in, on their
+    backend's device."""
+    dev = torch.device(device)
+    if self.state is None or self.state.device.type != dev.type or dev.index not in (None, self.state.device.index):
+      self._ensure(dev)
+    return self
+
   def reset_state(self):
     if self.state is not None:
       self.state.zero_()

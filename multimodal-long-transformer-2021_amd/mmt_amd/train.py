@@ -5,6 +5,10 @@ Launch one process per GPU (torchrun / torch.distributed.run).  The pretraining 
 `task.train_data.input_path` is a local file pattern and `task.train_data.vocab_filename` names a vocabulary file
 (`pretrain_dataloader.MmtPretrainDataLoader`); otherwise -- the `gs://` placeholder of the committed YAMLs, an empty
 path, the classification task -- data are synthetic (`input_utils.synthetic_batch`).  One log line says which.
+
+Modes: `train` trains; `train_and_eval` / `continuous_train_and_eval` also evaluate `task.validation_data` on the schedule
+of `trainer.validation_interval` / `validation_steps` and keep the best checkpoint when `trainer.best_checkpoint_*` say
+so; `eval` restores the latest checkpoint of `model_dir` and evaluates once (`mmt_amd/evaluation.py`).
 """
 from __future__ import annotations
 
@@ -15,7 +19,7 @@ import time
 
 import torch
 
-from . import checkpoint, configs, distribute, graphed, optimization, tasks
+from . import checkpoint, configs, distribute, evaluation, graphed, optimization, tasks
 
 
 def run_experiment(params: configs.ExperimentConfig, mode: str, model_dir: str, device=None,
@@ -58,6 +62,27 @@ def run_experiment(params: configs.ExperimentConfig, mode: str, model_dir: str, 
       checkpoint.save(model_dir, step, model, optimizer, max_to_keep=params.trainer.max_to_keep)
 
   from . import metrics as metrics_lib
+  # the validation loop (evaluation.py): `train` mode runs none; `train_and_eval` / `continuous_train_and_eval` evaluate
+  # task.validation_data after every train step that `evaluation_due` names; `eval` evaluates once and trains nothing
+  evaluates = 'eval' in mode
+  eval_step = exporter = None
+  if evaluates:
+    best_key = evaluation.check_startup(task, params.trainer, params.task.validation_data)     # before the first train step
+    if best_key and model_dir:
+      exporter = evaluation.BestCheckpointExporter(
+          os.path.join(model_dir, params.trainer.best_checkpoint_export_subdir), best_key,
+          params.trainer.best_checkpoint_metric_comp, rank=strategy.rank)
+    eval_step = evaluation.make_eval_step(task, model, device)
+
+  def run_evaluation(step, **note):
+    eval_logs = evaluation.evaluate(task, model, params.task.validation_data, device=device, rank=strategy.rank,
+                                    steps=params.trainer.validation_steps, step_fn=eval_step)
+    logs.append({'step': step, **eval_logs, **note})
+    if strategy.rank == 0:
+      print(json.dumps(logs[-1]), flush=True)
+    if exporter is not None and 'train' in mode:
+      exporter.maybe_export(step, eval_logs, model, optimizer)
+
   if 'train' in mode:
     t0 = time.perf_counter()
     # `task.build_metrics()` objects, updated on the device inside every step (process_metrics, pretraining.py:297);
@@ -89,19 +114,19 @@ def run_experiment(params: configs.ExperimentConfig, mode: str, model_dir: str, 
             print(json.dumps(logs[-1]), flush=True)
         if ckpt_every and (step + 1) % ckpt_every == 0 and step + 1 < steps:
           save(step + 1)
-      if steps > start:
-        save(steps)
+        if step + 1 == steps:
+          save(steps)                  # before the last evaluation: what `eval` mode restores is what was evaluated
+        if evaluates and evaluation.evaluation_due(step + 1, params.trainer.validation_interval, steps):
+          run_evaluation(step + 1)
     finally:
       if graphed_step is not None:       # also when the loop raised: the device-resident step scalars must not outlive it
         graphed_step.close()
-  if 'eval' in mode:
-    vdata = task.build_inputs(params.task.validation_data, device=device, rank=strategy.rank)
-    eval_metrics = task.build_metrics(training=False)
-    out = task.validation_step(next(vdata), model, metrics=eval_metrics)
-    logs.append({'validation_loss': float(out[task.loss]),
-                 **{f'validation_{k}': round(v, 6) for k, v in metrics_lib.results(eval_metrics).items()}})
-    if strategy.rank == 0:
-      print(json.dumps(logs[-1]), flush=True)
+    if evaluates and start >= steps:     # a resumed run with nothing left to train still reports where it stands
+      run_evaluation(start)
+  elif evaluates:                        # `eval`: the restored weights (the JSON line says from where; null = none found)
+    run_evaluation(start, restored_from=resume_from)
+  if eval_step is not None:
+    eval_step.close()
   return model, logs
 
 

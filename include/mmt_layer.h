@@ -186,6 +186,31 @@ int mmt_lamb_step_host(const mmt_lamb_desc* desc, float* param, float* grad, flo
                        void* param_bf16, const float* chunk_wd, const int32_t* segment_start, const int32_t* segment_adapt,
                        const float* grad_scale, void* workspace, size_t workspace_bytes);
 
+/* Exponential moving average of the weights over a flat parameter slab (TFM `optimizer_config.ema`, restated from memory
+ * of official/modeling/optimization/ema_optimizer.py: no TensorFlow was at hand to pin it).  Per element, in fp32, with
+ * omd = 1 - decay of the step:
+ *   avg = fmaf(omd, param - avg, avg)                (the subtraction rounded first, then ONE fused multiply-add)
+ * and exactly param for omd == 1, exactly avg for omd == 0.  `one_minus_decay_dev` is a DEVICE float read by the kernel
+ * INSTEAD of the field, or NULL: the convention of mmt_adamw_desc.hyper, for a step replayed from a HIP graph.  One
+ * launch, 12 bytes per element; nothing is allocated and the host does not wait.
+ * mmt_ema_swap exchanges param and avg in place and writes param_bf16[i] = bf16(new param[i]) (round to nearest even,
+ * what torch's copy_ gives; param_bf16 may be NULL): two calls restore all three buffers bit for bit.
+ * n must be a positive multiple of 1024, the fp32 slabs 16-byte and the bf16 shadow 8-byte aligned, avg != param, and
+ * one_minus_decay in [0, 1] when no device word is given: MMT_E_INVALID otherwise.  Padding elements are zero in param,
+ * hence in avg, and stay zero.  The _host functions run the same per-element functions (csrc/ema.h) as plain loops on
+ * HOST arrays (there the decay word, if given, is a host float). */
+typedef struct mmt_ema_desc {
+  int64_t n;
+  float one_minus_decay;
+  int32_t reserved;
+  const float* one_minus_decay_dev;
+} mmt_ema_desc;
+
+int mmt_ema_step(const mmt_ema_desc* desc, const float* param, float* avg, void* stream);
+int mmt_ema_step_host(const mmt_ema_desc* desc, const float* param, float* avg);
+int mmt_ema_swap(int64_t n, float* param, float* avg, void* param_bf16, void* stream);
+int mmt_ema_swap_host(int64_t n, float* param, float* avg, void* param_bf16);
+
 /* Weight gradient of a Dense layer, accumulated into the fp32 master gradient:
  *   dw[M,N] += dy[K,M]^T . x[K,N]        (bf16 operands, fp32 accumulation, float atomics)
  * = the per-layer `tape.gradient` product + `AccumulateGrad` of src/tasks/pretraining.py:262-296.

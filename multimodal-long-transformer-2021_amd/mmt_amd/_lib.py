@@ -55,7 +55,8 @@ EXPORTS = ('mmt_abi_version', 'mmt_last_error', 'mmt_write_step_scalars', 'mmt_w
            'mmt_png_info', 'mmt_png_inflate', 'mmt_png_workspace_bytes', 'mmt_png_pixels', 'mmt_png_pixels_host',
            'mmt_png_gather', 'mmt_png_scanlines_workspace_bytes', 'mmt_png_scanlines', 'mmt_png_scanlines_host',
            'mmt_lamb_workspace_bytes', 'mmt_lamb_step', 'mmt_lamb_step_host',
-           'mmt_pack_rows_workspace_bytes', 'mmt_pack_rows', 'mmt_pack_rows_host')
+           'mmt_pack_rows_workspace_bytes', 'mmt_pack_rows', 'mmt_pack_rows_host',
+           'mmt_ema_step', 'mmt_ema_step_host', 'mmt_ema_swap', 'mmt_ema_swap_host')
 
 
 class EmbedDesc(ctypes.Structure):
@@ -104,6 +105,11 @@ class LambDesc(ctypes.Structure):       # mmt_adamw_desc with the slab's paramet
               ('beta2', ctypes.c_float), ('eps', ctypes.c_float), ('bias_correction1', ctypes.c_float),
               ('bias_correction2', ctypes.c_float), ('zero_grad', ctypes.c_int32),
               ('n_segments', ctypes.c_int32), ('hyper', ctypes.c_void_p)]
+
+
+class EmaDesc(ctypes.Structure):
+  _fields_ = [('n', ctypes.c_int64), ('one_minus_decay', ctypes.c_float), ('reserved', ctypes.c_int32),
+              ('one_minus_decay_dev', ctypes.c_void_p)]
 
 
 MMT_PACK_MAX_EXAMPLES = 4096             # examples (and example slots) of one mmt_pack_rows call: its plan lives in LDS
@@ -311,6 +317,14 @@ def lib() -> ctypes.CDLL:
   L.mmt_pack_rows.argtypes = [ctypes.POINTER(PackDesc)] + [vp] * 16 + [ctypes.c_size_t, vp]
   L.mmt_pack_rows_host.restype = ctypes.c_int
   L.mmt_pack_rows_host.argtypes = [ctypes.POINTER(PackDesc)] + [vp] * 16 + [ctypes.c_size_t]
+  L.mmt_ema_step.restype = ctypes.c_int
+  L.mmt_ema_step.argtypes = [ctypes.POINTER(EmaDesc), vp, vp, vp]
+  L.mmt_ema_step_host.restype = ctypes.c_int
+  L.mmt_ema_step_host.argtypes = [ctypes.POINTER(EmaDesc), vp, vp]
+  L.mmt_ema_swap.restype = ctypes.c_int
+  L.mmt_ema_swap.argtypes = [ctypes.c_int64, vp, vp, vp, vp]
+  L.mmt_ema_swap_host.restype = ctypes.c_int
+  L.mmt_ema_swap_host.argtypes = [ctypes.c_int64, vp, vp, vp]
   L.mmt_grad_clip_scale.restype = ctypes.c_int
   L.mmt_grad_clip_scale.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64), ctypes.c_float,
                                     ctypes.c_float, vp, vp, vp, ctypes.c_size_t, vp]

@@ -47,6 +47,8 @@ def make_train_step_bench(cfg: dict, device, rank: int, world: int, dtype=torch.
       }})
   if cfg.get('D', 64) != 64:    # another head size: hidden size H over N heads (the BASELINE configurations keep the defaults)
     exp.override({'task': {'model': {'encoder': {'mmt': {'hidden_size': cfg['H'], 'num_attention_heads': cfg['N']}}}}})
+  if cfg.get('ema') is not None:      # an `optimizer_config.ema` block (tools/ema_step_timing.py; no BASELINE configuration has one)
+    exp.override({'trainer': {'optimizer_config': {'ema': dict(cfg['ema'])}}})
   strategy = distribute.DataParallelStrategy(torch.distributed.get_backend() if _exchanging(world) else None)
   task = tasks.PretrainingTask(exp.task, compute_dtype=dtype, num_replicas=world)
   torch.manual_seed(0)

@@ -45,7 +45,21 @@ class Config:
     return self
 
   def as_dict(self):
-    return dataclasses.asdict(self)
+    out = dataclasses.asdict(self)
+    _add_extra_items(self, out)
+    return out
+
+  def extra_items(self) -> Dict[str, Any]:
+    """Attributes outside the dataclass's field list that `as_dict` reports too (OptimizerConfig's `ema_*`)."""
+    return {}
+
+
+def _add_extra_items(cfg, out) -> None:
+  out.update(cfg.extra_items())
+  for f in dataclasses.fields(cfg):
+    child = getattr(cfg, f.name)
+    if isinstance(child, Config):
+      _add_extra_items(child, out[f.name])
 
 
 @dataclasses.dataclass
@@ -187,6 +201,7 @@ class PretrainingTaskConfig(Config):         # pretraining.py:42-48
   validation_data: MmtDataConfig = dataclasses.field(
       default_factory=lambda: MmtPretrainDataConfig(is_training=False))
   init_checkpoint: str = ''
+  init_checkpoint_averages: bool = False   # warm start from the file's weight averages (`ema_items`) instead of its weights
   micro_batch_size: int = 64     # BATCH_SIZE_PER_REPLICA, pretraining.py:39 (App. B q7)
   # Build-defined: how data-parallel replicas' gradients combine when scale_loss is False -- 'mean' (default) or
   # 'sum' = what the reference's optimizer literally applies (pretraining.py:273).  With scale_loss
@@ -202,6 +217,7 @@ class ClassificationConfig(Config):          # classification.py:40-52
   validation_data: MmtDataConfig = dataclasses.field(
       default_factory=lambda: MmtDataConfig(is_training=False))
   init_checkpoint: str = ''
+  init_checkpoint_averages: bool = False   # warm start from the file's weight averages (`ema_items`) instead of its weights
   init_cls_pooler: bool = False
   metric_type: str = 'accuracy'
   gradient_reduction: str = 'mean'   # as PretrainingTaskConfig.gradient_reduction (classification.py:200-210)
@@ -227,6 +243,30 @@ class OptimizerConfig(Config):   # the adamw / polynomial / warmup block of `_TR
   # exclude_from_weight_decay)
   optimizer_type: str = 'adamw'
   exclude_from_layer_adaptation: Optional[List[str]] = None
+  # TFM's `optimizer_config.ema` block, flattened (`TrainerConfig.override`): `ema_enabled` says that the block was there;
+  # the others are its keys with TFM's defaults (recalled, not pinned).  `optimization.ema_decay_at` has the rule.
+  # `ema_trainable_weights_only`: parameters without requires_grad are in no slab and are never averaged, and the model
+  # has no other non-trainable weights, so both values behave the same.
+  # They are init-only variables that become plain attributes: settable through the constructor, `override` and
+  # --params_override like any field, but not in the dataclass's field list, so that `dataclasses.asdict` of a config
+  # is key for key what it was before the block was served.  `Config.as_dict` (params.yaml) adds them when the block is on.
+  ema_enabled: dataclasses.InitVar[bool] = False
+  ema_average_decay: dataclasses.InitVar[float] = 0.99
+  ema_start_step: dataclasses.InitVar[int] = 0
+  ema_dynamic_decay: dataclasses.InitVar[bool] = True
+  ema_trainable_weights_only: dataclasses.InitVar[bool] = True
+
+  def __post_init__(self, ema_enabled, ema_average_decay, ema_start_step, ema_dynamic_decay, ema_trainable_weights_only):
+    self.ema_enabled, self.ema_average_decay, self.ema_start_step = ema_enabled, ema_average_decay, ema_start_step
+    self.ema_dynamic_decay, self.ema_trainable_weights_only = ema_dynamic_decay, ema_trainable_weights_only
+
+  def extra_items(self):
+    if not self.ema_enabled:
+      return {}
+    return {'ema_enabled': True, **{'ema_' + k: getattr(self, 'ema_' + k) for k in _EMA_KEYS}}
+
+
+_EMA_KEYS = ('average_decay', 'start_step', 'dynamic_decay', 'trainable_weights_only')
 
 
 # TFM `LAMBConfig` defaults for the keys a `lamb` block omits (recalled, not pinned: no TF Model Garden at hand)
@@ -268,8 +308,26 @@ class TrainerConfig(Config):
         sub = (oc.get(block) or {}).get(inner) or {}
         for k, v in sub.items():
           flat['warmup_power' if (block == 'warmup' and k == 'power') else k] = v
+      # the `ema` block (a dict, also an empty one; `ema: null` is TFM's "no EMA") or dotted `ema.<key>` overrides: its
+      # keys become the ema_* fields and its presence `ema_enabled`
+      ema = {}
+      for k, v in oc.items():
+        if k == 'ema' and isinstance(v, dict):
+          ema.update(v)
+          flat['ema_enabled'] = True
+        elif k.startswith('ema.'):
+          ema[k[4:]] = v
+          flat['ema_enabled'] = True
+      for k, v in ema.items():
+        if k in _EMA_KEYS:
+          flat['ema_' + k] = v
+        elif strict:
+          raise KeyError(f'unknown config key `{_path}optimizer_config.ema.{k}`')
+        else:
+          warnings.warn(f'unknown config key `{_path}optimizer_config.ema.{k}` (ignored)')
       values = dict(values, optimizer_config={**{k: v for k, v in oc.items()
-                                                 if k not in ('optimizer', 'learning_rate', 'warmup')}, **flat})
+                                                 if k not in ('optimizer', 'learning_rate', 'warmup', 'ema') and not k.startswith('ema.')},
+                                              **flat})
     return super().override(values, strict, _path)
 
 

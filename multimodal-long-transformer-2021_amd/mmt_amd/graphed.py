@@ -60,6 +60,8 @@ class GraphedTrainStep:
   def _write_scalars(self, step: int):
     c = self.opt_cfg
     self.scalars.write(step, optimization.learning_rate_at(c, step - 1), self.optimizer.t + 1, c.beta_1, c.beta_2)
+    if getattr(self.optimizer, 'ema_enabled', False):      # 1 - decay of the weight averages, in the optimizer's own device word
+      self.optimizer.write_ema_scalar(self.optimizer.t + 1)
 
   def _same_signature(self, batch) -> bool:
     """Does `batch` fit the recorded graph's input buffers?  Same keys, same tensor shapes / dtypes / devices, equal

@@ -20,6 +20,37 @@ def learning_rate_at(cfg: OptimizerConfig, step: int) -> float:
   return decayed
 
 
+def check_ema_config(cfg: OptimizerConfig) -> None:
+  """ValueError for an `ema` block no decay can be computed from (`create_optimizer` calls this: before the first step)."""
+  if not getattr(cfg, 'ema_enabled', False):
+    return
+  d, s = cfg.ema_average_decay, cfg.ema_start_step
+  if isinstance(d, bool) or not isinstance(d, (int, float)) or not 0.0 <= d <= 1.0:       # NaN fails the comparison too
+    raise ValueError(f'optimizer_config.ema.average_decay must be in [0, 1], got {d!r}')
+  if isinstance(s, bool) or not isinstance(s, int) or s < 0:
+    raise ValueError(f'optimizer_config.ema.start_step must be a non-negative integer, got {s!r}')
+
+
+def ema_decay_at(cfg: OptimizerConfig, t: int) -> float:
+  """Decay of the weight averages at optimizer step `t` (counted after the step's increment: 1 for the first step), in
+  Python floats.  TFM `ExponentialMovingAverage` (official/modeling/optimization/ema_optimizer.py; recalled, not pinned):
+  0 before `start_step` -- the average IS the parameter -- then `average_decay`, capped by (1 + s) / (10 + s) with
+  s = t - start_step while `dynamic_decay` is on."""
+  t = int(t)
+  if t < cfg.ema_start_step:
+    return 0.0
+  if not cfg.ema_dynamic_decay:
+    return float(cfg.ema_average_decay)
+  s = t - cfg.ema_start_step
+  return min(float(cfg.ema_average_decay), (1 + s) / (10 + s))
+
+
+def ema_one_minus_decay(cfg: OptimizerConfig, t: int) -> float:
+  """What the update multiplies with: 1 - decay in double (the descriptor, `Tensor.fill_` and numpy round it to fp32
+  the same way)."""
+  return 1.0 - ema_decay_at(cfg, t)
+
+
 def split_decay_groups(named_params, exclude_patterns):
   decay, no_decay = [], []
   for name, p in named_params:
@@ -43,7 +74,15 @@ class _FlatSlabOptimizer:
   """What the flat optimizers share: per gradient bucket of the reducer one slab each of fp32 master parameters, the
   two moments and the bf16 shadow weights the forward pass uses (`param._mmt_shadow`), and a per-chunk weight-decay
   array (every parameter owns whole 1024-element chunks, `distribute.GradientBucketReducer`).  The parameters are
-  re-homed into `slab['param']`.  A subclass adds `step`."""
+  re-homed into `slab['param']`.  A subclass adds `step`.
+
+  With `cfg.ema_enabled` every slab carries one more fp32 slab, `slab['avg']`: the exponential moving average of the
+  parameters (TFM `optimizer_config.ema`; `ema_decay_at`), a copy of them to begin with, updated by one `mmt_ema_step`
+  launch per slab behind the slab's update launch, on the same stream -- so it is recorded with the step.  Eager steps
+  carry 1 - decay in the descriptor; while the device step scalars are active the descriptor names a one-float device
+  word of the optimizer's (`write_ema_scalar`), as `hyper` does for the learning rate.  `swap_weights` exchanges
+  parameters and averages in place (`mmt_ema_swap`, which also writes the bf16 shadow of what becomes the parameter):
+  exact, so twice is the identity."""
 
   def __init__(self, named_params, cfg: OptimizerConfig, reducer, shadow_dtype=torch.bfloat16):
     from . import _lib
@@ -72,6 +111,56 @@ class _FlatSlabOptimizer:
       slab['shadow'].copy_(slab['param'])
     for p, _, _ in reducer.layout:
       p._mmt_shadow_version = p._version     # layers._current_shadow re-syncs after any later torch-side write
+    self.ema_enabled = bool(getattr(cfg, 'ema_enabled', False))
+    self._ema_word = {}                      # device -> the one-float DEVICE word mmt_ema_desc.one_minus_decay_dev names
+    if self.ema_enabled:
+      check_ema_config(cfg)
+      for slab in self.slabs:
+        slab['avg'] = slab['param'].clone()  # TFM's shadow_copy: the averages start as the parameters
+        dev = slab['param'].device
+        if dev not in self._ema_word:
+          self._ema_word[dev] = torch.ones(1, dtype=torch.float32, device=dev)
+
+  # ---- the weight averages (no-ops without an `ema` block) ----
+  def _ema_desc(self):
+    """The descriptor of this step's `mmt_ema_step` launches, or None without EMA.  `self.t` is already this step's."""
+    if not self.ema_enabled:
+      return None
+    d = self._lib.EmaDesc()
+    d.one_minus_decay = ema_one_minus_decay(self.cfg, self.t)
+    return d
+
+  def _queue_ema(self, L, d, slab, dev):
+    d.n = slab['param'].numel()
+    d.one_minus_decay_dev = self._ema_word[dev].data_ptr() if step_scalars.device_active(dev) else None
+    self._lib.check(L.mmt_ema_step(d, slab['param'].data_ptr(), slab['avg'].data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+
+  def write_ema_scalar(self, t: int) -> None:
+    """Queues 1 - decay of optimizer step `t` into the device word(s) on the current stream.  The value travels as a
+    kernel argument of `fill_`'s launch, so the host may run ahead of the device (`DeviceStepScalars.write`)."""
+    for word in self._ema_word.values():
+      word.fill_(ema_one_minus_decay(self.cfg, t))
+
+  @torch.no_grad()
+  def swap_weights(self) -> None:
+    """Exchanges the parameters and their averages in place, the bf16 shadows following the parameters (TFM's
+    `swap_weights`).  torch's version counters are not touched and `_mmt_shadow_version` stays right: the kernel
+    writes master and shadow together, as the optimizer step does."""
+    if not self.ema_enabled:
+      return
+    L = self._lib.lib()
+    for slab in self.slabs:
+      dev = slab['param'].device
+      with torch.cuda.device(dev):
+        self._lib.check(L.mmt_ema_swap(slab['param'].numel(), slab['param'].data_ptr(), slab['avg'].data_ptr(),
+                                       slab['shadow'].data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+
+  @torch.no_grad()
+  def reset_averages(self) -> None:
+    """The averages become a copy of the parameters (a restore from a file that has none)."""
+    for slab in self.slabs:
+      if 'avg' in slab:
+        slab['avg'].copy_(slab['param'])
 
   def zero_grad(self, set_to_none: bool = False):
     self.reducer.zero_grad()
@@ -116,6 +205,7 @@ class FusedAdamW(_FlatSlabOptimizer):
   def step(self, grad_scale=None):
     self.t += 1
     d = self._fill_desc(self._lib.AdamwDesc())
+    ema = self._ema_desc()
     L = self._lib.lib()
     for slab in self.slabs:
       d.n = slab['grad'].numel()
@@ -127,6 +217,8 @@ class FusedAdamW(_FlatSlabOptimizer):
             slab['shadow'].data_ptr(), slab['wd'].data_ptr(),
             None if grad_scale is None else grad_scale.data_ptr(),
             torch.cuda.current_stream(dev).cuda_stream))
+        if ema is not None:
+          self._queue_ema(L, ema, slab, dev)
     self.reducer.buckets_are_zero = True
 
 
@@ -156,6 +248,7 @@ class FusedLamb(_FlatSlabOptimizer):
   def step(self, grad_scale=None):
     self.t += 1
     d = self._fill_desc(self._lib.LambDesc())
+    ema = self._ema_desc()
     L = self._lib.lib()
     for slab in self.slabs:
       d.n = slab['grad'].numel()
@@ -168,6 +261,8 @@ class FusedLamb(_FlatSlabOptimizer):
             slab['shadow'].data_ptr(), slab['wd'].data_ptr(), slab['segment_start'].data_ptr(),
             slab['segment_adapt'].data_ptr(), None if grad_scale is None else grad_scale.data_ptr(),
             slab['workspace'].data_ptr(), slab['workspace'].numel() * 4, torch.cuda.current_stream(dev).cuda_stream))
+        if ema is not None:
+          self._queue_ema(L, ema, slab, dev)
     self.reducer.buckets_are_zero = True
 
 
@@ -224,10 +319,89 @@ class Lamb(torch.optim.Optimizer):
     return loss
 
 
+class WeightAverages:
+  """The weight averages of an optimizer off the flat path (`torch.optim.AdamW`, `Lamb`; CPU, or no reducer) in plain
+  torch ops, and the fp32 yardstick of the flat optimizers' `slab['avg']`: one fp32 average per trainable parameter, a
+  copy of it to begin with, updated from a step post-hook of `optimizer` with the recurrence of `ema_decay_at`:
+    avg <- fp32(avg + omd * fp32(param - avg)),  omd = fp32(1 - decay)
+  -- the product and the sum in double, rounded once, which is the fused multiply-add of `mmt_ema_step` up to the last
+  bit (the double sum can land on an fp32 midpoint); decay 0 copies the parameter and decay 1 changes nothing, exactly.
+  `t` counts the optimizer's steps (a restore sets it from the checkpoint's step).  `swap_weights` exchanges parameters
+  and averages in place."""
+
+  def __init__(self, optimizer: torch.optim.Optimizer, cfg: OptimizerConfig):
+    check_ema_config(cfg)
+    self.cfg, self.t = cfg, 0
+    self.params = [p for g in optimizer.param_groups for p in g['params'] if p.requires_grad]
+    self.averages = [p.detach().clone() for p in self.params]
+    self._hook = optimizer.register_step_post_hook(lambda *_: self.update())
+
+  @torch.no_grad()
+  def update(self) -> None:
+    self.t += 1
+    omd = float(torch.tensor(ema_one_minus_decay(self.cfg, self.t), dtype=torch.float32))
+    if omd == 0.0:
+      return
+    for p, a in zip(self.params, self.averages):
+      if omd == 1.0:
+        a.copy_(p)
+      else:
+        a.copy_(a.double().add_((p - a).double(), alpha=omd))
+
+  @torch.no_grad()
+  def swap_weights(self) -> None:
+    for p, a in zip(self.params, self.averages):
+      tmp = p.detach().clone()
+      p.copy_(a)
+      a.copy_(tmp)
+
+  @torch.no_grad()
+  def reset_averages(self) -> None:
+    for p, a in zip(self.params, self.averages):
+      a.copy_(p)
+
+
+def weight_averager(optimizer):
+  """Who holds `optimizer`'s weight averages and can `swap_weights()` them in: the flat optimizer itself, the
+  `WeightAverages` that `create_optimizer` hung on a torch optimizer, or None without an `ema` block."""
+  if optimizer is None:
+    return None
+  if getattr(optimizer, 'ema_enabled', False):
+    return optimizer
+  return getattr(optimizer, 'weight_averages', None)
+
+
+class averaged_weights:
+  """`with averaged_weights(optimizer):` -- the model holds the averages inside (TFM's `swap_weights` around its
+  evaluation) and its own weights again after, also when the body raises.  Nothing happens without an `ema` block."""
+
+  def __init__(self, optimizer):
+    self.averager = weight_averager(optimizer)
+
+  def __enter__(self):
+    if self.averager is not None:
+      self.averager.swap_weights()
+    return self.averager
+
+  def __exit__(self, *exc):
+    if self.averager is not None:
+      self.averager.swap_weights()
+    return False
+
+
 def create_optimizer(model: torch.nn.Module, cfg: OptimizerConfig, reducer=None):
   """torch.optim.AdamW (fused) by default; with a gradient reducer on the GPU, the flat
   `FusedAdamW` that shares the reducer's bucket layout.  `cfg.optimizer_type == 'lamb'`: `FusedLamb` under the same
-  condition, else `Lamb`."""
+  condition, else `Lamb`.  With `cfg.ema_enabled` the flat optimizers keep the weight averages themselves; a torch
+  optimizer gets a `WeightAverages` as `optimizer.weight_averages` (`weight_averager` finds either)."""
+  check_ema_config(cfg)
+  optimizer = _create_optimizer(model, cfg, reducer)
+  if getattr(cfg, 'ema_enabled', False) and not hasattr(optimizer, 'slabs'):
+    optimizer.weight_averages = WeightAverages(optimizer, cfg)
+  return optimizer
+
+
+def _create_optimizer(model: torch.nn.Module, cfg: OptimizerConfig, reducer=None):
   flat = reducer is not None and all(p.is_cuda for p in reducer.params)
   if cfg.optimizer_type == 'lamb':
     if flat:

@@ -190,12 +190,14 @@ class _TaskBase:
   @torch.no_grad()
   def initialize(self, model):
     """`pretraining.py:341-351`: load `task_config.init_checkpoint` (file, or the latest checkpoint of a
-    directory) into the whole model by checkpoint-item name; missing items are tolerated."""
+    directory) into the whole model by checkpoint-item name; missing items are tolerated.  With
+    `task_config.init_checkpoint_averages` the file's weight averages (`ema_items`) are loaded instead of its weights."""
     from . import checkpoint
     path = checkpoint.latest_checkpoint(getattr(self.task_config, 'init_checkpoint', '') or '')
     if not path:
       return []                        # 'init_checkpoint is empty. Train from scratch.'
-    return checkpoint.restore_items(path, checkpoint.model_items(model))
+    return checkpoint.restore_items(path, checkpoint.model_items(model),
+                                    averages=bool(getattr(self.task_config, 'init_checkpoint_averages', False)))
 
   def validation_step(self, inputs, model, metrics=None):
     """`pretraining.py:300-313` / `classification.py:214-227`: forward, losses, metrics."""
@@ -316,7 +318,7 @@ class ClassificationTask(_TaskBase):
       for key, item in items.items():
         if head_cfg.name and head_cfg.name in key:
           mapping[key] = item
-    return checkpoint.restore_items(path, mapping)
+    return checkpoint.restore_items(path, mapping, averages=bool(getattr(self.task_config, 'init_checkpoint_averages', False)))
 
   def _logits_key(self, model_outputs):
     if self.logits_field in model_outputs:

@@ -8,7 +8,9 @@ path, the classification task -- data are synthetic (`input_utils.synthetic_batc
 
 Modes: `train` trains; `train_and_eval` / `continuous_train_and_eval` also evaluate `task.validation_data` on the schedule
 of `trainer.validation_interval` / `validation_steps` and keep the best checkpoint when `trainer.best_checkpoint_*` say
-so; `eval` restores the latest checkpoint of `model_dir` and evaluates once (`mmt_amd/evaluation.py`).
+so; `eval` restores the latest checkpoint of `model_dir` and evaluates once (`mmt_amd/evaluation.py`).  With a
+`trainer.optimizer_config.ema` block the optimizer keeps an exponential moving average of the weights, every evaluation
+runs on the averages, and the checkpoints carry them (`ema_items`).
 """
 from __future__ import annotations
 
@@ -75,8 +77,11 @@ def run_experiment(params: configs.ExperimentConfig, mode: str, model_dir: str, 
     eval_step = evaluation.make_eval_step(task, model, device)
 
   def run_evaluation(step, **note):
-    eval_logs = evaluation.evaluate(task, model, params.task.validation_data, device=device, rank=strategy.rank,
-                                    steps=params.trainer.validation_steps, step_fn=eval_step)
+    # on the weight averages when the optimizer keeps them (TFM's eval_begin / eval_end: swap_weights round the loop);
+    # the exchange is exact and in place, so the recorded steps and the weights after it are what they were
+    with optimization.averaged_weights(optimizer):
+      eval_logs = evaluation.evaluate(task, model, params.task.validation_data, device=device, rank=strategy.rank,
+                                      steps=params.trainer.validation_steps, step_fn=eval_step)
     logs.append({'step': step, **eval_logs, **note})
     if strategy.rank == 0:
       print(json.dumps(logs[-1]), flush=True)

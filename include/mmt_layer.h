@@ -898,6 +898,60 @@ int mmt_pack_rows_host(const mmt_pack_desc* desc, const int32_t* word_ids, const
                        int64_t* first_positions, float* example_weight, int32_t* out_mlm_positions, int32_t* out_mpp_positions,
                        int32_t* consumed, void* workspace, size_t workspace_bytes);
 
+/* Random item masking in one launch (csrc/item_masking.hip, csrc/item_masking.h; DESIGN.md section 4, "Masking in one
+ * launch"): feature_pipeline.random_item_masking -- tf_text.mask_language_model with a RandomItemSelector and a
+ * MaskValuesChooser, the random draws as inputs -- for a padded batch, bit for bit what its torch ops give.
+ *
+ * In: token_ids int32 [B, T]; n_tokens [B], int64 when desc->n_tokens_i64 is set and int32 otherwise (positions at or
+ * beyond it are padding and never count, whatever the other inputs hold there); word_start uint8 [B, T], nonzero at the
+ * first token of an item, or NULL (every token is an item); item_keys and value_u float [B, T], entry i for item i of the
+ * row; random_ids int32 [B, T], entry t for token t.
+ *
+ * Definition.  Item of a valid token t: (word starts among the valid tokens [0, t]) - 1, at least 0.  An item is
+ * selectable if it has a valid token and none of its valid tokens is one of the n_unselectable ids.  With n of them,
+ * n_sel = min(ceil(float(n) * selection_rate), float(max_selections)), the product one fp32 multiplication rounded once.
+ * The T keys -- an index that is no selectable item counts as +inf -- are ranked in ascending float order, NaN above
+ * everything, -0 equal to +0, the lower index first among equals; a selectable item is chosen when its rank is below
+ * n_sel.  A valid token of a chosen item becomes mask_token_id when value_u[item] < mask_threshold, random_ids[t] when
+ * value_u[item] < random_threshold, and stays otherwise.  The caller rounds the thresholds to float the way its
+ * reference does.
+ *
+ * Out, every element written by every call: masked int32 [B, T]; positions int32 [B, T], the chosen tokens ascending in
+ * the first n_masked[b] entries and 0 behind them; labels int32 [B, T], token_ids at those positions, 0 behind them;
+ * n_masked int64 [B].
+ *
+ * The device call takes DEVICE memory throughout, allocates nothing, takes no workspace and does not wait, so it records
+ * into a graph: one launch whatever the arguments and the data are (grid B, 1024 threads, a row's three int32 arrays in
+ * LDS: 12 * T + 1104 bytes), no atomics on global memory, no floating-point sum -- bitwise reproducible.  n_tokens is
+ * clamped into [0, T]; item indices and compacted positions are counts below T and are clamped again where they become
+ * addresses; token_ids and random_ids are values only -- wrong inputs give wrong rows, never a stray access.
+ * MMT_E_INVALID before any launch: a NULL pointer other than word_start, B or T below 1, a negative n_unselectable,
+ * B * T at or above 2^31.  MMT_E_UNSUPPORTED: T above MMT_MASK_MAX_TOKENS, more than MMT_MASK_MAX_UNSELECTABLE ids.  The
+ * host variant runs the same functions (csrc/item_masking.h) as loops over HOST memory (CPU tensors, the host tests, the
+ * sanitizer program). */
+#define MMT_MASK_MAX_TOKENS 8192
+#define MMT_MASK_MAX_UNSELECTABLE 8
+typedef struct mmt_item_masking_desc {
+  int32_t B, T;
+  int32_t max_selections;
+  int32_t mask_token_id;
+  int32_t n_unselectable;
+  int32_t unselectable[MMT_MASK_MAX_UNSELECTABLE];
+  int32_t n_tokens_i64;     /* n_tokens is int64 [B] (nonzero) or int32 [B] (0) */
+  float selection_rate;
+  float mask_threshold;     /* value_u below it: mask_token_id                   */
+  float random_threshold;   /* otherwise, value_u below it: the random id        */
+  int32_t reserved;
+} mmt_item_masking_desc;
+
+int mmt_item_masking(const mmt_item_masking_desc* desc, const int32_t* token_ids, const void* n_tokens,
+                     const uint8_t* word_start, const float* item_keys, const float* value_u, const int32_t* random_ids,
+                     int32_t* masked, int32_t* positions, int64_t* n_masked, int32_t* labels, void* stream);
+int mmt_item_masking_host(const mmt_item_masking_desc* desc, const int32_t* token_ids, const void* n_tokens,
+                          const uint8_t* word_start, const float* item_keys, const float* value_u,
+                          const int32_t* random_ids, int32_t* masked, int32_t* positions, int64_t* n_masked,
+                          int32_t* labels);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,7 +56,8 @@ EXPORTS = ('mmt_abi_version', 'mmt_last_error', 'mmt_write_step_scalars', 'mmt_w
            'mmt_png_gather', 'mmt_png_scanlines_workspace_bytes', 'mmt_png_scanlines', 'mmt_png_scanlines_host',
            'mmt_lamb_workspace_bytes', 'mmt_lamb_step', 'mmt_lamb_step_host',
            'mmt_pack_rows_workspace_bytes', 'mmt_pack_rows', 'mmt_pack_rows_host',
-           'mmt_ema_step', 'mmt_ema_step_host', 'mmt_ema_swap', 'mmt_ema_swap_host')
+           'mmt_ema_step', 'mmt_ema_step_host', 'mmt_ema_swap', 'mmt_ema_swap_host',
+           'mmt_item_masking', 'mmt_item_masking_host')
 
 
 class EmbedDesc(ctypes.Structure):
@@ -118,6 +119,17 @@ MMT_PACK_MAX_EXAMPLES = 4096             # examples (and example slots) of one m
 class PackDesc(ctypes.Structure):
   _fields_ = [('E', ctypes.c_int32), ('S', ctypes.c_int32), ('R', ctypes.c_int32), ('S_row', ctypes.c_int32),
               ('E_max', ctypes.c_int32), ('n_mlm', ctypes.c_int32), ('n_mpp', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+
+
+MMT_MASK_MAX_TOKENS = 8192               # positions of a row of one mmt_item_masking call: the row lives in LDS
+MMT_MASK_MAX_UNSELECTABLE = 8
+
+
+class ItemMaskingDesc(ctypes.Structure):
+  _fields_ = [('B', ctypes.c_int32), ('T', ctypes.c_int32), ('max_selections', ctypes.c_int32), ('mask_token_id', ctypes.c_int32),
+              ('n_unselectable', ctypes.c_int32), ('unselectable', ctypes.c_int32 * MMT_MASK_MAX_UNSELECTABLE),
+              ('n_tokens_i64', ctypes.c_int32), ('selection_rate', ctypes.c_float), ('mask_threshold', ctypes.c_float),
+              ('random_threshold', ctypes.c_float), ('reserved', ctypes.c_int32)]
 
 
 class ImageDesc(ctypes.Structure):
@@ -325,6 +337,10 @@ def lib() -> ctypes.CDLL:
   L.mmt_ema_swap.argtypes = [ctypes.c_int64, vp, vp, vp, vp]
   L.mmt_ema_swap_host.restype = ctypes.c_int
   L.mmt_ema_swap_host.argtypes = [ctypes.c_int64, vp, vp, vp]
+  L.mmt_item_masking.restype = ctypes.c_int
+  L.mmt_item_masking.argtypes = [ctypes.POINTER(ItemMaskingDesc)] + [vp] * 11
+  L.mmt_item_masking_host.restype = ctypes.c_int
+  L.mmt_item_masking_host.argtypes = [ctypes.POINTER(ItemMaskingDesc)] + [vp] * 10
   L.mmt_grad_clip_scale.restype = ctypes.c_int
   L.mmt_grad_clip_scale.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64), ctypes.c_float,
                                     ctypes.c_float, vp, vp, vp, ctypes.c_size_t, vp]

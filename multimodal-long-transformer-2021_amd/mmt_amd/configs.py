@@ -160,6 +160,10 @@ class MmtDataConfig(Config):        # data/configs.py:20-55 (+ TFM DataConfig ba
   # Packed batches ("Packed batches"): rows per batch, 0 = off (the reference's one example per row)
   pack_rows: int = 0
   pack_row_len: int = 0             # positions of a packed row; 0 = max_seq_len
+  # TFM's DataConfig key (recalled, not pinned): batches the loader keeps ready ahead of the step (`prefetch.Prefetcher`,
+  # a worker thread with its own stream).  None or 0 = off, the default: TFM reads None as "tune it", here it means no
+  # prefetch, so every existing run is what it was.  Negative: ValueError.
+  prefetch_buffer_size: Optional[int] = None
 
 
 @dataclasses.dataclass

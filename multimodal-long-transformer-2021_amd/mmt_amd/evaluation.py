@@ -17,7 +17,7 @@ from typing import Dict, List, Optional
 
 import torch
 
-from . import checkpoint
+from . import checkpoint, prefetch
 from . import metrics as metrics_lib
 
 # `graph=None` with MMT_STEP_GRAPH unset.  Eager: at the BASELINE config-3 shape the replayed step's median per batch was
@@ -191,7 +191,7 @@ class GraphedEvalStep(EvalStep):
     stream = torch.cuda.Stream(dev)
     self.sync_words = ops.reserve_sync_words(dev, stream, _SYNC_WORDS)
     try:
-      with torch.cuda.graph(graph, stream=stream):
+      with prefetch.capture_gate, torch.cuda.graph(graph, stream=stream):     # (no loader thread allocates or waits inside the capture)
         self._run(self.static_batch)
     finally:
       ops.release_sync_words(dev, stream)
@@ -266,12 +266,16 @@ def run_batches(task, step: EvalStep, data_cfg, *, device, rank: int = 0, steps:
   for m in step.all_metrics():
     m.reset_state()
   n = 0
-  while steps < 0 or n < steps:
-    batch = next(data, None)
-    if batch is None:                                            # a finite pass that ends earlier ends the evaluation
-      break
-    step(batch)
-    n += 1
+  try:
+    while steps < 0 or n < steps:
+      batch = next(data, None)
+      if batch is None:                                          # a finite pass that ends earlier ends the evaluation
+        break
+      step(batch)
+      n += 1
+  finally:
+    if isinstance(data, prefetch.Prefetcher):                    # an evaluation that stops early leaves no loader reading and decoding
+      data.close()
   return n
 
 

@@ -1035,7 +1035,7 @@ def make_retrieval_labels(features: Dict[str, torch.Tensor], pos_weight: float =
 def random_item_masking(token_ids: torch.Tensor, n_tokens: torch.Tensor, *, selection_rate: float,
                         max_selections: int, unselectable_ids, mask_token_id: int, item_keys: torch.Tensor,
                         value_u: torch.Tensor, random_ids: torch.Tensor, word_start: torch.Tensor = None,
-                        mask_token_rate: float = 0.8, random_token_rate: float = 0.1):
+                        mask_token_rate: float = 0.8, random_token_rate: float = 0.1, kernel: bool = None):
   """tf_text.mask_language_model(ids, RandomItemSelector(max_selections, selection_rate, unselectable_ids),
   MaskValuesChooser(vocab, mask_token_id, mask_token_rate)) for a padded batch.
 
@@ -1047,7 +1047,20 @@ def random_item_masking(token_ids: torch.Tensor, n_tokens: torch.Tensor, *, sele
   item becomes [MASK] when its value_u < mask_token_rate, random ids when < mask_token_rate +
   random_token_rate, and stays as it is otherwise.
   Returns (masked_token_ids [B,T], positions [B,T] (ascending, first n_masked valid, rest 0), n_masked [B],
-  original ids at those positions [B,T])."""
+  original ids at those positions [B,T]).
+
+  kernel: None -- GPU tensors inside the limits of `mmt_item_masking` (include/mmt_layer.h: int32 token_ids, T <= 8192,
+  at most 8 unselectable ids; lengths [B], draws [B,T], `word_start` bool [B,T] or None) take its one launch on the
+  current stream, everything else the torch ops below; False --
+  the torch ops, the definition and the yardstick; True -- the kernel, or `mmt_item_masking_host` on CPU tensors, and
+  an error outside the limits.  The three give the same bits."""
+  unselectable_ids = tuple(unselectable_ids)
+  if kernel is None:
+    kernel = token_ids.is_cuda and _item_masking_kernel_serves(token_ids, n_tokens, unselectable_ids, mask_token_id, item_keys, value_u,
+                                                               random_ids, word_start)
+  if kernel:
+    return _random_item_masking_kernel(token_ids, n_tokens, selection_rate, max_selections, [int(u) for u in unselectable_ids],
+                                       mask_token_id, item_keys, value_u, random_ids, word_start, mask_token_rate, random_token_rate)
   B, T = token_ids.shape
   dev = token_ids.device
   pos = torch.arange(T, device=dev)[None]
@@ -1086,6 +1099,72 @@ def random_item_masking(token_ids: torch.Tensor, n_tokens: torch.Tensor, *, sele
   return masked, positions, n_masked, labels
 
 
+_INT32_MIN, _INT32_MAX = -(1 << 31), (1 << 31) - 1
+
+
+def _item_masking_kernel_serves(token_ids, n_tokens, unselectable_ids, mask_token_id, item_keys, value_u, random_ids, word_start) -> bool:
+  """What `kernel=None` sends to `mmt_item_masking`: int32 ids inside the library's limits and every other input in the
+  plain form -- [B] lengths, [B,T] draws, a bool [B,T] `word_start` or none.  Anything the torch ops would broadcast or
+  convert (other shapes, an integer `word_start`, an id that is no int32 value) stays with the torch ops."""
+  from . import _lib
+  if not (token_ids.dim() == 2 and token_ids.dtype == torch.int32 and 1 <= token_ids.shape[1] <= _lib.MMT_MASK_MAX_TOKENS and
+          1 <= token_ids.shape[0] and token_ids.numel() < (1 << 31) and len(unselectable_ids) <= _lib.MMT_MASK_MAX_UNSELECTABLE):
+    return False
+  shape = token_ids.shape
+  if n_tokens.shape != shape[:1] or n_tokens.is_floating_point() or not _INT32_MIN <= int(mask_token_id) <= _INT32_MAX:
+    return False
+  if any(t.shape != shape for t in (item_keys, value_u, random_ids)):
+    return False
+  return word_start is None or (word_start.dtype == torch.bool and word_start.shape == shape)
+
+
+def _random_item_masking_kernel(token_ids, n_tokens, selection_rate, max_selections, unselectable_ids, mask_token_id, item_keys,
+                                value_u, random_ids, word_start, mask_token_rate, random_token_rate):
+  """`mmt_item_masking` (GPU tensors, the current stream, fresh outputs, no host wait) or `mmt_item_masking_host`."""
+  from . import _lib
+  if token_ids.dim() != 2 or token_ids.dtype != torch.int32:
+    raise ValueError('random_item_masking(kernel=True) expects token_ids int32 [B,T]')
+  if not _INT32_MIN <= int(mask_token_id) <= _INT32_MAX:
+    raise ValueError(f'mask_token_id {mask_token_id} is no int32 value')
+  dev = token_ids.device
+  B, T = token_ids.shape
+  same = lambda t, dtype: t.to(device=dev, dtype=dtype).contiguous()
+  token_ids = token_ids.contiguous()
+  if n_tokens.dtype not in (torch.int32, torch.int64):
+    n_tokens = n_tokens.to(torch.int64)
+  n_tokens = same(n_tokens, n_tokens.dtype)
+  if n_tokens.shape != (B,):
+    raise ValueError('random_item_masking expects n_tokens [B]')
+  item_keys, value_u, random_ids = same(item_keys, torch.float32), same(value_u, torch.float32), same(random_ids, torch.int32)
+  if word_start is not None:
+    word_start = same(word_start, torch.bool).view(torch.uint8)
+  for t in (item_keys, value_u, random_ids, word_start):
+    if t is not None and t.shape != (B, T):
+      raise ValueError('random_item_masking expects item_keys, value_u, random_ids and word_start [B,T]')
+  d = _lib.ItemMaskingDesc()
+  d.B, d.T = B, T
+  d.max_selections = min(max(int(max_selections), _INT32_MIN), _INT32_MAX)
+  d.mask_token_id = int(mask_token_id)
+  ids = [u for u in unselectable_ids if _INT32_MIN <= u <= _INT32_MAX]          # (no int32 token equals any other)
+  d.n_unselectable = len(ids)
+  for k, u in enumerate(ids[:_lib.MMT_MASK_MAX_UNSELECTABLE]):
+    d.unselectable[k] = u
+  d.n_tokens_i64 = int(n_tokens.dtype == torch.int64)
+  # torch compares a float32 tensor with a Python number in float32: each threshold is the Python value rounded once
+  d.selection_rate, d.mask_threshold = float(selection_rate), float(mask_token_rate)
+  d.random_threshold = float(mask_token_rate + random_token_rate)
+  masked, positions, labels = (torch.empty((B, T), dtype=torch.int32, device=dev) for _ in range(3))
+  n_masked = torch.empty((B,), dtype=torch.int64, device=dev)
+  args = (d, token_ids.data_ptr(), n_tokens.data_ptr(), None if word_start is None else word_start.data_ptr(), item_keys.data_ptr(),
+          value_u.data_ptr(), random_ids.data_ptr(), masked.data_ptr(), positions.data_ptr(), n_masked.data_ptr(), labels.data_ptr())
+  if dev.type == 'cuda':
+    with torch.cuda.device(dev):
+      _lib.check(_lib.lib().mmt_item_masking(*args, torch.cuda.current_stream(dev).cuda_stream))
+  else:
+    _lib.check(_lib.lib().mmt_item_masking_host(*args))
+  return masked, positions, n_masked, labels
+
+
 def _pad_or_fail(x: torch.Tensor, n_live: torch.Tensor, width: int, what: str) -> torch.Tensor:
   """tensor_utils.pad_to_max_seq_len on the compacted [B,T] rows: tf.pad cannot shorten, so more live entries
   than `width` is an error in the reference as well."""
@@ -1101,14 +1180,16 @@ def make_mlm_and_mpp_features(features: Dict[str, torch.Tensor], randoms: Dict[s
                               mask_token_id: int, unselectable_ids, mlm_fraction_to_mask: float = 0.15,
                               mpp_fraction_to_mask: float = 0.5, mlm_max_selections_per_seq: int = 256,
                               mpp_max_selections_per_seq: int = 98, patch_mask_token_id: int = None,
-                              channels: int = 3, output_channel_bits: int = 3, max_pixel_val: int = 256):
+                              channels: int = 3, output_channel_bits: int = 3, max_pixel_val: int = 256,
+                              masking_kernel: bool = None):
   """`make_mlm_and_mpp_features` (data_utils.py:507-637) + `make_word_ids_features` (:728-741), batched.
 
   features: patch_token_ids [B, 2+P] ([CLS] [PATCH] patch tokens), text_token_ids [B,T] + num_text_wordpieces
   [B] (+ optional text_word_start [B,T] for whole-word masking), patch_embeddings [B,P,E],
   unnormalized_patch_embeddings [B,P,E].  randoms: {mlm,mpp}_{item_keys,value_u,random_ids}.
   Returns the new features: word_ids [B,S], patch_token_ids, text_token_ids [B, S-2-P], patch_embeddings (rows
-  of [MASK]ed patches zeroed), mlm_/mpp_ positions, label_ids, label_weights."""
+  of [MASK]ed patches zeroed), mlm_/mpp_ positions, label_ids, label_weights.  masking_kernel: the `kernel` switch of
+  the two `random_item_masking` calls (None: one launch each for GPU tensors)."""
   out = dict(features)
   B = features['patch_token_ids'].shape[0]
   dev = features['patch_token_ids'].device
@@ -1120,7 +1201,7 @@ def make_mlm_and_mpp_features(features: Dict[str, torch.Tensor], randoms: Dict[s
   mpp_tok, mpp_pos, n_mpp, _ = random_item_masking(
       ptok, n_ptok, selection_rate=mpp_fraction_to_mask, max_selections=mpp_max_selections_per_seq,
       unselectable_ids=unselectable_ids, mask_token_id=pm, item_keys=randoms['mpp_item_keys'],
-      value_u=randoms['mpp_value_u'], random_ids=randoms['mpp_random_ids'])
+      value_u=randoms['mpp_value_u'], random_ids=randoms['mpp_random_ids'], kernel=masking_kernel)
   mpp_pos = _pad_or_fail(mpp_pos, n_mpp, mpp_max_selections_per_seq, 'mpp')
   live = torch.arange(mpp_max_selections_per_seq, device=dev)[None] < n_mpp[:, None]
   shifted = (mpp_pos.to(torch.int64) - 2).clamp_(min=0)                                  # -2: [CLS] and [PATCH]
@@ -1141,7 +1222,7 @@ def make_mlm_and_mpp_features(features: Dict[str, torch.Tensor], randoms: Dict[s
       ttok, features['num_text_wordpieces'].to(torch.int64), selection_rate=mlm_fraction_to_mask,
       max_selections=mlm_max, unselectable_ids=unselectable_ids, mask_token_id=mask_token_id,
       item_keys=randoms['mlm_item_keys'], value_u=randoms['mlm_value_u'], random_ids=randoms['mlm_random_ids'],
-      word_start=features.get('text_word_start'))
+      word_start=features.get('text_word_start'), kernel=masking_kernel)
   tlive = torch.arange(ttok.shape[1], device=dev)[None] < n_mlm[:, None]
   mlm_pos = torch.where(tlive, mlm_pos + (2 + num_patches), torch.zeros_like(mlm_pos))     # offset before the padding
   out['mlm_positions'] = _pad_or_fail(mlm_pos, n_mlm, mlm_max, 'mlm')

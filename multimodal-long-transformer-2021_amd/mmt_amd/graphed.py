@@ -18,7 +18,7 @@ from typing import Optional
 
 import torch
 
-from . import fused, ops, optimization, step_scalars
+from . import fused, ops, optimization, prefetch, step_scalars
 
 # arrival counters reserved for a recorded step (one word per attention plane, batch x heads: ops.reserve_sync_words)
 _SYNC_WORDS = 4096
@@ -109,7 +109,7 @@ class GraphedTrainStep:
     # of this or any other model in the process go on taking their epoch and learning rate from the host
     self.scalars.enable()
     try:
-      with torch.cuda.graph(graph, stream=stream):
+      with prefetch.capture_gate, torch.cuda.graph(graph, stream=stream):     # (no loader thread allocates or waits inside the capture)
         self.out = self.task.train_step(self.static_batch, self.model, self.optimizer, metrics=self.metrics,
                                         reducer=self.reducer, clip_norm=self.clip_norm, step=step)
     finally:

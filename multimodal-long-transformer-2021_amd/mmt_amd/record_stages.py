@@ -113,6 +113,8 @@ class RecordStages:
     self._key_ids: Dict[bytes, int] = {}
     if int(getattr(params, 'pack_rows', 0) or 0) < 0 or int(getattr(params, 'pack_row_len', 0) or 0) < 0:
       raise ValueError('pack_rows and pack_row_len must not be negative')
+    if int(getattr(params, 'prefetch_buffer_size', 0) or 0) < 0:
+      raise ValueError('prefetch_buffer_size must not be negative')
     if int(getattr(params, 'pack_rows', 0) or 0) and self.dense_side_inputs:
       raise ValueError('pack_rows takes the structured side inputs: dense_side_inputs must be off')
     # the packing stage's own cost: batches packed, and the seconds spent waiting for their `consumed` words

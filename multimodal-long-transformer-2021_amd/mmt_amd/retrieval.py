@@ -23,7 +23,7 @@ from typing import Any, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import feature_pipeline, predict
+from . import feature_pipeline, predict, prefetch
 from .input_utils import attention_pattern_from_config
 
 # `graph=None` with MMT_STEP_GRAPH unset, as for the train step: on.  Two measurements of this code show the replayed
@@ -230,7 +230,7 @@ class PairScorer:
     stream = torch.cuda.Stream(dev)
     self.sync_words = ops.reserve_sync_words(dev, stream, 4096)
     try:
-      with torch.cuda.graph(graph, stream=stream):
+      with prefetch.capture_gate, torch.cuda.graph(graph, stream=stream):     # (no loader thread allocates or waits inside the capture)
         self.out = self._forward(self.image_entry, self.text_entry)
     finally:
       ops.release_sync_words(dev, stream)
@@ -383,16 +383,23 @@ def write_results_from_scores(scores, scored, image_index, text_index, gt_image_
 
 # ---- from records to recall@k -------------------------------------------------------------------------------------------
 def evaluate_from_records(task, model, data_cfg, batch_size: int, output_dir: Optional[str] = None,
-                          topks: Sequence[int] = (1, 3, 5, 10), shard=(0, 1), **loader_args):
+                          topks: Sequence[int] = (1, 3, 5, 10), shard=(0, 1), prefetch: int = 0, **loader_args):
   """Retrieval evaluation on TFRecord files: `retrieval_dataloader.MmtRetrievalDataLoader(data_cfg, **loader_args)`
   fills the sets, a `PairScorer` scores this shard's pairs -- all of them (`score_all`) for separate sets, the listed
   ones (`score_pairs`, scattered into the [I, T] matrix and its `scored` mask) for pairs in records -- and
   `recall_at_k_from_scores` turns the matrix into the recall dictionary, which is returned.  With `output_dir` the
   reference's two result files are written too (`write_results_from_scores`).  shard (id, n) scores the pairs with
-  p % n == id only; merging the shards of several ranks into one result is not built."""
+  p % n == id only; merging the shards of several ranks into one result is not built.  prefetch > 0: the set build -- all
+  the reading and decoding of this evaluation -- runs on a `prefetch.Prefetcher`'s worker thread and side stream, under
+  the capture gate, and reaches this thread's stream through its event (a negative value is a ValueError)."""
+  from . import prefetch as prefetch_lib
   from .retrieval_dataloader import MmtRetrievalDataLoader
   loader = MmtRetrievalDataLoader(data_cfg, **loader_args)
-  sets, listed = loader.sets(), loader.pairs()
+  if prefetch_lib.check_buffer_size(prefetch) > 0:
+    with prefetch_lib.Prefetcher(((loader.sets(), loader.pairs()) for _ in range(1)), device=loader.device, depth=1) as ahead:
+      sets, listed = next(ahead)
+  else:
+    sets, listed = loader.sets(), loader.pairs()
   scorer = PairScorer(task, model, sets, batch_size)
   try:
     if listed is None:

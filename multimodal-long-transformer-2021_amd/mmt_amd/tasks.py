@@ -68,6 +68,19 @@ class _TaskBase:
 
   def build_inputs(self, params, device='cuda', rank: int = 0, dense_side_inputs: bool = False,
                    batch_size: Optional[int] = None, ragged: bool = False, loader_args: Optional[Dict] = None):
+    """`_build_inputs`, and with `params.prefetch_buffer_size > 0` a `prefetch.Prefetcher` of that depth round what it
+    returns -- records or synthetic, packed or not, both tasks: the iterator then runs on a worker thread and a side
+    stream, ahead of the step ("Prefetch on a side stream").  `self.input_prefetch` is that
+    prefetcher, or None; whoever drives the iterator closes it."""
+    from . import prefetch
+    depth = prefetch.check_buffer_size(getattr(params, 'prefetch_buffer_size', None))
+    data = self._build_inputs(params, device=device, rank=rank, dense_side_inputs=dense_side_inputs, batch_size=batch_size,
+                              ragged=ragged, loader_args=loader_args)
+    self.input_prefetch = prefetch.Prefetcher(data, device=device, depth=depth) if depth > 0 else None
+    return data if self.input_prefetch is None else self.input_prefetch
+
+  def _build_inputs(self, params, device='cuda', rank: int = 0, dense_side_inputs: bool = False,
+                    batch_size: Optional[int] = None, ragged: bool = False, loader_args: Optional[Dict] = None):
     """An iterator of (inputs, labels) with the reference's feature contract; per-replica batch =
     global_batch_size / replicas (`pretrain_dataloader.py:107-108`), seeded per rank.  A task reads TFRecord shards
     when `params.input_path` is a local pattern (no URL scheme) and `params.vocab_filename` names a file: the pretraining

@@ -44,8 +44,10 @@ def run_experiment(params: configs.ExperimentConfig, mode: str, model_dir: str, 
   reducer = strategy.make_reducer(list(model.parameters()), reduce=tasks.gradient_reduce_mode(params.task))
   optimizer = optimization.create_optimizer(model, opt_cfg, reducer=reducer)
   data = task.build_inputs(params.task.train_data, device=device, rank=strategy.rank)
+  train_prefetch = getattr(task, 'input_prefetch', None)      # (an evaluation's build_inputs sets the attribute again)
   if strategy.rank == 0:
     print(json.dumps({'input_source': getattr(task, 'input_source', 'synthetic'),
+                      'input_prefetch': train_prefetch.depth if train_prefetch is not None else 0,
                       'input_path': params.task.train_data.input_path if getattr(task, 'input_source', '') == 'records' else ''}), flush=True)
   steps = max_steps or params.trainer.train_steps
   logs = []
@@ -126,12 +128,16 @@ def run_experiment(params: configs.ExperimentConfig, mode: str, model_dir: str, 
     finally:
       if graphed_step is not None:       # also when the loop raised: the device-resident step scalars must not outlive it
         graphed_step.close()
+      if train_prefetch is not None:     # the loader's worker thread ends with the loop
+        train_prefetch.close()
     if evaluates and start >= steps:     # a resumed run with nothing left to train still reports where it stands
       run_evaluation(start)
   elif evaluates:                        # `eval`: the restored weights (the JSON line says from where; null = none found)
     run_evaluation(start, restored_from=resume_from)
   if eval_step is not None:
     eval_step.close()
+  if train_prefetch is not None:         # (`eval` mode: built, never read)
+    train_prefetch.close()
   return model, logs
 
 

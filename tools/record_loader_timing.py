@@ -12,8 +12,16 @@ rounds; host stages by wall clock, best of 3.  A record, not a gate: nothing is 
   (c) with --finetune, alone: the fine-tuning loader (mmt_amd/classification_dataloader.py) per batch and the retrieval
       set build (mmt_amd/retrieval_dataloader.py, 64 images and 512 texts) at the fine-tuning shape (batch 64,
       max_seq_len 256, image 224, patch 16, ratio 1), beside the fine-tuning step of the same run.
+  (d) with --masking, alone: the masking stage of (b), `random_item_masking` over [4, 3971] and [4, 125] together, and the
+      fine-tuning shape [64, 256]: the one launch of csrc/item_masking.hip against the torch ops (`kernel=False`) in the
+      same call, the two routes alternating, after their outputs were compared bit for bit.
 
-Writes one JSON record (--out, default profiles/record_loader_timing.json; profiles/finetune_loader_timing.json for (c))."""
+  (e) with --prefetch, alone: the train step at the shape of (b), recorded as a HIP graph, fed by one resident batch, by the
+      plain loader on the training thread, and by the loader behind a `prefetch.Prefetcher` of depth 2; three readings of
+      --steps steps each, alternating, host clock around a final synchronise.
+
+Writes one JSON record (--out, default profiles/record_loader_timing.json; profiles/finetune_loader_timing.json for (c),
+profiles/masking_timing.json for (d), profiles/prefetch_timing.json for (e))."""
 import argparse
 import ctypes
 import json
@@ -140,9 +148,10 @@ def crc_leg(torch, _lib, name, payloads, args):
   return out
 
 
-def loader_leg(torch, _lib, files, args):
-  from mmt_amd import configs, feature_pipeline as fp, input_utils, pretrain_dataloader as pd, records, text_frontend
-  from mmt_amd.ops import side_inputs
+def config3_shard(torch, _lib, files):
+  """One shard of 16 records at the benchmark's shape (batch 4, max_seq_len 4096, image 1008, patch 16) from the
+  synthesised files, with its vocabulary: (shard, vocab_path, fields, payloads, (B, S, IMG, PATCH))."""
+  from mmt_amd import records
   L = _lib.lib()
   B, S, IMG, PATCH = 4, 4096, 1008, 16
   rng = np.random.default_rng(1)
@@ -172,6 +181,14 @@ def loader_leg(torch, _lib, files, args):
       head = struct.pack('<Q', len(p))
       f.write(head + struct.pack('<I', mask(crc32c(head))) + p + struct.pack('<I', mask(c)))
 
+  return shard, vocab_path, fields, payloads, (B, S, IMG, PATCH)
+
+
+def loader_leg(torch, _lib, files, args):
+  from mmt_amd import configs, feature_pipeline as fp, input_utils, pretrain_dataloader as pd, records, text_frontend
+  from mmt_amd.ops import side_inputs
+  L = _lib.lib()
+  shard, vocab_path, fields, payloads, (B, S, IMG, PATCH) = config3_shard(torch, _lib, files)
   cfg = configs.MmtPretrainDataConfig(input_path=shard, vocab_filename=vocab_path, is_training=True, global_batch_size=B, image_size=IMG,
                                       patch_size=PATCH, max_seq_len=S, tasks='mlm', text_special_token_field_dict=json.dumps(fields), seed=3)
   loader = pd.MmtPretrainDataLoader(cfg, device='cuda', shuffle_buffer=8)
@@ -364,9 +381,106 @@ def finetune_leg(torch, _lib, args):
   return out
 
 
+def masking_leg(torch, args):
+  """The masking stage alone, `random_item_masking` through its one launch against `kernel=False` (the torch ops) in the
+  same call, HIP events: the config-3 pair of calls -- the patch row [4, 3971], every token an item, and the text row
+  [4, 125] with whole words -- timed together, as `device_masking` of leg (b) holds them, and the fine-tuning shape
+  [64, 256]."""
+  from mmt_amd import feature_pipeline as fp
+  g = torch.Generator(device='cuda').manual_seed(5)
+
+  def inputs(B, T, whole_word, rate, cap):
+    tok = torch.randint(1000, 30000, (B, T), device='cuda', generator=g).to(torch.int32)
+    tok[:, 0] = 101
+    kw = dict(selection_rate=rate, max_selections=cap, unselectable_ids=[101, 102, 5, 6], mask_token_id=103,
+              item_keys=torch.rand(B, T, device='cuda', generator=g), value_u=torch.rand(B, T, device='cuda', generator=g),
+              random_ids=torch.randint(0, 30000, (B, T), device='cuda', generator=g).to(torch.int32),
+              word_start=(torch.rand(B, T, device='cuda', generator=g) < 0.6) if whole_word else None)
+    n = torch.randint(T // 2, T + 1, (B,), device='cuda', generator=g) if whole_word else torch.full((B,), T, device='cuda')
+    return tok, n, kw
+
+  shapes = {'config3_patches_4x3971_and_text_4x125': [inputs(4, 3971, False, 0.5, 1985), inputs(4, 125, True, 0.15, 125)],
+            'finetune_64x256': [inputs(64, 256, True, 0.15, 20)]}
+  out = {}
+  for name, calls in shapes.items():
+    def run(kernel):
+      return [fp.random_item_masking(tok, n, kernel=kernel, **kw) for tok, n, kw in calls]
+    for a, b in zip(run(True), run(False)):
+      assert all(torch.equal(x, y) for x, y in zip(a, b)), name
+    # alternate the two routes, so that a drift of the clocks falls on both
+    rec = {'kernel': [], 'torch_ops': []}
+    for _ in range(3):
+      rec['kernel'].append(event_times(torch, lambda: run(True), args.rounds, args.calls))
+      rec['torch_ops'].append(event_times(torch, lambda: run(False), args.rounds, args.calls))
+    out[name] = {k: {'us_median': statistics.median(r['us_median'] for r in v), 'us_min': min(r['us_min'] for r in v),
+                     'us_max': max(r['us_max'] for r in v), 'repeats_us_median': [r['us_median'] for r in v]} for k, v in rec.items()}
+    print(name, json.dumps(out[name]))
+  return out
+
+
+def prefetch_leg(torch, _lib, files, args):
+  """The train step at the config-3 shape (bench.py's model and optimizer, recorded as a HIP graph; tasks = 'mlm', as in
+  leg (b)) fed three ways, alternating in one process, `--steps` steps each after warm-up, host clock around a final
+  synchronise: one resident batch; the plain loader on the training thread; the loader behind a Prefetcher of depth 2."""
+  import bench
+  from mmt_amd import distribute, graphed, optimization, tasks, configs
+  shard, vocab_path, fields, _, (B, S, IMG, PATCH) = config3_shard(torch, _lib, files)
+  c = bench.get_config(3)
+  exp = configs.get_exp_config('mmt/pretraining')
+  exp.override({'task': {'micro_batch_size': B,
+                         'model': {'encoder': {'mmt': {'relative_pos_max_distance': c['m'], 'relative_vocab_size': c['R']}},
+                                   'cls_heads': [{'inner_dim': 768, 'num_classes': 2, 'name': 'itm'}]},
+                         'train_data': dict(input_path=shard, vocab_filename=vocab_path, max_seq_len=S, image_size=IMG, patch_size=PATCH,
+                                            global_batch_size=B, tasks='mlm', mpp_fraction_to_mask=0.0, seed=3,
+                                            text_special_token_field_dict=json.dumps(fields), relative_pos_max_distance=c['m'],
+                                            local_radius=c['radius'], num_global_tokens=c['ng'])}})
+  task = tasks.PretrainingTask(exp.task, compute_dtype=torch.bfloat16)
+  torch.manual_seed(0)
+  model = task.build_model().cuda()
+  opt_cfg = exp.trainer.optimizer_config
+  reducer = distribute.DataParallelStrategy(None).make_reducer(list(model.parameters()), reduce=tasks.gradient_reduce_mode(exp.task))
+  optimizer = optimization.create_optimizer(model, opt_cfg, reducer=reducer)
+  step = graphed.GraphedTrainStep(task, model, optimizer, reducer, opt_cfg, clip_norm=opt_cfg.gradient_clip_norm)
+  d = exp.task.train_data
+  plain = task.build_inputs(d, device='cuda', batch_size=B, loader_args=dict(shuffle_buffer=8))
+  d.prefetch_buffer_size = 2
+  ahead = task.build_inputs(d, device='cuda', batch_size=B, loader_args=dict(shuffle_buffer=8))
+  ahead.timeout = 120
+  resident = next(plain)
+  feeds = {'resident_batch': lambda: resident, 'plain_loader': lambda: next(plain), 'prefetched_depth_2': lambda: next(ahead)}
+  n = {'i': 0}
+
+  def run(feed, steps):
+    for _ in range(steps):
+      n['i'] += 1
+      step(feed(), n['i'])
+    torch.cuda.synchronize()
+  out = {'shape': dict(batch=B, max_seq_len=S, image_size=IMG, patch_size=PATCH, tasks='mlm'), 'steps_per_reading': args.steps}
+  try:
+    for feed in feeds.values():                                    # warm-up: the eager steps, the recording, every feed
+      run(feed, 6)
+    assert step.graph is not None, 'the step was not recorded'
+    ms = {k: [] for k in feeds}
+    for _ in range(3):
+      for k, feed in feeds.items():
+        t0 = time.perf_counter()
+        run(feed, args.steps)
+        ms[k].append((time.perf_counter() - t0) * 1e3 / args.steps)
+    for k, v in ms.items():
+      out[k] = {'ms_per_step_median': round(statistics.median(v), 3), 'min': round(min(v), 3), 'max': round(max(v), 3)}
+      print(f'  prefetch {k}: {out[k]}')
+  finally:
+    ahead.close()
+    step.close()
+  return out
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--finetune', action='store_true', help='run leg (c) alone and write profiles/finetune_loader_timing.json')
+  ap.add_argument('--masking', action='store_true', help='time the masking stage alone and write profiles/masking_timing.json')
+  ap.add_argument('--prefetch', action='store_true', help='time the train step fed three ways and write profiles/prefetch_timing.json')
+  ap.add_argument('--steps', type=int, default=100, help='steps of one reading of --prefetch')
   ap.add_argument('--batch', type=int, default=64)
   ap.add_argument('--size', type=int, default=1008)
   ap.add_argument('--quality', type=int, default=90)
@@ -379,6 +493,25 @@ def main():
   import torch
   from mmt_amd import _lib
   assert torch.cuda.is_available(), 'record_loader_timing needs a GPU'
+  if args.masking:
+    out = args.out if args.out != ap.get_default('out') else os.path.join(ROOT, 'profiles', 'masking_timing.json')
+    record = {'device': torch.cuda.get_device_name(0), 'rounds': args.rounds, 'calls_per_round': args.calls,
+              'masking': masking_leg(torch, args)}
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'w') as f:
+      json.dump(record, f, indent=1)
+    print('wrote', out)
+    return
+  if args.prefetch:
+    out = args.out if args.out != ap.get_default('out') else os.path.join(ROOT, 'profiles', 'prefetch_timing.json')
+    rng = np.random.default_rng(0)
+    distinct = [encode_jpeg(rng.integers(0, 256, size=(args.size, args.size, 3), dtype=np.uint8), args.quality) for _ in range(min(args.distinct, 4))]
+    record = {'device': torch.cuda.get_device_name(0), 'prefetch': prefetch_leg(torch, _lib, distinct, args)}
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'w') as f:
+      json.dump(record, f, indent=1)
+    print('wrote', out)
+    return
   if args.finetune:
     out = args.out if args.out != ap.get_default('out') else os.path.join(ROOT, 'profiles', 'finetune_loader_timing.json')
     record = {'device': torch.cuda.get_device_name(0), 'finetune': finetune_leg(torch, _lib, args)}

@@ -9,11 +9,14 @@ and `reduce='sum'` reproduces the reference default -- SURVEY.md 8(e).
 """
 from __future__ import annotations
 
+import ctypes
 import os
 from typing import List, Optional
 
 import torch
 import torch.distributed as dist
+
+from . import _lib, deferred
 
 _VALID = ('off', 'one_device', 'mirrored', 'multi_worker_mirrored', 'tpu', 'parameter_server')
 
@@ -117,7 +120,6 @@ class GradientBucketReducer:
     if self.exchange:
       if self.params and self.params[0].is_cuda:
         # leave compute units to the RCCL kernels that run under backward (csrc/wgrad_gemm.hip)
-        from . import _lib
         _lib.lib().mmt_wgrad_set_cu_budget(int(os.environ.get('MMT_WGRAD_CUS', '224')))
         _lib.lib().mmt_ffn_set_cu_budget(int(os.environ.get('MMT_FFN_CUS', '224')))
       for p in self.params:
@@ -139,8 +141,7 @@ class GradientBucketReducer:
     self._ready = set()
     self.armed = True
     # a backward that raised may have left parameters marked "product still queued": start every step clean
-    for p in self._bucket_of:
-      p._mmt_grad_deferred = False
+    deferred.clear_grad_deferred(*self._bucket_of)
 
   def set_armed(self, armed: bool):
     """With gradient accumulation over micro-batches only the LAST backward may launch the
@@ -149,7 +150,7 @@ class GradientBucketReducer:
 
   def _on_grad_ready_from_kernel(self, p):
     """A kernel that wrote p.grad itself reports that the write is enqueued."""
-    p._mmt_grad_deferred = False
+    deferred.clear_grad_deferred(p)
     self._on_grad_ready(p)
 
   def _on_grad_ready(self, p):
@@ -196,8 +197,6 @@ class GradientBucketReducer:
     ps = getattr(self, 'pending_scale', 1.0)                  # buckets hold ps^-1 x the true gradient
     if self.buckets[0].is_cuda and len(self.buckets) <= 16:
       # one streaming HIP pass over the slabs + a fixed-order sum; the clip factor is written on the device
-      import ctypes
-      from . import _lib
       dev = self.buckets[0].device
       if getattr(self, '_clip_ws', None) is None:
         self._clip_ws = torch.empty(2048 + 2, dtype=torch.float32, device=dev)

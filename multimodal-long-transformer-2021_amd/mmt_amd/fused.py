@@ -13,6 +13,9 @@ from typing import Optional
 import torch
 
 from . import _lib, step_scalars
+from .deferred import (DeferredLaunches, Product, Reduce, _byte_range, _ranges_overlap,  # noqa: F401
+                       clear_grad_deferred, forget_stale_queues as _forget_stale_queues, grouping_is_safe,
+                       mark_grad_deferred, notify_grad_ready, reset_host_queues)
 
 # Dropout seeds are a pure function of (train step, micro step, data-parallel rank, index of the
 # dropout site within the forward pass): replicas draw different masks for their shards and a run
@@ -90,8 +93,7 @@ def _finish(param, buf, direct):
   """Return value for autograd + gradient-ready notification for directly written grads."""
   if not direct:
     return buf
-  for hook in getattr(param, '_mmt_grad_ready_hooks', ()):
-    hook(param)
+  notify_grad_ready(param)
   return None
 
 
@@ -100,46 +102,8 @@ def _finish(param, buf, direct):
 # workspace and a 5-us reduce launch folds them -- ~32 of those per step.  When the gradients go straight into fp32
 # masters and nothing waits for them before the backward pass ends (no parameter carries a reducer's hooks), the
 # reduces are queued (desc.defer_reduce; the workspaces stay alive in the queue) and launched ONCE by an engine callback
-# at the end of backward (`mmt_colsum_reduce_batch`).
+# at the end of backward (`mmt_colsum_reduce_batch`).  The queue (`deferred.DeferredLaunches`) holds up to _CS_MAX of them.
 _CS_MAX = 48
-# (device, graph-task id) -> (graph-task id, [(workspace, rows, H, kind, outs)]): ONE entry per backward pass and device.
-# A re-entrant pass (torch.utils.checkpoint(..., use_reentrant=True) runs one inside a node of the outer pass) has an id
-# and an entry of its own, flushed by its own end-of-backward callback; the outer pass's entry waits for the outer one.
-_cs_deferred = {}
-
-
-def _byte_range(t: torch.Tensor):
-  """[lo, hi) addresses a row-strided 2-D (or contiguous 1-D) tensor spans, gaps between its rows included."""
-  lo = t.data_ptr()
-  n = t.numel() if t.dim() != 2 else (t.shape[0] - 1) * t.stride(0) + t.shape[1]
-  return lo, lo + n * t.element_size()
-
-
-def _ranges_overlap(a, b) -> bool:
-  return any(x[0] < y[1] and y[0] < x[1] for x in a for y in b)
-
-
-def _drop_entries(queue, stale) -> None:
-  for key in stale:
-    for item in queue.pop(key)[1]:
-      for prm in (item[4] if queue is _wg_deferred else ()):
-        prm._mmt_grad_deferred = False
-
-
-def _forget_passes_after(gid) -> None:
-  """A pass whose id is larger than the running one's began after it, i.e. inside one of its nodes, and has returned: what
-  it still has queued was left behind when it raised (its end-of-backward callback never ran) and is nobody's to launch."""
-  for queue in (_cs_deferred, _wg_deferred):
-    _drop_entries(queue, [key for key in queue if key[1] > gid])
-
-
-def _forget_stale_queues() -> None:
-  """Called where a forward pass starts work (descriptors, the step's seed stream): OUTSIDE any backward pass every queued
-  item was left behind by a pass that raised -- its operands belong to a step that is over -- and is dropped.  (Inside
-  one -- a checkpointed segment recomputed by the outer pass -- the outer pass's items are alive and stay.)"""
-  if (_wg_deferred or _cs_deferred) and _graph_task_id() == -1 and grouping_is_safe():
-    for queue in (_cs_deferred, _wg_deferred):
-      _drop_entries(queue, list(queue))
 
 
 def _defer_colsum_ok(direct: bool, *params) -> bool:
@@ -150,89 +114,81 @@ def _defer_colsum_ok(direct: bool, *params) -> bool:
 def _launch_colsum_batch(items, device) -> None:
   """The queued reduces in one launch on the current stream of `device`."""
   arr = (_lib.ColsumItem * len(items))()
-  for q, (ws, rows, H, kind, outs, *_) in zip(arr, items):
-    o = list(outs) + [None] * (3 - len(outs))
-    q.workspace, q.o0, q.o1, q.o2 = ws.data_ptr(), _p(o[0]), _p(o[1]), _p(o[2])
-    q.rows, q.H, q.kind, q.accumulate = rows, H, kind, 1
+  for q, item in zip(arr, items):
+    o = list(item.outs) + [None] * (3 - len(item.outs))
+    q.workspace, q.o0, q.o1, q.o2 = item.ws.data_ptr(), _p(o[0]), _p(o[1]), _p(o[2])
+    q.rows, q.H, q.kind, q.accumulate = item.rows, item.H, item.kind, 1
   with torch.cuda.device(device):
     _lib.check(_lib.lib().mmt_colsum_reduce_batch(len(items), arr, torch.cuda.current_stream(device).cuda_stream))
 
 
-def _flush_colsum(key) -> None:
-  entry = _cs_deferred.pop(key, None)
-  if not entry or not entry[1]:
-    return
-  _launch_colsum_batch(entry[1], key[0])
+# (the launch functions of both queues are looked up when a launch is due: the host tests replace them with recorders)
+_cs_deferred = DeferredLaunches(launch=lambda items, device: _launch_colsum_batch(items, device), limit=lambda items: _CS_MAX)
 
 
-def _flush_all_colsum():
-  """End-of-backward callback: the reduces of the pass that is ending (the callback runs under its graph-task id)."""
-  gid = _graph_task_id()
-  for key in [k for k in _cs_deferred if k[1] == gid]:
-    _flush_colsum(key)
-  _forget_passes_after(gid)
+def _defer_colsum(ws, rows: int, H: int, kind: int, outs: tuple) -> None:
+  _cs_deferred.add(ws.device, Reduce(ws, rows, H, kind, outs, tuple(_byte_range(o) for o in outs if o is not None)))
 
 
-def _defer_colsum(ws, rows: int, H: int, kind: int, outs) -> None:
-  gid = _graph_task_id()
-  key = (ws.device, gid)
-  _forget_passes_after(gid)
-  outs = tuple(outs)
-  ranges = tuple(_byte_range(o) for o in outs if o is not None)
-  entry = _cs_deferred.get(key)
-  # an output another queued reduce adds to as well (a bias or LayerNorm parameter used twice in this pass): every reduce
-  # of a batch reads, adds and stores from a workgroup of its own, so the two go in launches one after the other
-  if entry is not None and any(_ranges_overlap(ranges, item[5]) for item in entry[1]):
-    _flush_colsum(key)
-    entry = None
-  if entry is None:
-    entry = _cs_deferred[key] = (gid, [])
-    torch.autograd.Variable._execution_engine.queue_callback(_flush_all_colsum)    # end of this backward pass
-  entry[1].append((ws, rows, H, kind, outs, ranges))
-  if len(entry[1]) >= _CS_MAX:
-    _flush_colsum(key)             # (a later item opens a new entry and queues another callback: harmless)
+def _param_grads(d, params, likes):
+  """The parameter-gradient half of a fused backward; `likes`: the parameters' fp32 stand-ins (None where the op runs
+  without that parameter).  Gives `bufs`, where the kernel writes each gradient -- straight into the fp32 `.grad`s when
+  EVERY one can be (`direct`), else fresh buffers -- with `d.accumulate` and `d.defer_reduce` set to match, and
+  `done(ws, kind)` for after the launch: it queues the column-sum reduce if that was put off and returns what autograd
+  gets per parameter (None for a gradient written in place, whose parameter is reported ready)."""
+  targets = [(None, True) if like is None else _grad_target(p, like) for p, like in zip(params, likes)]
+  direct = all(ok for _, ok in targets)
+  bufs = [buf for buf, _ in targets] if direct else [None if like is None else torch.empty_like(like) for like in likes]
+  d.accumulate, d.defer_reduce = int(direct), int(_defer_colsum_ok(direct, *params))
+
+  def done(ws, kind: int):
+    if d.defer_reduce:
+      _defer_colsum(ws, d.rows, d.H, kind, tuple(buf for buf in bufs if buf is not None))
+    return [None if buf is None else _finish(p, buf, direct) for p, buf in zip(params, bufs)]
+  return bufs, done
+
+
+def _ln_forward(ctx, x, gamma, beta, eps):
+  _check(x, gamma, beta)
+  shape = x.shape
+  x2 = x.reshape(-1, shape[-1]).contiguous()
+  g32, b32 = _f32(gamma), _f32(beta)
+  y = torch.empty_like(x2)
+  mean = torch.empty(x2.shape[0], dtype=torch.float32, device=x.device)
+  rstd = torch.empty_like(mean)
+  d = _desc(x2, eps)
+  with torch.cuda.device(x.device):
+    _lib.check(_lib.lib().mmt_ln_fwd(d, _p(x2), _p(g32), _p(b32), _p(y), _p(mean), _p(rstd), _stream(x)))
+  ctx.save_for_backward(x2, g32, mean, rstd)
+  ctx.eps, ctx.shape, ctx.params = eps, shape, (gamma, beta)
+  return y.view(shape)
+
+
+def _ln_backward(ctx, dy, din=None):
+  """(dx, dgamma, dbeta) for autograd; `din`: a gradient that reached the input another way, added to dx by the kernel."""
+  x2, gamma, mean, rstd = ctx.saved_tensors
+  dy2 = dy.reshape(x2.shape).contiguous()
+  din = None if din is None else din.reshape(x2.shape).contiguous()
+  dx = torch.empty_like(x2)
+  d = _desc(x2, ctx.eps)
+  (dg, db), done = _param_grads(d, ctx.params, (gamma, gamma))
+  ws = _ws(d, x2)
+  ins, outs = (d, _p(dy2), _p(x2), _p(gamma), _p(mean), _p(rstd)), (_p(dx), _p(dg), _p(db), _p(ws), ws.numel(), _stream(x2))
+  with torch.cuda.device(x2.device):
+    L = _lib.lib()
+    _lib.check(L.mmt_ln_bwd(*ins, *outs) if din is None else L.mmt_ln_bwd_add(*ins, _p(din), *outs))
+  return (dx.view(ctx.shape), *done(ws, 0))
 
 
 class _LayerNormFn(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, x, gamma, beta, eps):
-    _check(x, gamma, beta)
-    shape = x.shape
-    x2 = x.reshape(-1, shape[-1]).contiguous()
-    gamma_p, beta_p = gamma, beta
-    gamma, beta = _f32(gamma), _f32(beta)
-    y = torch.empty_like(x2)
-    mean = torch.empty(x2.shape[0], dtype=torch.float32, device=x.device)
-    rstd = torch.empty_like(mean)
-    d = _desc(x2, eps)
-    with torch.cuda.device(x.device):
-      _lib.check(_lib.lib().mmt_ln_fwd(d, _p(x2), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), _stream(x)))
-    ctx.save_for_backward(x2, gamma, mean, rstd)
-    ctx.eps, ctx.shape = eps, shape
-    ctx.params = (gamma_p, beta_p)
-    return y.view(shape)
+    return _ln_forward(ctx, x, gamma, beta, eps)
 
   @staticmethod
   def backward(ctx, dy):
-    x2, gamma, mean, rstd = ctx.saved_tensors
-    gamma_p, beta_p = ctx.params
-    dy2 = dy.reshape(x2.shape).contiguous()
-    dx = torch.empty_like(x2)
-    (dg, dg_direct), (db, db_direct) = _grad_target(gamma_p, gamma), _grad_target(beta_p, gamma)
-    direct = dg_direct and db_direct
-    if not direct:
-      dg, db = torch.empty_like(gamma), torch.empty_like(gamma)
-    d = _desc(x2, ctx.eps)
-    d.accumulate = int(direct)
-    d.defer_reduce = int(_defer_colsum_ok(direct, gamma_p, beta_p))
-    ws = _ws(d, x2)
-    with torch.cuda.device(x2.device):
-      _lib.check(_lib.lib().mmt_ln_bwd(d, _p(dy2), _p(x2), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dg),
-                                       _p(db), _p(ws), ws.numel(), _stream(x2)))
-    if d.defer_reduce:
-      _defer_colsum(ws, x2.shape[0], x2.shape[1], 0, (dg, db))
-    return dx.view(ctx.shape), _finish(gamma_p, dg, direct), _finish(beta_p, db, direct), None
+    return (*_ln_backward(ctx, dy), None)
 
 
 def layer_norm(x, gamma, beta, eps=1e-12):
@@ -247,45 +203,13 @@ class _LayerNormKeepFn(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, x, gamma, beta, eps):
-    _check(x, gamma, beta)
-    shape = x.shape
-    x2 = x.reshape(-1, shape[-1]).contiguous()
-    gamma_p, beta_p = gamma, beta
-    gamma, beta = _f32(gamma), _f32(beta)
-    y = torch.empty_like(x2)
-    mean = torch.empty(x2.shape[0], dtype=torch.float32, device=x.device)
-    rstd = torch.empty_like(mean)
-    d = _desc(x2, eps)
-    with torch.cuda.device(x.device):
-      _lib.check(_lib.lib().mmt_ln_fwd(d, _p(x2), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), _stream(x)))
-    ctx.save_for_backward(x2, gamma, mean, rstd)
-    ctx.eps, ctx.shape = eps, shape
-    ctx.params = (gamma_p, beta_p)
-    return x.view_as(x), y.view(shape)
+    return x.view_as(x), _ln_forward(ctx, x, gamma, beta, eps)
 
   @staticmethod
   def backward(ctx, dx_alias, dy):
-    x2, gamma, mean, rstd = ctx.saved_tensors
-    gamma_p, beta_p = ctx.params
     if dy is None:
       return dx_alias, None, None, None
-    dy2 = dy.reshape(x2.shape).contiguous()
-    din = None if dx_alias is None else dx_alias.reshape(x2.shape).contiguous()
-    dx = torch.empty_like(x2)
-    (dg, dg_direct), (db, db_direct) = _grad_target(gamma_p, gamma), _grad_target(beta_p, gamma)
-    direct = dg_direct and db_direct
-    if not direct:
-      dg, db = torch.empty_like(gamma), torch.empty_like(gamma)
-    d = _desc(x2, ctx.eps)
-    d.accumulate = int(direct)
-    d.defer_reduce = int(_defer_colsum_ok(direct, gamma_p, beta_p))
-    ws = _ws(d, x2)
-    with torch.cuda.device(x2.device):
-      _lib.check(_lib.lib().mmt_ln_bwd_add(d, _p(dy2), _p(x2), _p(gamma), _p(mean), _p(rstd), _p(din), _p(dx), _p(dg),
-                                           _p(db), _p(ws), ws.numel(), _stream(x2)))
-    if d.defer_reduce:
-      _defer_colsum(ws, x2.shape[0], x2.shape[1], 0, (dg, db))
-    return dx.view(ctx.shape), _finish(gamma_p, dg, direct), _finish(beta_p, db, direct), None
+    return (*_ln_backward(ctx, dy, dx_alias), None)
 
 
 def layer_norm_keep(x, gamma, beta, eps=1e-12):
@@ -329,29 +253,15 @@ class _ResidualBlockFn(torch.autograd.Function):
     if has_ln and dh2 is None:
       dh2 = torch.zeros_like(x_new)
     d_o, dx = torch.empty_like(x_new), torch.empty_like(x_new)
-    bias_p, gamma_p, beta_p = ctx.params
-    dbias, direct = _grad_target(bias_p, bias)
-    dg = db = None
-    if has_ln:
-      (dg, d1), (db, d2) = _grad_target(gamma_p, gamma), _grad_target(beta_p, gamma)
-      direct = direct and d1 and d2
-    if not direct:
-      dbias = torch.empty_like(bias)
-      dg = torch.empty_like(gamma) if has_ln else None
-      db = torch.empty_like(gamma) if has_ln else None
     d = _desc(x_new, eps, p, seed)
-    d.accumulate = int(direct)
-    d.defer_reduce = int(_defer_colsum_ok(direct, bias_p, gamma_p, beta_p))
+    (dbias, dg, db), done = _param_grads(d, ctx.params, (bias, gamma, gamma))    # (gamma is None without the LayerNorm)
     ws = _ws(d, x_new)
     with torch.cuda.device(x_new.device):
       _lib.check(_lib.lib().mmt_residual_block_bwd(
           d, _p(dxn), _p(dh2), _p(x_new), _p(gamma), _p(mean), _p(rstd), _p(d_o), _p(dx), _p(dbias),
           _p(dg), _p(db), _p(ws), ws.numel(), _stream(x_new)))
-    if d.defer_reduce:
-      _defer_colsum(ws, x_new.shape[0], x_new.shape[1], 1 if has_ln else 2, (dbias, dg, db) if has_ln else (dbias,))
-    return (d_o.view(shape), _finish(bias_p, dbias, direct), dx.view(shape),
-            _finish(gamma_p, dg, direct) if has_ln else None,
-            _finish(beta_p, db, direct) if has_ln else None, None, None, None)
+    g_bias, g_gamma, g_beta = done(ws, 1 if has_ln else 2)
+    return d_o.view(shape), g_bias, dx.view(shape), g_gamma, g_beta, None, None, None
 
 
 def residual_block(o, bias, x, gamma=None, beta=None, eps=1e-12, p=0.0, seed=0):
@@ -381,17 +291,13 @@ class _BiasGeluFn(torch.autograd.Function):
     u2, bias = ctx.saved_tensors
     dy2 = dy.reshape(u2.shape).contiguous()
     du = torch.empty_like(u2)
-    dbias, direct = _grad_target(ctx.param, bias)
     d = _desc(u2)
-    d.accumulate = int(direct)
-    d.defer_reduce = int(_defer_colsum_ok(direct, ctx.param))
+    (dbias,), done = _param_grads(d, (ctx.param,), (bias,))
     ws = _ws(d, u2)
     with torch.cuda.device(u2.device):
       _lib.check(_lib.lib().mmt_bias_gelu_bwd(d, _p(dy2), _p(u2), _p(bias), _p(du), _p(dbias), _p(ws),
                                               ws.numel(), _stream(u2)))
-    if d.defer_reduce:
-      _defer_colsum(ws, u2.shape[0], u2.shape[1], 3, (dbias,))
-    return du.view(ctx.shape), _finish(ctx.param, dbias, direct)
+    return (du.view(ctx.shape), *done(ws, 3))
 
 
 def bias_gelu_forward_(u2: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
@@ -406,7 +312,6 @@ def bias_gelu_forward_(u2: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
 def bias_gelu(u, bias):
   """gelu_tanh(u + bias)."""
   return _BiasGeluFn.apply(u, bias)
-
 
 
 def _ffn_gemm_ok(a: torch.Tensor, w: torch.Tensor, M: int, N: int, K: int) -> bool:
@@ -478,21 +383,28 @@ def accumulate_grad_(acc: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
   return acc
 
 
+def _wgrad_layout_ok(dw, dy, x, dbias, m_multiple: int, k_multiple: int) -> bool:
+  """What the weight-gradient kernels take: dw fp32 [M,N], dy [K,M] and x [K,N] bf16 with unit column stride, rows and
+  bases aligned for 16-byte accesses, dbias fp32 [M] contiguous on dw's device; M, K multiples of what the kernel tiles."""
+  K, M = dy.shape
+  N = x.shape[1]
+  return (dw.is_cuda and dw.dtype == torch.float32 and dy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16
+          and dw.shape == (M, N) and x.shape[0] == K and M % m_multiple == 0 and N % 256 == 0 and K % k_multiple == 0
+          and K > 0 and dw.stride(1) == 1 and dy.stride(1) == 1 and x.stride(1) == 1
+          and dy.stride(0) % 8 == 0 and x.stride(0) % 8 == 0 and dy.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0
+          and dw.stride(0) % 4 == 0 and dw.data_ptr() % 16 == 0
+          and (dbias is None or (dbias.dtype == torch.float32 and dbias.is_contiguous() and dbias.numel() == M
+                                 and dbias.device == dw.device)))
+
+
 def wgrad_accumulate_(dw: torch.Tensor, dy: torch.Tensor, x: torch.Tensor, dbias: Optional[torch.Tensor] = None) -> bool:
   """dw (fp32 [M,N]) += dy[K,M]^T @ x[K,N] (bf16) with the hand-written split-K kernel; with
   `dbias` (fp32 [M], contiguous) also dbias += dy.sum(0) from the same pass over dy.
   Returns False (nothing done) when the shape/layout is outside what the kernel is built for."""
+  if not _wgrad_layout_ok(dw, dy, x, dbias, 128, 1):
+    return False
   K, M = dy.shape
   N = x.shape[1]
-  ok = (dw.is_cuda and dw.dtype == torch.float32 and dy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16
-        and dw.shape == (M, N) and x.shape[0] == K and M % 128 == 0 and N % 256 == 0 and K > 0
-        and dw.stride(1) == 1 and dy.stride(1) == 1 and x.stride(1) == 1
-        and dy.stride(0) % 8 == 0 and x.stride(0) % 8 == 0 and dy.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0
-        and dw.stride(0) % 4 == 0 and dw.data_ptr() % 16 == 0
-        and (dbias is None or (dbias.dtype == torch.float32 and dbias.is_contiguous() and dbias.numel() == M
-                               and dbias.device == dw.device)))
-  if not ok:
-    return False
   L = _lib.lib()
   ws = _wgrad_ws(dw.device, L.mmt_wgrad_workspace_bytes(M, N, K))
   with torch.cuda.device(dw.device):
@@ -503,32 +415,8 @@ def wgrad_accumulate_(dw: torch.Tensor, dy: torch.Tensor, x: torch.Tensor, dbias
 
 
 # ---- weight gradients: grouped launches -----------------------------------------------------------------
-_GRAPH_TASK_ID = getattr(torch._C, '_current_graph_task_id', None)
-
-
-def _graph_task_id():
-  return _GRAPH_TASK_ID() if _GRAPH_TASK_ID is not None else -1
-
-
-def grouping_is_safe() -> bool:
-  """The queues of grouped weight-gradient products tell a new backward pass from a stale one by autograd's graph-task
-  id.  Without that symbol every pass would look alike and products left behind by a backward that raised would be
-  launched (with dead operands) by the next one: fail closed -- no grouping, every product launched on its own."""
-  return _GRAPH_TASK_ID is not None
-
-
 def _wgrad_groupable(dw, dy, x, dbias) -> bool:
-  K, M = dy.shape
-  N = x.shape[1]
-  if not grouping_is_safe():
-    return False
-  return (dw.is_cuda and dw.dtype == torch.float32 and dy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16
-          and dw.shape == (M, N) and x.shape[0] == K and M % 256 == 0 and N % 256 == 0 and K % 64 == 0 and K > 0
-          and dw.stride(1) == 1 and dy.stride(1) == 1 and x.stride(1) == 1 and dy.stride(0) % 8 == 0
-          and x.stride(0) % 8 == 0 and dy.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0 and dw.stride(0) % 4 == 0
-          and dw.data_ptr() % 16 == 0
-          and (dbias is None or (dbias.dtype == torch.float32 and dbias.is_contiguous() and dbias.numel() == M
-                                 and dbias.device == dw.device)))
+  return grouping_is_safe() and _wgrad_layout_ok(dw, dy, x, dbias, 256, 64)
 
 
 # Weight-gradient products waiting to be launched together (per device): the four Dense layers of an encoder
@@ -551,57 +439,40 @@ def _launch_wgrad_group(items, device) -> None:
   L = _lib.lib()
   stream = torch.cuda.current_stream(device)
   if len(items) == 1:
-    dw, dy, x, dbias = items[0][:4]
-    if not wgrad_accumulate_(dw, dy, x, dbias):
+    only, = items
+    if not wgrad_accumulate_(only.dw, only.dy, only.x, only.dbias):
       raise RuntimeError('mmt_wgrad_accumulate refused a shape _wgrad_groupable admitted')
     return
-  K = items[0][1].shape[0]
+  K = items[0].dy.shape[0]
   arr = (_lib.WgradProblem * len(items))()
-  for q, (dw, dy, x, dbias, *_) in zip(arr, items):
-    q.dw, q.ldw, q.dbias = dw.data_ptr(), dw.stride(0), (None if dbias is None else dbias.data_ptr())
-    q.dy, q.ldy, q.x, q.ldx = dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0)
-    q.M, q.N = dy.shape[1], x.shape[1]
+  for q, it in zip(arr, items):
+    q.dw, q.ldw, q.dbias = it.dw.data_ptr(), it.dw.stride(0), _p(it.dbias)
+    q.dy, q.ldy, q.x, q.ldx = it.dy.data_ptr(), it.dy.stride(0), it.x.data_ptr(), it.x.stride(0)
+    q.M, q.N = it.dy.shape[1], it.x.shape[1]
   ws = _wgrad_ws(device, max(16, L.mmt_wgrad_group_workspace_bytes(len(items), arr, K)))
   with torch.cuda.device(device):
     _lib.check(L.mmt_wgrad_grouped(len(items), arr, K, ws.data_ptr(), ws.numel(), stream.cuda_stream))
 
 
-# The products are queued and launched together on the CURRENT stream, and only then are the
-# parameters reported ready -- the reducer ignores autograd's own post-accumulate notification for a parameter
-# while `_mmt_grad_deferred` is set, so a bucket's all-reduce can never be enqueued ahead of its last product.
-# (device, graph-task id) -> (graph-task id, [(dw, dy, x, dbias, notify, output ranges)]), keyed as `_cs_deferred` is.
-_wg_deferred = {}
+# The products are queued and launched together on the CURRENT stream, and only then are the parameters reported ready
+# (`deferred.mark_grad_deferred`).  The queue is a `deferred.DeferredLaunches` like that of the reduces; its own rules:
+# one launch has one K (the rows the products contract), and its size depends on whether a reducer listens (above).
+def _products_launched(items) -> None:
+  still_queued = {id(prm) for item in _wg_deferred.queued() for prm in item.notify}
+  for prm in [prm for item in items for prm in item.notify if id(prm) not in still_queued]:
+    clear_grad_deferred(prm)                   # (a parameter used again later in the pass is reported at that launch)
+    notify_grad_ready(prm)
 
 
-def _flush_wgrad_deferred(key) -> None:
-  entry = _wg_deferred.pop(key, None)
-  if not entry or not entry[1]:
-    return
-  items = entry[1]
-  _launch_wgrad_group(items, key[0])
-  still_queued = {id(prm) for e in _wg_deferred.values() for item in e[1] for prm in item[4]}
-  for item in items:
-    for prm in item[4]:
-      if id(prm) not in still_queued:          # (a parameter used again later in the pass is reported at that launch)
-        prm._mmt_grad_deferred = False
-        for hook in getattr(prm, '_mmt_grad_ready_hooks', ()):
-          hook(prm)
+def _wg_limit(items) -> int:
+  exchanged = any(getattr(prm, '_mmt_grad_ready_hooks', ()) for item in items for prm in item.notify)
+  return _WG_GROUP if exchanged else _WG_GROUP_ALONE
 
 
-def reset_host_queues() -> None:
-  """Forgets every weight-gradient product and column-sum reduce a backward pass has queued but not launched.  For a step
-  that was ABANDONED half-way (a graph capture that raised inside backward, `graphed.py`): its queued products point at
-  activations of a step that never ran; the retry must not launch them."""
-  for queue in (_cs_deferred, _wg_deferred):
-    _drop_entries(queue, list(queue))
-
-
-def _flush_all_deferred():
-  """End-of-backward callback: the products of the pass that is ending (the callback runs under its graph-task id)."""
-  gid = _graph_task_id()
-  for key in [k for k in _wg_deferred if k[1] == gid]:
-    _flush_wgrad_deferred(key)
-  _forget_passes_after(gid)
+_wg_deferred = DeferredLaunches(
+    launch=lambda items, device: _launch_wgrad_group(items, device), limit=_wg_limit,
+    may_join=lambda items, item: items[0].dy.shape[0] == item.dy.shape[0], on_launched=_products_launched,
+    on_queued=lambda item: mark_grad_deferred(*item.notify), on_dropped=lambda item: clear_grad_deferred(*item.notify))
 
 
 def wgrad_accumulate_deferred_(dw, dy, x, dbias, notify) -> bool:
@@ -610,29 +481,8 @@ def wgrad_accumulate_deferred_(dw, dy, x, dbias, notify) -> bool:
   takes (the caller launches and notifies at once)."""
   if _WG_GROUP <= 1 or not _wgrad_groupable(dw, dy, x, dbias):
     return False
-  gid = _graph_task_id()
-  key = (dw.device, gid)
-  _forget_passes_after(gid)
   ranges = (_byte_range(dw),) + (() if dbias is None else (_byte_range(dbias),))
-  entry = _wg_deferred.get(key)
-  if entry is not None and entry[1] and entry[1][0][1].shape[0] != dy.shape[0]:
-    _flush_wgrad_deferred(key)
-    entry = None
-  # an output a queued product adds to as well (a weight or bias used twice in this pass, or a view into the same
-  # gradient buffer): the tiles of one launch are added by different workgroups with plain loads and stores, so the
-  # queue is launched first and this product goes into the next one, stream-ordered behind it
-  if entry is not None and any(_ranges_overlap(ranges, item[5]) for item in entry[1]):
-    _flush_wgrad_deferred(key)
-    entry = None
-  if entry is None:
-    entry = _wg_deferred[key] = (gid, [])
-    torch.autograd.Variable._execution_engine.queue_callback(_flush_all_deferred)    # end of this backward pass
-  for prm in notify:
-    prm._mmt_grad_deferred = True
-  entry[1].append((dw, dy, x, dbias, tuple(notify), ranges))
-  exchanged = any(getattr(prm, '_mmt_grad_ready_hooks', ()) for item in entry[1] for prm in item[4])
-  if len(entry[1]) >= (_WG_GROUP if exchanged else _WG_GROUP_ALONE):
-    _flush_wgrad_deferred(key)
+  _wg_deferred.add(dw.device, Product(dw, dy, x, dbias, tuple(notify), ranges))
   return True
 
 

@@ -16,6 +16,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import fused, ops
+from .deferred import notify_grad_ready
 
 
 def truncated_normal_(t: torch.Tensor, stddev: float) -> torch.Tensor:
@@ -72,8 +73,7 @@ class _CastParamFn(torch.autograd.Function):
       param.grad = g.to(param.dtype)
     else:
       fused.accumulate_grad_(param.grad, g)
-    for hook in getattr(param, '_mmt_grad_ready_hooks', ()):
-      hook(param)
+    notify_grad_ready(param)
     return None, None
 
 
@@ -90,11 +90,6 @@ def cast_param(param: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
 def _param_weight(param: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
   shadow = _current_shadow(param, dtype)
   return shadow if shadow is not None else param.detach().to(dtype)
-
-
-def _notify(param):
-  for hook in getattr(param, '_mmt_grad_ready_hooks', ()):
-    hook(param)
 
 
 def _add_bias_grad(bias, dy2):
@@ -127,7 +122,7 @@ def _accumulate_dense_grads(weight, bias, dy2, x2):
       # queued with the block's other weight gradients; the parameters are reported ready at the launch
       if want_b and not fuse_b:
         _add_bias_grad(bias, dy2)
-        _notify(bias)
+        notify_grad_ready(bias)
       return
     wgrad = fused.wgrad_accumulate_
     if weight.grad.dtype == torch.float32 and wgrad(weight.grad, dy2, x2, bias.grad if fuse_b else None):
@@ -136,11 +131,11 @@ def _accumulate_dense_grads(weight, bias, dy2, x2):
       fused.accumulate_grad_(weight.grad, torch.mm(dy2.t(), x2))
     else:
       weight.grad.add_(torch.mm(dy2.t(), x2))
-    _notify(weight)
+    notify_grad_ready(weight)
   if want_b:
     if not b_done:
       _add_bias_grad(bias, dy2)
-    _notify(bias)
+    notify_grad_ready(bias)
 
 
 class _LinearFn(torch.autograd.Function):

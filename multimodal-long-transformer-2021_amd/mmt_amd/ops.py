@@ -32,6 +32,7 @@ from typing import Optional
 import torch
 
 from . import _lib, step_scalars
+from .deferred import notify_grad_ready
 
 
 @dataclasses.dataclass(frozen=True)
@@ -547,8 +548,8 @@ class _RelativeAttentionQkvFn(torch.autograd.Function):
         grads_out=(dqkv[:, :, 0], dqkv[:, :, 1], dqkv[:, :, 2]), rel_grads_accum=accum, **kw)
     if accum is not None:
       for p in ctx.sinks:
-        for hook in getattr(p, '_mmt_grad_ready_hooks', ()) if p is not None else ():
-          hook(p)
+        if p is not None:
+          notify_grad_ready(p)
       return dqkv, None, None, None, None
     de = None if de is None else de.to(rel_emb.dtype)
     db = None if db is None else db.to(rel_bias.dtype)

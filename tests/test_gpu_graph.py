@@ -198,7 +198,7 @@ def test_a_capture_that_fails_inside_backward_leaves_no_queued_work(monkeypatch)
       seen['calls'] += 1
       if seen['calls'] == 2:            # the second attention backward of the pass: layers above it have run theirs
         seen['raised'] = 1
-        seen['queued'] = sum(len(e[1]) for e in fused._wg_deferred.values())
+        seen['queued'] = len(fused._wg_deferred.queued())
         seen['ready'] = len(gs.reducer._ready) + sum(1 for p in gs.model.parameters() if getattr(p, '_mmt_grad_deferred', False))
         raise RuntimeError('not capturable (test)')
     return real(*a, **k)

@@ -1,5 +1,5 @@
-"""State that outlives a launch, host side (mmt_amd/fused.py: the queues of weight-gradient products and column-sum
-reduces that one launch at the end of a backward pass serves): the REAL queue code on CPU tensors, with only the launches
+"""State that outlives a launch, host side (mmt_amd/deferred.py, and fused.py's two instances of its queue: weight-gradient
+products and column-sum reduces that one launch at the end of a backward pass serves): the REAL queue code on CPU tensors, with only the launches
 replaced by recorders that do the arithmetic in fp32 and log what one launch was given.  Plus the refusals of the C
 boundary, which run before any launch.  No GPU."""
 import contextlib
@@ -25,7 +25,8 @@ class Recorder:
 
   def wgrad(self, items, device):
     group = []
-    for dw, dy, x, dbias, *_ in items:
+    for item in items:
+      dw, dy, x, dbias = item.dw, item.dy, item.x, item.dbias
       self.keep.append(dy)
       dw += dy.float().t() @ x.float()
       ranges = [_range(dw)]
@@ -38,7 +39,8 @@ class Recorder:
 
   def colsum(self, items, device):
     group = []
-    for ws, rows, H, kind, outs, *_ in items:          # (the toy layers leave their finished sums in the "workspace")
+    for item in items:                                 # (the toy layers leave their finished sums in the "workspace")
+      ws, outs = item.ws, item.outs
       self.keep.append(ws)
       for o, part in zip(outs, ws):
         o += part
@@ -296,7 +298,7 @@ def test_a_backward_that_raises_leaves_nothing_a_later_pass_launches(rec, monkey
   monkeypatch.setattr(ToyDense, 'raise_here', staticmethod(lambda weight: weight is w1))
   with pytest.raises(RuntimeError, match='fails here'):
     y.backward(torch.ones_like(y))
-  assert sum(len(e[1]) for e in fused._wg_deferred.values()) == 2 and sum(len(e[1]) for e in fused._cs_deferred.values()) == 1
+  assert len(fused._wg_deferred.queued()) == 2 and len(fused._cs_deferred.queued()) == 1
   assert w3._mmt_grad_deferred and w2._mmt_grad_deferred
   assert not rec.launched
   monkeypatch.setattr(ToyDense, 'raise_here', staticmethod(lambda weight: False))
@@ -327,6 +329,94 @@ def test_reset_host_queues_empties_everything(rec, monkeypatch):
   assert not fused._wg_deferred and not fused._cs_deferred
   assert not any(getattr(p, '_mmt_grad_deferred', False) for level in params for p in level)
   assert not rec.launched
+
+
+# ---- when a queue launches: its limit, and which items may share a launch ---------------------------------------------
+
+def _outputs(group):
+  """First output range of every item of one recorded launch, in the launch's order."""
+  return [ranges[0] for _, _, ranges in group]
+
+
+def test_the_reduce_queue_launches_at_its_limit(rec):
+  """One more reduce than a batch holds, every one on an output of its own: a full batch is launched when the last
+  place is taken, the one left over at the end of backward, both in the order the reduces were queued."""
+  from mmt_amd import fused
+  n = fused._CS_MAX + 1
+  cs = [_param(N, seed=60 + i) for i in range(n)]
+  before = [c.grad.clone() for c in cs]
+  y = _x(59)
+  for c in cs:
+    y = ToyBias.apply(y, c)
+  dy = torch.randn(K, N, generator=torch.Generator().manual_seed(58)).bfloat16()
+  y.backward(dy)
+  rec.assert_no_launch_shares_an_output()
+  assert [len(g) for g in rec.groups] == [fused._CS_MAX, 1]
+  queued = [_range(c.grad) for c in reversed(cs)]            # (backward meets the layers last to first)
+  assert _outputs(rec.groups[0]) + _outputs(rec.groups[1]) == queued
+  for c, g in zip(cs, before):
+    assert torch.equal(c.grad, g + dy.float().sum(0))
+  assert not fused._cs_deferred
+
+
+def test_products_of_another_k_go_into_another_launch(rec):
+  """Products with K = 64, 64, 128, 128 on outputs of their own, queued in that order by one backward pass: two
+  launches of two, neither of them mixed (one grouped launch has one K)."""
+  from mmt_amd import fused
+  ws = [_param(M, N, seed=70 + i) for i in range(4)]
+  k_of = {_range(w.grad): k for w, k in zip(ws, (2 * K, 2 * K, K, K))}
+  xs = {k: _x(74 + k, rows=k) for k in (K, 2 * K)}
+  # the graph of the K = 128 pair is built first, so backward (latest node first) meets the K = 64 pair first
+  ys = [ToyDense.apply(ToyDense.apply(xs[k], a, None, _grads), b, None, _grads) for k, (a, b) in ((2 * K, ws[:2]), (K, ws[2:]))]
+  dys = [torch.randn(k, M, generator=torch.Generator().manual_seed(78 + k)).bfloat16() for k in (2 * K, K)]
+  torch.autograd.backward(ys, dys)
+  rec.assert_no_launch_shares_an_output()
+  assert [[k_of[r] for r in _outputs(g)] for g in rec.groups] == [[K, K], [2 * K, 2 * K]]
+  assert len(set(rec.launched)) == 4
+  assert not fused._wg_deferred
+  assert not any(getattr(w, '_mmt_grad_deferred', False) for w in ws)
+
+
+def _run_chain(rec, n, with_hooks):
+  """`n` dense layers in a row, every weight with a gradient of its own; with hooks, every call of one is logged as
+  (parameter, products launched so far, was its own product among them)."""
+  ws = [_param(M, N, seed=80 + i) for i in range(n)]
+  calls = []
+  if with_hooks:
+    launched_outputs = lambda: [r for g in rec.groups for r in _outputs(g)]
+    for w in ws:
+      w._mmt_grad_ready_hooks = (lambda q: calls.append((q, len(rec.launched), _range(q.grad) in launched_outputs())),)
+  y = _x(79)
+  for w in ws:
+    y = ToyDense.apply(y, w, None, _grads)
+  y.backward(torch.randn(K, M, generator=torch.Generator().manual_seed(78)).bfloat16())
+  return ws, calls
+
+
+def test_the_product_queue_launches_sooner_when_somebody_listens(rec):
+  """One more product than a block's group holds.  With gradient-ready hooks on the parameters (a reducer listens) the
+  queue launches when the group is full and again at the end of backward; every hook runs once, after the launch that
+  holds its parameter's product, and no parameter stays marked as queued.  Without hooks nobody waits: one launch at
+  the end of backward."""
+  from mmt_amd import fused
+  n = fused._WG_GROUP + 1
+  assert n < fused._WG_GROUP_ALONE
+  ws, calls = _run_chain(rec, n, True)
+  rec.assert_no_launch_shares_an_output()
+  assert [len(g) for g in rec.groups] == [fused._WG_GROUP, 1]
+  queued = [_range(w.grad) for w in reversed(ws)]
+  assert _outputs(rec.groups[0]) + _outputs(rec.groups[1]) == queued
+  assert [q for q, _, _ in calls] == list(reversed(ws))                      # once per parameter, in launch order
+  assert [seen for _, seen, _ in calls] == [fused._WG_GROUP] * fused._WG_GROUP + [n]    # the first launch came before the last product
+  assert all(own for _, _, own in calls)
+  assert not any(getattr(w, '_mmt_grad_deferred', False) for w in ws)
+  assert not fused._wg_deferred
+  rec.groups.clear(); rec.launched.clear()
+  ws, calls = _run_chain(rec, n, False)
+  assert [len(g) for g in rec.groups] == [n] and not calls
+  assert _outputs(rec.groups[0]) == [_range(w.grad) for w in reversed(ws)]
+  assert not any(getattr(w, '_mmt_grad_deferred', False) for w in ws)
+  assert not fused._wg_deferred
 
 
 # ---- the C boundary ----------------------------------------------------------------------------------------------------

@@ -281,8 +281,20 @@ _LAMB_DEFAULTS = {'weight_decay_rate': 0.0, 'exclude_from_weight_decay': [], 'ex
 @dataclasses.dataclass
 class TrainerConfig(Config):
   train_steps: int = 1000000
+  # steps_per_loop / summary_interval are read in the trainer's loop mode (train.py: `summaries=True`, which the command
+  # line passes unless --no_summaries, or a recovery_max_trials): the loss and the train metrics accumulate on the device
+  # and are read once per loop of steps_per_loop steps; at loop ends that are multiples of summary_interval (a multiple of
+  # steps_per_loop, checked before the first train step) rank 0 writes them to model_dir/train as TensorBoard scalars, and
+  # every evaluation's result to model_dir/<validation_summary_subdir> (TFM's name, recalled and not pinned)
   steps_per_loop: int = 100
   summary_interval: int = 100
+  validation_summary_subdir: str = 'validation'
+  # TFM's recovery rule, checked at every loop end on the loop's mean loss: not finite, or above loss_upper_bound from
+  # step recovery_begin_steps on, restores the latest checkpoint of model_dir, at most recovery_max_trials times (then a
+  # RuntimeError; 0 = fail on the first bad loop).  None: no check, no recovery
+  recovery_max_trials: Optional[int] = None
+  recovery_begin_steps: int = 0
+  loss_upper_bound: float = 1e6
   checkpoint_interval: int = 1000
   max_to_keep: int = 5
   validation_interval: int = 1000

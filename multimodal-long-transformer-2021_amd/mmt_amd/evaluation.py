@@ -1,7 +1,8 @@
 """The validation loop of the trainer: `evaluate` runs `task.validation_step` over `task.validation_data` without
 gradients and reads the metrics once at the end; `GraphedEvalStep` records that forward-only step once as a HIP graph
 and replays it; `BestCheckpointExporter` keeps the checkpoint with the best value of one reported metric;
-`evaluation_due` is the schedule.  DESIGN.md section 4, "Validation loop".
+`evaluation_due` is the schedule, `loop_end_due` the one of the trainer's loops beside it.  DESIGN.md section 4,
+"Validation loop".
 
 The reference gets all of this from TFM's trainer: `trainer.validation_interval` / `validation_steps` drive
 `orbit.Controller.evaluate`, the `validation_loss` is a `Mean` over the batches' losses (unweighted per batch), and
@@ -40,6 +41,27 @@ def evaluation_due(step: int, interval: int, train_steps: int) -> bool:
   if step == train_steps:
     return True
   return interval > 0 and step > 0 and step % interval == 0
+
+
+def loop_end_due(step: int, steps_per_loop: int, train_steps: int) -> bool:
+  """Does a trainer loop end after train step `step` (counted from 1, steps before a resume included)?  At every
+  positive multiple of `steps_per_loop` and at `train_steps`."""
+  step, steps_per_loop, train_steps = int(step), int(steps_per_loop), int(train_steps)
+  if step == train_steps:
+    return True
+  return step > 0 and step % steps_per_loop == 0
+
+
+def check_loop_startup(trainer_cfg) -> None:
+  """What a run in loop mode checks before its first train step: `steps_per_loop` and `summary_interval` are at least 1,
+  and summaries fall on loop ends (`summary_interval` a multiple of `steps_per_loop`, as orbit requires).  ValueError
+  naming both values."""
+  per_loop, interval = int(trainer_cfg.steps_per_loop), int(trainer_cfg.summary_interval)
+  if per_loop < 1 or interval < 1:
+    raise ValueError(f'trainer.steps_per_loop ({per_loop}) and trainer.summary_interval ({interval}) must both be at least 1')
+  if interval % per_loop != 0:
+    raise ValueError(f'trainer.summary_interval ({interval}) must be a multiple of trainer.steps_per_loop ({per_loop}): '
+                     f'summaries are written at loop ends')
 
 
 def reported_names(task) -> List[str]:

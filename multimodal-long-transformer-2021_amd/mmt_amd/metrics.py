@@ -64,6 +64,11 @@ class Metric:
       return torch.zeros(self.n_state, dtype=torch.float32)
     return _dist_sum_(self.state.clone())
 
+  def result_of(self, state: torch.Tensor) -> torch.Tensor:
+    """The result from given sums (`synced_state()`'s, or a copy of them on another device): `result()` without the
+    all-reduce."""
+    raise NotImplementedError
+
 
 class Mean(Metric):
   """`tf.keras.metrics.Mean`: weighted running mean, total / count with divide_no_nan."""
@@ -80,7 +85,9 @@ class Mean(Metric):
       st[1] += w.sum()
 
   def result(self) -> torch.Tensor:
-    st = self.synced_state()
+    return self.result_of(self.synced_state())
+
+  def result_of(self, st: torch.Tensor) -> torch.Tensor:
     return _divide_no_nan(st[0], st[1])
 
 
@@ -133,7 +140,10 @@ class AUC(Metric):
     st[3] += (~pred_pos * wp).sum(1)
 
   def result(self) -> torch.Tensor:
-    st = self.synced_state().view(4, self.num_thresholds)
+    return self.result_of(self.synced_state())
+
+  def result_of(self, st: torch.Tensor) -> torch.Tensor:
+    st = st.view(4, self.num_thresholds)
     tp, fp, tn, fn = st[0], st[1], st[2], st[3]
     n = self.num_thresholds
     if self.curve == 'PR':
